@@ -24,10 +24,18 @@ torch.distributed.run child, created before anything in this process touches
 the GPU) and forwards the child's JSON line and exit code; under a launcher
 (RANK / WORLD_SIZE set) it is one of the ranks.
 
-The default run (one GPU, no overrides) times C3 -- the configuration the north star quotes -- and then, in
-the same process, a few steps of C2, C4 and C5, one Newton-Raphson smoothing pass on the 125 k-site slice of
-C3 and one SPR round on the 25 k-site slice of C5 (the per-GPU shares of an 8-way split): their figures go
-into `also` of the same line (`--no-also` skips them).
+A plain run (`--gpus 1 --steps N --warmup W`) sets up C3 -- the configuration the north star quotes --,
+warms up, times the N steps and prints the line: nothing else.  `--full` adds what takes time or runs of its
+own: the CPU baseline and the parity sample against the oracle (`cpu_baseline`, `dlnl_per_site`), and for the
+default shape the two `rocprofv3 --pmc` traffic passes and, in the same process, a few steps of C2, C4 and C5,
+C3 with site repeats and evaluate-only, one Newton-Raphson smoothing pass on the 125 k-site slice of C3 and C4
+and one SPR round on the 25 k-site slice of C5 (the per-GPU shares of an 8-way split): their figures go into
+`also` of the same line (`--no-also` skips them).
+
+`--dump-outputs DIR` writes what the last timed step computed, after the timing: `lnl.npy` (the summed lnL the
+step returns, float64) and `persite_lnl.npy` (float64: the per-site lnL at the root edge of the sites on rank 0,
+partitions in order; above 6 M sites a fixed, seeded sample of them, whose site numbers go to
+`persite_lnl_sites.npy`).  The inputs are seeded: the same arguments give the same inputs in every run.
 
 Prints ONE JSON line on rank 0.
 """
@@ -83,17 +91,22 @@ def parse_args():
     ap.add_argument("--transient", action="store_true",
                     help="evaluate-only traversals (pllhip_eval_set_transient): the vectors inside operation chains stay in "
                          "registers; what a model-parameter optimiser's full evaluations need")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: CPU baseline + parity sample against the oracle, and for "
+                         "the default shape the rocprofv3 --pmc traffic passes and the `also` legs (off: a lean timed run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"],
                     help="roofline.traffic from two rocprofv3 --pmc child passes of this very command (FETCH_SIZE, WRITE_SIZE), "
-                         "started before this process touches the GPU; auto: for the default line only")
+                         "started before this process touches the GPU; auto: for the default line of --full only")
     ap.add_argument("--tree", default="random", choices=["random", "ladder", "balanced"],
                     help="tree shape: random stepwise addition (seed 42, the benchmark's), a caterpillar, a complete binary tree")
     ap.add_argument("--as-rank", default="",
                     help="R/N: run, on ONE GPU and without a reduction, the share rank R of N would hold (the cost-balanced "
                          "partition assignment of --config c4); `value` then counts that share only")
     ap.add_argument("--no-also", action="store_true",
-                    help="default run only: skip the C2 / C4 / C5 / branch-length / SPR legs behind the C3 line")
+                    help="--full default run only: skip the C2 / C4 / C5 / branch-length / SPR legs behind the C3 line")
     ap.add_argument("--also-steps", type=int, default=5)
     ap.add_argument("--cpu-sites", type=int, default=0, help="sites of the CPU baseline sample")
     return ap.parse_args()
@@ -492,9 +505,26 @@ class Ctx:
         self.__dict__.update(kw)
 
 
-def run_leg(ctx, config, sites=0, taxa=0, steps=10, warmup=2, cpu="full"):
+# --dump-outputs: at most this many per-site values (float64: 48 MB); above it a fixed, seeded sample of the sites
+DUMP_MAX_SITES = 6_000_000
+
+
+def dump_outputs(outdir, ev, lnl):
+    """the arrays the last evaluation handed its caller: the lnL and the per-site lnL of the local partitions"""
+    os.makedirs(outdir, exist_ok=True)
+    persite = np.concatenate([ev.persite_lnl(k)[1] for k in range(len(ev.parts))]).astype(np.float64)
+    np.save(os.path.join(outdir, "lnl.npy"), np.array([lnl], dtype=np.float64))
+    if persite.size > DUMP_MAX_SITES:
+        pick = np.sort(np.random.default_rng(12345).choice(persite.size, DUMP_MAX_SITES, replace=False))
+        np.save(os.path.join(outdir, "persite_lnl_sites.npy"), pick.astype(np.float64))
+        persite = persite[pick]
+    np.save(os.path.join(outdir, "persite_lnl.npy"), persite)
+
+
+def run_leg(ctx, config, sites=0, taxa=0, steps=10, warmup=2, cpu="full", dump=""):
     """one timed workload (W1 on `config`); returns the JSON object of its line.
-    cpu: "full" = CPU baseline + parity sample, "parity" = parity sample only, None = neither"""
+    cpu: "full" = CPU baseline + parity sample, "parity" = parity sample only, None = neither;
+    dump: directory for the outputs of the last timed step (rank 0)"""
     pc, product, args = ctx.pc, ctx.product, ctx.args
     rank, world, dist, comm = ctx.rank, ctx.world, ctx.dist, ctx.comm
     states, rate_cats, ntips, nsites = pc.CONFIGS[config]
@@ -732,6 +762,8 @@ def run_leg(ctx, config, sites=0, taxa=0, steps=10, warmup=2, cpu="full"):
                   "algorithmic bytes of the partials launches / their HIP-event time (rank 0)",
     }
 
+    if dump and rank == 0:
+        dump_outputs(dump, ev, lnl)
     ev.close()                   # frees the CLVs: the parity sample below gets its own partitions
     cpu_base = parity = None
     if rank == 0 and world == 1 and not ctx.internal and cpu and not emulate:
@@ -903,7 +935,7 @@ def main():
     # kernel arguments in device memory (3 - 5 us per short launch, pll_core.hip): decided HERE, before any
     # library that initialises the HIP runtime is loaded, so that N = 1 and N > 1 run under the same setting
     os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
-    default_shape = (world == 1 and not internal and args.config == "c3" and not args.sites and not args.taxa and
+    default_shape = (args.full and world == 1 and not internal and args.config == "c3" and not args.sites and not args.taxa and
                      not args.rate_scalers and not args.no_also and not args.no_cpu_baseline and not args.site_repeats and
                      args.data == "random" and args.tree == "random" and not args.transient and not args.clv_tips)
     traffic_measured = None
@@ -970,11 +1002,11 @@ def main():
     ctx = Ctx(pc=pc, product=product, args=args, rank=rank, world=world, dist=dist, comm=comm,
               comm_mode=comm_mode, internal=internal, traffic=traffic_measured)
     out = run_leg(ctx, args.config, sites=args.sites, taxa=args.taxa, steps=args.steps, warmup=args.warmup,
-                  cpu=None if args.no_cpu_baseline else "full")
+                  cpu="full" if args.full and not args.no_cpu_baseline else None, dump=args.dump_outputs)
     out["runtime"] = {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG"),
                       "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
                       "torch_loaded_before_engine": world > 1}
-    default_run = (world == 1 and not internal and args.config == "c3" and not args.sites and not args.taxa and
+    default_run = (args.full and world == 1 and not internal and args.config == "c3" and not args.sites and not args.taxa and
                    not args.rate_scalers and not args.no_also and not args.no_cpu_baseline and not args.site_repeats and
                    args.data == "random" and args.tree == "random" and not args.transient)
     if default_run:

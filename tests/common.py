@@ -5,8 +5,10 @@ comparison utilities.  Everything here drives a library through the C ABI only.
 import json
 import math
 import os
+import subprocess
 
 import numpy as np
+import pytest
 
 import pllhip_ctypes as pc
 
@@ -24,6 +26,28 @@ FORCED = FORCED_REPEATS or FORCED_TRANSIENT
 def fixtures():
     with open(os.path.join(GOLDEN, "blopt_fixtures.json")) as f:
         return json.load(f)
+
+
+# ---------------------------------------------------------------------------
+# programs of the reference linked with the oracle (oracle/Makefile.ref -> oracle/_ref/, built by build())
+# ---------------------------------------------------------------------------
+def ref_program(name):
+    """path of oracle/_ref/<name>; made on demand where a pll-modules checkout is present, a skip where
+    there is none to build it from (the oracle itself must be built: request the `oracle` fixture first)"""
+    exe = os.path.join(ROOT, "oracle", "_ref", name)
+    if not os.path.exists(exe):
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "-f", "Makefile.ref"], check=True)
+    if not os.path.exists(exe):
+        pytest.skip(f"oracle/_ref/{name} not built: no pll-modules checkout to build it from (oracle/Makefile.ref)")
+    return exe
+
+
+def ref_env():
+    """environment of a reference program: the oracle build the tests load (PLLHIP_ORACLE_LIB) comes first"""
+    from conftest import ORACLE_LIB
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = os.pathsep.join(filter(None, [os.path.dirname(ORACLE_LIB), env.get("LD_LIBRARY_PATH")]))
+    return env
 
 
 # ---------------------------------------------------------------------------

@@ -1,11 +1,12 @@
 """Drop-in check of the boundary at the level pll-modules' clients use it.
 
-Where /root/reference is present, the reference's UNMODIFIED upper layers --
-src/tree/treeinfo.c, src/optimize/pll_optimize.c + opt_algorithms.c + lbfgsb,
-src/algorithm/algo_search.c / pllmod_algorithm.c / algo_callback.c and the tree
-utilities they pull in -- are compiled where they lie against include/pll.h and
-linked with this repository's library (the CPU oracle build of the same
-interface, since this container has no GPU).  A small client
+The reference's UNMODIFIED upper layers -- src/tree/treeinfo.c,
+src/optimize/pll_optimize.c + opt_algorithms.c + lbfgsb, src/algorithm/algo_search.c /
+pllmod_algorithm.c / algo_callback.c and the tree utilities they pull in -- are
+compiled where they lie against include/pll.h and linked with this repository's
+library (the CPU oracle build of the same interface, so that no GPU is needed) by
+oracle/Makefile.ref, which build() runs where a pll-modules checkout is present
+(the programs land in oracle/_ref/; without them these tests skip).  A small client
 (tests/dropin/treeinfo_driver.c) then runs a two-partition analysis: full and
 incremental likelihood, multi-partition Newton-Raphson branch-length
 optimisation, and one pllmod_algo_spr_round.  The reference's own internal
@@ -16,43 +17,26 @@ This is a test of the BOUNDARY (names, struct fields, semantics of ~35 libpll
 functions incl. the SPR/NNI primitives and the partial-traversal callbacks), not
 an oracle: the arithmetic underneath is this repository's.
 """
-import glob
 import os
 import re
 import subprocess
 
 import pytest
 
-from conftest import ROOT, ORACLE_LIB
+import common
 
-REF = "/root/reference"
-MODULES = ["src/pllmod_common.c", "src/tree/treeinfo.c", "src/tree/utree_operations.c",
-           "src/tree/rtree_operations.c", "src/tree/pll_tree.c", "src/tree/utree_constraint.c",
-           "src/tree/utree_distances.c", "src/tree/tree_hashtable.c", "src/tree/consensus.c",
-           "src/util/models.c", "src/util/models_dna.c", "src/util/models_gt.c", "src/util/models_mult.c",
-           "src/optimize/pll_optimize.c", "src/optimize/opt_algorithms.c",
-           "src/algorithm/algo_search.c", "src/algorithm/algo_callback.c",
-           "src/algorithm/pllmod_algorithm.c"]
+ENV = common.ref_env()
 
 
 @pytest.fixture(scope="module")
-def driver(oracle, tmp_path_factory):
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present on this box")
-    exe = tmp_path_factory.mktemp("dropin") / "ti_driver"
-    src = [os.path.join(ROOT, "tests", "dropin", "treeinfo_driver.c")]
-    src += [os.path.join(REF, m) for m in MODULES] + sorted(glob.glob(f"{REF}/src/optimize/lbfgsb/*.c"))
-    inc = sum((["-I", d] for d in [f"{ROOT}/include", f"{REF}/src", f"{REF}/src/optimize", f"{REF}/src/tree",
-                                   f"{REF}/src/algorithm", f"{REF}/src/util"]), [])
-    libdir = os.path.dirname(ORACLE_LIB)
-    subprocess.run(["gcc", "-std=gnu99", "-D_GNU_SOURCE", "-O2", "-w", *inc, "-o", str(exe), *src,
-                    "-L", libdir, "-lpll_oracle", "-lm", f"-Wl,-rpath,{libdir}"], check=True)
-    return str(exe)
+def driver(oracle):
+    """tests/dropin/treeinfo_driver.c with the reference's upper layers (oracle/_ref/ti_driver)"""
+    return common.ref_program("ti_driver")
 
 
 @pytest.mark.parametrize("args", [[], ["tv"]])
 def test_reference_treeinfo_blo_and_spr_round_run_on_this_library(driver, args):
-    out = subprocess.run([driver, *args], check=True, capture_output=True, text=True, timeout=600).stdout
+    out = subprocess.run([driver, *args], check=True, capture_output=True, text=True, timeout=600, env=ENV).stdout
     v = {k.strip(): float(x) for k, x in re.findall(r"^(.*?):\s+(-?[0-9.]+)$", out, re.M)}
     assert set(v) == {"direct lnL", "driver full lnL", "driver incremental", "driver after BLO",
                       "full lnL", "incremental lnL", "after BLO", "after SPR round", "full recomputation"}
@@ -69,18 +53,9 @@ def test_reference_treeinfo_blo_and_spr_round_run_on_this_library(driver, args):
 
 
 @pytest.fixture(scope="module")
-def linkage_driver(oracle, tmp_path_factory):
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present on this box")
-    exe = tmp_path_factory.mktemp("dropin") / "linkage_driver"
-    src = [os.path.join(ROOT, "tests", "dropin", "linkage_driver.c")]
-    src += [os.path.join(REF, m) for m in MODULES] + sorted(glob.glob(f"{REF}/src/optimize/lbfgsb/*.c"))
-    inc = sum((["-I", d] for d in [f"{ROOT}/include", f"{REF}/src", f"{REF}/src/optimize", f"{REF}/src/tree",
-                                   f"{REF}/src/algorithm", f"{REF}/src/util"]), [])
-    libdir = os.path.dirname(ORACLE_LIB)
-    subprocess.run(["gcc", "-std=gnu99", "-D_GNU_SOURCE", "-O2", "-w", *inc, "-o", str(exe), *src,
-                    "-L", libdir, "-lpll_oracle", "-lm", f"-Wl,-rpath,{libdir}"], check=True)
-    return str(exe)
+def linkage_driver(oracle):
+    """tests/dropin/linkage_driver.c with the reference's upper layers (oracle/_ref/linkage_driver)"""
+    return common.ref_program("linkage_driver")
 
 
 @pytest.mark.parametrize("mode", ["scaled", "unlinked"])
@@ -89,7 +64,7 @@ def test_scaled_and_unlinked_branch_lengths_match_the_reference(linkage_driver, 
     Newton-Raphson optimisation of this repository's driver against the reference's treeinfo +
     pllmod_algo_opt_brlen_treeinfo (src/tree/treeinfo.c:176-183, 849-852;
     src/optimize/pll_optimize.c:1223-1287, 1395-1712) on identical data"""
-    out = subprocess.run([linkage_driver, mode], check=True, capture_output=True, text=True, timeout=600).stdout
+    out = subprocess.run([linkage_driver, mode], check=True, capture_output=True, text=True, timeout=600, env=ENV).stdout
     v = {k.strip(): float(x) for k, x in re.findall(r"^(.*?):\s+(-?[0-9.]+)$", out, re.M)}
     assert abs(v["driver lnL"] - v["lnL"]) < 1e-6
     assert v["after BLO"] > v["lnL"] + 1.0
@@ -103,8 +78,8 @@ def test_scaled_and_unlinked_branch_lengths_match_the_reference(linkage_driver, 
 
 
 def test_tip_pattern_mode_gives_the_same_numbers(driver):
-    a = subprocess.run([driver], check=True, capture_output=True, text=True).stdout
-    b = subprocess.run([driver, "tv"], check=True, capture_output=True, text=True).stdout
+    a = subprocess.run([driver], check=True, capture_output=True, text=True, env=ENV).stdout
+    b = subprocess.run([driver, "tv"], check=True, capture_output=True, text=True, env=ENV).stdout
     assert a == b       # the reference's own cross-backend criterion (test/runtest.py:45-51)
 
 
@@ -182,18 +157,9 @@ def _brlens(nwk):
 
 
 @pytest.fixture(scope="module")
-def spr_driver(oracle, tmp_path_factory):
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present on this box")
-    exe = tmp_path_factory.mktemp("dropin_spr") / "spr_driver"
-    src = [os.path.join(ROOT, "tests", "dropin", "spr_driver.c")]
-    src += [os.path.join(REF, m) for m in MODULES] + sorted(glob.glob(f"{REF}/src/optimize/lbfgsb/*.c"))
-    inc = sum((["-I", d] for d in [f"{ROOT}/include", f"{REF}/src", f"{REF}/src/optimize", f"{REF}/src/tree",
-                                   f"{REF}/src/algorithm", f"{REF}/src/util"]), [])
-    libdir = os.path.dirname(ORACLE_LIB)
-    subprocess.run(["gcc", "-std=gnu99", "-D_GNU_SOURCE", "-O2", "-w", *inc, "-o", str(exe), *src,
-                    "-L", libdir, "-lpll_oracle", "-lm", f"-Wl,-rpath,{libdir}"], check=True)
-    return str(exe)
+def spr_driver(oracle):
+    """tests/dropin/spr_driver.c with the reference's upper layers (oracle/_ref/spr_driver)"""
+    return common.ref_program("spr_driver")
 
 
 @pytest.mark.parametrize("mode,ntaxa,radius,rounds,ntopol,seed,linkage", [
@@ -213,7 +179,7 @@ def test_own_spr_round_makes_the_reference_s_moves(spr_driver, tmp_path, mode, n
     (tmp_path / "aln.txt").write_text(aln)
     out = subprocess.run([spr_driver, str(tmp_path / "start.nwk"), str(tmp_path / "aln.txt"), mode,
                           str(radius), str(rounds), str(ntopol), linkage],
-                         check=True, capture_output=True, text=True, timeout=900).stdout
+                         check=True, capture_output=True, text=True, timeout=900, env=ENV).stdout
     ref_tree = re.search(r"^ref tree: (.*)$", out, re.M).group(1)
     own_tree = re.search(r"^own tree: (.*)$", out, re.M).group(1)
     assert _splits(ref_tree) != _splits(nwk), "the round should have changed the starting topology"
@@ -246,19 +212,9 @@ def test_reference_binary_module_round_trip(oracle, tmp_path, mode):
     include/pll.h it must dump and restore a partition of this library such that the
     edge log-likelihood is the same without recomputing anything
     (test/src/binary/binary-sequential.c:344-354 uses 1e-7)."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present on this box")
-    exe = tmp_path / "binary_driver"
-    src = [os.path.join(ROOT, "tests", "dropin", "binary_driver.c"), f"{REF}/src/pllmod_common.c", f"{REF}/src/msa/pll_msa.c"]
-    src += sorted(glob.glob(f"{REF}/src/binary/*.c"))
-    inc = sum((["-I", d] for d in [f"{ROOT}/include", f"{REF}/src", f"{REF}/src/binary", f"{REF}/src/tree",
-                                   f"{REF}/src/msa"]), [])
-    libdir = os.path.dirname(ORACLE_LIB)
-    # (pll_msa.c's statistics function calls into src/util, which is not on this path: unused sections are dropped)
-    subprocess.run(["gcc", "-std=gnu99", "-D_GNU_SOURCE", "-O2", "-w", "-ffunction-sections", *inc, "-o", str(exe), *src,
-                    "-L", libdir, "-lpll_oracle", "-lm", f"-Wl,-rpath,{libdir}", "-Wl,--gc-sections"], check=True)
-    out = subprocess.run([str(exe), str(tmp_path / "ckpt.bin"), mode], check=True, capture_output=True,
-                         text=True, timeout=120).stdout
+    exe = common.ref_program("binary_driver")
+    out = subprocess.run([exe, str(tmp_path / "ckpt.bin"), mode], check=True, capture_output=True,
+                         text=True, timeout=120, env=ENV).stdout
     v = {k.strip(): float(x) for k, x in re.findall(r"^(lnL \w+):\s+(-?[0-9.]+)$", out, re.M)}
     assert set(v) == {"lnL before", "lnL after", "lnL redo"}
     assert v["lnL before"] < -1000

@@ -1,45 +1,32 @@
 """The CPU oracle against the reference's own golden vectors.
 
 Two layers of pinning:
- 1. `test_reference_programs_*`: where /root/reference is present (the build
-    container), the reference's OWN test programs blopt-minimal.c / blopt-5states.c
-    and its OWN optimiser sources (src/optimize/*.c) are compiled where they lie,
-    against include/pll.h, linked with the oracle, run, and their stdout is
-    compared byte for byte with the reference's golden .out files -- the same
-    check test/runtest.py performs.  Objects go to a temp dir, nothing is copied.
+ 1. `test_reference_programs_*`: the reference's OWN test programs blopt-minimal.c /
+    blopt-5states.c and its OWN optimiser sources (src/optimize/*.c), compiled where
+    they lie against include/pll.h and linked with the oracle by oracle/Makefile.ref
+    (build() makes oracle/_ref/ where a pll-modules checkout is present), are run and
+    their stdout is compared byte for byte with the reference's golden .out files
+    (tests/golden/) -- the same check test/runtest.py performs.
  2. `test_fixture_*`: the same numbers through the C ABI from Python with the
     committed fixtures (tests/golden/blopt_fixtures.json), runnable anywhere.
 """
-import glob
 import os
 import subprocess
 
 import pytest
 
 import common
-from conftest import ROOT, ORACLE_LIB
-
-REF = "/root/reference"
 
 
-def _build_and_run(tmp_path, name, args):
-    exe = tmp_path / name
-    src = [f"{REF}/test/src/optimize/{name}.c", f"{REF}/test/src/common.c",
-           f"{REF}/src/optimize/pll_optimize.c", f"{REF}/src/optimize/opt_algorithms.c",
-           f"{REF}/src/pllmod_common.c"] + sorted(glob.glob(f"{REF}/src/optimize/lbfgsb/*.c"))
-    inc = ["-I", f"{ROOT}/include", "-I", f"{REF}/src", "-I", f"{REF}/src/optimize",
-           "-I", f"{REF}/src/tree", "-I", f"{REF}/test/src"]
-    libdir = os.path.dirname(ORACLE_LIB)
-    subprocess.run(["gcc", "-std=gnu99", "-D_GNU_SOURCE", "-O2", "-w", *inc, "-o", str(exe), *src,
-                    "-L", libdir, "-lpll_oracle", "-lm", f"-Wl,-rpath,{libdir}"], check=True)
-    return subprocess.run([str(exe), *args], check=True, capture_output=True, text=True).stdout
+def _run(name, args):
+    exe = common.ref_program(name)
+    return subprocess.run([exe, *args], check=True, capture_output=True, text=True, env=common.ref_env()).stdout
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present on this box")
 @pytest.mark.parametrize("name,args", [("blopt-minimal", []), ("blopt-minimal", ["avx"]),
                                        ("blopt-5states", []), ("blopt-5states", ["tv"])])
-def test_reference_programs_reproduce_golden_output(oracle, tmp_path, name, args):
-    out = _build_and_run(tmp_path, name, args)
+def test_reference_programs_reproduce_golden_output(oracle, name, args):
+    out = _run(name, args)
     golden = open(os.path.join(common.GOLDEN, name + ".out")).read()
     assert out == golden
 
