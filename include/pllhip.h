@@ -66,6 +66,14 @@ PLL_EXPORT int pllhip_set_sharding(unsigned int count, const int * devices);
 /* number of devices `partition` is spread over (1: an ordinary partition) */
 PLL_EXPORT unsigned int pllhip_shard_count(const pll_partition_t * partition);
 
+/* ---- parsimony (pll_fastparsimony_init objects; INTEGRATION.md, "Parsimony") ----
+ * The Fitch cost of `tree` over the `count` partitions of `list` (same tip count): sum over partitions and sites
+ * of pattern weight x empty intersections.  The tree is any binary unrooted tree whose tip clv_index values are
+ * tip indices of the partitions.  PLL_ERROR_STEPWISE_TIPS: different tip counts or fewer than 3 tips;
+ * PLL_ERROR_TREE_INVALID: a non-binary tree or an unknown tip. */
+PLL_EXPORT int pllhip_parsimony_tree_score(pll_parsimony_t * const * list, unsigned int count,
+                                           const pll_utree_t * tree, unsigned int * score);
+
 /* gfx architecture name of a device, e.g. "gfx950" */
 PLL_EXPORT int pllhip_device_arch(int device, char * out, size_t out_len);
 

@@ -6,6 +6,8 @@
  * that also links those files resolves its symbols.  Every one of them fails
  * loudly: it sets pll_errno = PLL_ERROR_NOT_IMPLEMENTED and returns
  * NULL / PLL_FAILURE.  Nothing on the likelihood path calls them.
+ * (pll_fastparsimony_init / _stepwise and pll_parsimony_destroy are real in the product library:
+ * pll_parsimony.c; the stubs below are weak and stay for the oracle.)
  * (The SPR / NNI topology primitives that pllmod_algo_spr_round needs are real:
  * pll_utree_moves.c.)
  */
@@ -29,9 +31,10 @@ NI_INT(pll_rtree_traverse, (pll_rnode_t * r, int t, int (*cb)(pll_rnode_t *), pl
 NI_VOID(pll_rtree_create_operations, (pll_rnode_t * const * b, unsigned int n, double * br, unsigned int * pm, pll_operation_t * ops, unsigned int * mc, unsigned int * oc))
 NI_PTR(pll_rtree_t *, pll_rtree_wraptree, (pll_rnode_t * r, unsigned int t))
 
-NI_PTR(pll_parsimony_t *, pll_fastparsimony_init, (const pll_partition_t * p))
-NI_VOID(pll_parsimony_destroy, (pll_parsimony_t * p))
-NI_PTR(pll_utree_t *, pll_fastparsimony_stepwise, (pll_parsimony_t ** l, char * const * lab, unsigned int * s, unsigned int c, unsigned int seed))
+/* weak: the product library links the real ones (pll_parsimony.c); the oracle keeps these */
+__attribute__((weak)) NI_PTR(pll_parsimony_t *, pll_fastparsimony_init, (const pll_partition_t * p))
+__attribute__((weak)) NI_VOID(pll_parsimony_destroy, (pll_parsimony_t * p))
+__attribute__((weak)) NI_PTR(pll_utree_t *, pll_fastparsimony_stepwise, (pll_parsimony_t ** l, char * const * lab, unsigned int * s, unsigned int c, unsigned int seed))
 NI_INT(pll_fastparsimony_stepwise_extend, (pll_utree_t * t, pll_parsimony_t ** l, unsigned int c, char * const * lab, unsigned int * m, unsigned int seed, unsigned int * s))
 NI_INT(pll_fastparsimony_stepwise_spr_round, (pll_utree_t * t, pll_parsimony_t ** l, unsigned int c, const unsigned int * m, unsigned int seed, const int * v, unsigned int * cost))
 

@@ -1,0 +1,244 @@
+// pll_parsimony_dev.hip -- device side of pll_fastparsimony_* and pllhip_parsimony_tree_score (parsimony_dev.h):
+// packing of the engine's tip data into bit-sliced state sets, and the walks of kernels_parsimony.hpp.
+//
+// A partition is one unit (its device, a stream of the object's own); a partition spread over devices by
+// pllhip_set_sharding is one unit per shard.  Shards hold disjoint sites, so their counts add up exactly.
+#include "engine.h"
+#include "kernels_parsimony.hpp"
+#include "parsimony_dev.h"
+
+#include <cstring>
+#include <new>
+#include <vector>
+
+using namespace pllhip;
+
+namespace {
+
+struct ParsUnit
+{
+  int device = 0;
+  hipStream_t stream = nullptr;
+  unsigned nw = 0;                    // words per state (multiple of PARS_WG)
+  unsigned nplanes = 0;               // weight bit planes
+  uint32_t * d_sets = nullptr;        // D: [node][state][nw]
+  uint32_t * d_up = nullptr;          // U: [node][state][nw] (inner nodes only are written)
+  uint32_t * d_planes = nullptr;      // [nplanes][nw]
+  int * d_ops = nullptr;
+  unsigned long long * d_out = nullptr;   // [edges] + score
+  unsigned long long * h_out = nullptr;   // pinned copy of d_out
+  int * h_ops = nullptr;                  // pinned staging of the schedule
+  unsigned npre = 0;                      // of the last launch
+};
+
+} // namespace
+
+struct pllhip_pars_dev_s
+{
+  unsigned S = 0, tips = 0, nodes = 0;
+  size_t ops_cap = 0, out_cap = 0;
+  std::vector<ParsUnit> units;
+};
+
+static size_t vec_words(const pllhip_pars_dev_t * d, const ParsUnit & u) { return (size_t)d->S * u.nw; }
+
+static void unit_free(ParsUnit & u)
+{
+  if (u.stream) (void)hipSetDevice(u.device);
+  if (u.stream) (void)hipStreamSynchronize(u.stream);
+  (void)hipFree(u.d_sets);
+  (void)hipFree(u.d_up);
+  (void)hipFree(u.d_planes);
+  (void)hipFree(u.d_ops);
+  (void)hipFree(u.d_out);
+  if (u.h_out) (void)hipHostFree(u.h_out);
+  if (u.h_ops) (void)hipHostFree(u.h_ops);
+  if (u.stream) (void)hipStreamDestroy(u.stream);
+  u = ParsUnit();
+}
+
+template <typename T>
+static bool pars_alloc(T ** ptr, size_t count, const char * what)
+{
+  *ptr = nullptr;
+  const hipError_t err = hipMalloc(reinterpret_cast<void **>(ptr), (count ? count : 1) * sizeof(T));
+  if (err == hipSuccess) return true;
+  *ptr = nullptr;
+  set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s", (count ? count : 1) * sizeof(T), what,
+            hipGetErrorString(err));
+  return false;
+}
+
+// one ordinary (non-router) partition: sites [0, p->sites) of it, weights from `weights`
+static bool unit_create(pllhip_pars_dev_t * d, ParsUnit & u, const pll_partition_t * p, const unsigned * weights)
+{
+  const Engine * e = engine_of(p);
+  u.device = e->device;
+  if (!hip_ok(hipSetDevice(u.device), "hipSetDevice")) return false;
+  if (!hip_ok(hipStreamCreateWithFlags(&u.stream, hipStreamNonBlocking), "hipStreamCreate")) return false;
+  const unsigned nreal = e->Nreal;
+  const unsigned words = (nreal + 31u) / 32u;
+  u.nw = std::max(1u, (words + PARS_WG - 1u) / PARS_WG) * PARS_WG;
+  unsigned maxw = 0;
+  for (unsigned n = 0; n < nreal; ++n) maxw = std::max(maxw, weights[n]);
+  u.nplanes = 0;
+  while (u.nplanes < 32 && (maxw >> u.nplanes)) ++u.nplanes;
+  const size_t vec = vec_words(d, u);
+  if (!pars_alloc(&u.d_sets, (size_t)d->nodes * vec, "parsimony sets") ||
+      !pars_alloc(&u.d_up, (size_t)d->nodes * vec, "parsimony up-sets") ||
+      !pars_alloc(&u.d_planes, (size_t)std::max(1u, u.nplanes) * u.nw, "parsimony weights") ||
+      !pars_alloc(&u.d_ops, d->ops_cap, "parsimony schedule") ||
+      !pars_alloc(&u.d_out, d->out_cap, "parsimony costs"))
+    return false;
+  if (!hip_ok(hipHostMalloc(reinterpret_cast<void **>(&u.h_out), d->out_cap * sizeof(unsigned long long)),
+               "hipHostMalloc costs") ||
+      !hip_ok(hipHostMalloc(reinterpret_cast<void **>(&u.h_ops), d->ops_cap * sizeof(int)), "hipHostMalloc schedule"))
+    return false;
+
+  // weights as bit planes
+  std::vector<uint32_t> planes((size_t)std::max(1u, u.nplanes) * u.nw, 0u);
+  for (unsigned n = 0; n < nreal; ++n)
+    for (unsigned b = 0; b < u.nplanes; ++b)
+      if ((weights[n] >> b) & 1u) planes[(size_t)b * u.nw + n / 32u] |= 1u << (n % 32u);
+  if (!hip_ok(hipMemcpyAsync(u.d_planes, planes.data(), planes.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                              u.stream), "upload weight planes"))
+    return false;
+
+  // the tips, from the engine's device data (after whatever the engine's stream still has to upload)
+  unsigned long long * d_tipmap = nullptr;
+  if (e->coded_tips)
+  {
+    if (!pars_alloc(&d_tipmap, PLL_ASCII_SIZE, "parsimony code table")) return false;
+    if (!hip_ok(hipMemcpyAsync(d_tipmap, p->tipmap, PLL_ASCII_SIZE * sizeof(unsigned long long),
+                                hipMemcpyHostToDevice, u.stream), "upload code table"))
+    {
+      (void)hipFree(d_tipmap);
+      return false;
+    }
+  }
+  bool ok = hip_ok(hipStreamSynchronize(e->stream), "engine stream");
+  for (unsigned t = 0; ok && t < d->tips; ++t)
+  {
+    const bool coded = e->coded_tips;
+    hipLaunchKernelGGL(k_pars_pack, dim3(u.nw / 2u), dim3(PARS_WG), 0, u.stream,
+                       coded ? nullptr : e->d_clv[t], coded ? e->d_codes[t] : nullptr, d_tipmap,
+                       e->blocked ? 1u : 0u, e->R, e->Sp, e->rows, d->S, nreal, u.nw, u.d_sets + (size_t)t * vec);
+    ok = hip_ok(hipGetLastError(), "k_pars_pack");
+  }
+  ok = ok && hip_ok(hipStreamSynchronize(u.stream), "pack tips");
+  (void)hipFree(d_tipmap);
+  return ok;
+}
+
+extern "C" pllhip_pars_dev_t * pllhip_pars_dev_create(const pll_partition_t * p)
+{
+  const Engine * e = engine_of(p);
+  if (!e)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "The partition has no engine state");
+    return nullptr;
+  }
+  if (p->states < 2 || p->states > 64)
+  {
+    set_error(PLL_ERROR_STEPWISE_UNSUPPORTED, "Parsimony takes 2 .. 64 states, not %u", p->states);
+    return nullptr;
+  }
+  pllhip_pars_dev_t * d = new (std::nothrow) pllhip_pars_dev_t();
+  if (!d)
+  {
+    set_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate parsimony state");
+    return nullptr;
+  }
+  int saved = 0;
+  (void)hipGetDevice(&saved);
+  d->S = p->states;
+  d->tips = p->tips;
+  d->nodes = std::max(p->tips, 2u * p->tips - 2u);
+  d->ops_cap = 3u * (size_t)d->nodes + 4u * (size_t)d->nodes + 8u;
+  d->out_cap = (size_t)d->nodes + 1u;
+  bool ok = true;
+  if (e->shards.empty())
+  {
+    d->units.emplace_back();
+    ok = unit_create(d, d->units.back(), p, p->pattern_weights);
+  }
+  else
+    for (size_t k = 0; ok && k < e->shards.size(); ++k)
+    {
+      d->units.emplace_back();
+      ok = unit_create(d, d->units.back(), e->shards[k], p->pattern_weights + e->shard_first[k]);
+    }
+  (void)hipSetDevice(saved);
+  if (!ok)
+  {
+    pllhip_pars_dev_destroy(d);
+    return nullptr;
+  }
+  return d;
+}
+
+extern "C" void pllhip_pars_dev_destroy(pllhip_pars_dev_t * d)
+{
+  if (!d) return;
+  int saved = 0;
+  (void)hipGetDevice(&saved);
+  for (ParsUnit & u : d->units) unit_free(u);
+  (void)hipSetDevice(saved);
+  delete d;
+}
+
+extern "C" int pllhip_pars_dev_launch(pllhip_pars_dev_t * d, const int * ops, unsigned ndown, unsigned npre, int cand,
+                                      int count_score)
+{
+  const size_t nops = 3u * (size_t)ndown + 4u * (size_t)npre;
+  if (nops > d->ops_cap || npre + 1u > d->out_cap || (npre && (cand < 0 || (unsigned)cand >= d->nodes)))
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "Parsimony schedule out of range");
+    return PLL_FAILURE;
+  }
+  for (size_t i = 0; i < nops; ++i)
+    if (ops[i] >= (int)d->nodes)
+    {
+      set_error(PLL_ERROR_PARAM_INVALID, "Parsimony schedule names node %d of %u", ops[i], d->nodes);
+      return PLL_FAILURE;
+    }
+  int saved = 0;
+  (void)hipGetDevice(&saved);
+  for (ParsUnit & u : d->units)
+  {
+    PLLHIP_TRY(hipSetDevice(u.device));
+    PLLHIP_TRY(hipStreamSynchronize(u.stream));             // h_ops / h_out are free again
+    memcpy(u.h_ops, ops, nops * sizeof(int));
+    const size_t vec = vec_words(d, u);
+    PLLHIP_TRY(hipMemsetAsync(u.d_out, 0, (npre + 1u) * sizeof(unsigned long long), u.stream));
+    PLLHIP_TRY(hipMemcpyAsync(u.d_ops, u.h_ops, std::max<size_t>(1, nops) * sizeof(int), hipMemcpyHostToDevice,
+                              u.stream));
+    hipLaunchKernelGGL(k_pars_walk, dim3(u.nw / PARS_WG), dim3(PARS_WG), 0, u.stream, u.d_sets, u.d_up, vec, d->S,
+                       u.nw, (const uint32_t *)u.d_planes, u.nplanes, (const int *)u.d_ops, ndown, npre,
+                       (const uint32_t *)(u.d_sets + (size_t)(cand < 0 ? 0 : cand) * vec), u.d_out,
+                       count_score ? u.d_out + npre : nullptr);
+    PLLHIP_TRY(hipGetLastError());
+    PLLHIP_TRY(hipMemcpyAsync(u.h_out, u.d_out, (npre + 1u) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              u.stream));
+    u.npre = npre;
+  }
+  (void)hipSetDevice(saved);
+  return PLL_SUCCESS;
+}
+
+extern "C" int pllhip_pars_dev_collect(pllhip_pars_dev_t * d, unsigned long long * edge_acc,
+                                       unsigned long long * score_acc)
+{
+  int saved = 0;
+  (void)hipGetDevice(&saved);
+  for (ParsUnit & u : d->units)
+  {
+    PLLHIP_TRY(hipSetDevice(u.device));
+    PLLHIP_TRY(hipStreamSynchronize(u.stream));
+    if (edge_acc)
+      for (unsigned i = 0; i < u.npre; ++i) edge_acc[i] += u.h_out[i];
+    if (score_acc) *score_acc += u.h_out[u.npre];
+  }
+  (void)hipSetDevice(saved);
+  return PLL_SUCCESS;
+}

@@ -155,7 +155,8 @@ pllhip_compute_likelihood_derivatives_multi pllhip_free_trial_lengths pllhip_set
 pllhip_shard_count pllhip_results_create pllhip_results_destroy
 pllhip_results_edge_loglikelihood pllhip_results_derivatives pllhip_results_fetch
 pllhip_eval_attach_comm pllhip_update_partials_batch pllhip_results_poison pllhip_newton_branch pllhip_repeat_stats
-pllhip_set_transient pllhip_discard_transient pllhip_transient_stats pllhip_newton_branch_multi""".split()
+pllhip_set_transient pllhip_discard_transient pllhip_transient_stats pllhip_newton_branch_multi
+pllhip_parsimony_tree_score""".split()
 
 
 def _u32(a):
@@ -231,6 +232,13 @@ class PllLib:
                                                   C.POINTER(Operation), c_uint_p, c_uint_p]
         L.pll_utree_export_newick.restype = C.c_void_p
         L.pll_utree_export_newick.argtypes = [up, C.c_void_p]
+        L.pll_fastparsimony_init.restype = C.c_void_p
+        L.pll_fastparsimony_init.argtypes = [pp]
+        L.pll_parsimony_destroy.restype = None
+        L.pll_parsimony_destroy.argtypes = [C.c_void_p]
+        L.pll_fastparsimony_stepwise.restype = tp
+        L.pll_fastparsimony_stepwise.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), c_uint_p,
+                                                 C.c_uint, C.c_uint]
         if hasattr(L, "pllhip_eval_create"):
             L.pllhip_eval_create.restype = C.c_void_p
             L.pllhip_eval_create.argtypes = [tp, C.c_uint, C.c_uint]
@@ -300,6 +308,7 @@ class PllLib:
             L.pllhip_set_sharding.argtypes = [C.c_uint, C.POINTER(C.c_int)]
             L.pllhip_shard_count.argtypes = [pp]
             L.pllhip_shard_count.restype = C.c_uint
+            L.pllhip_parsimony_tree_score.argtypes = [C.POINTER(C.c_void_p), C.c_uint, tp, c_uint_p]
             L.pllhip_comm_rank.argtypes = [C.c_void_p]
             L.pllhip_comm_size.argtypes = [C.c_void_p]
             L.pllhip_eval_attach_comm.argtypes = [C.c_void_p, C.c_void_p]
@@ -784,6 +793,48 @@ def simulated_codes(tree, nsites, nstates, seed=45, scale=1.0):
             jump = 1 + (splitmix64(seed + 104729 * (k + 1), nsites) % np.uint64(S - 1)).astype(np.int64)
             stack.append((child, node, np.where(u < pchange, (state + jump) % S, state)))
     return out
+
+
+def utree_splits(tree):
+    """the splits of a pll_utree_t (a POINTER(UTree)) as a set of frozensets of tip clv indices: per edge the
+    side without the smallest tip index (so two trees over the same tips compare as sets)"""
+    t = tree.contents
+    tips = [t.nodes[i].contents.clv_index for i in range(t.tip_count)]
+    low = min(tips)
+    below = {}
+
+    def side(rec):
+        """tips behind the record `rec` (the subtree its `back` leads away from)"""
+        key = C.addressof(rec.contents)
+        if key in below:
+            return below[key]
+        out, stack = set(), [rec]
+        while stack:
+            r = stack.pop()
+            b = r.contents.back
+            if not b.contents.next:
+                out.add(b.contents.clv_index)
+                continue
+            n = b.contents.next
+            while C.addressof(n.contents) != C.addressof(b.contents):
+                stack.append(n)
+                n = n.contents.next
+        below[key] = frozenset(out)
+        return below[key]
+
+    splits = set()
+    for i in range(t.tip_count + t.inner_count):
+        r = t.nodes[i]
+        recs = [r]
+        if r.contents.next:
+            n = r.contents.next
+            while C.addressof(n.contents) != C.addressof(r.contents):
+                recs.append(n)
+                n = n.contents.next
+        for rec in recs:
+            s = side(rec)
+            splits.add(s if low not in s else frozenset(tips) - s)
+    return splits
 
 
 def state_charmap(nstates):

@@ -1,0 +1,70 @@
+"""Times pll_fastparsimony_stepwise at the C2, C3 and C5 shapes on device 0 and prints one JSON line per shape:
+wall time of the stepwise call, the bytes of the traffic model in DESIGN.md ("Parsimony") and the fraction of
+8 TB/s they stand for.  Alignments are simulated along a random tree (pllhip_ctypes.simulated_codes), tips coded
+(PLL_ATTRIB_PATTERN_TIP), unit weights.
+
+usage: python tools/gpu_parsimony.py [--shapes c2,c3,c5] [--repeat N] [--seed S]"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "pll-modules_amd"))
+import pllhip_ctypes as pc  # noqa: E402
+
+SHAPES = {"c2": (100, 1_000_000, 4), "c3": (200, 1_000_000, 20), "c5": (50, 200_000, 61)}
+PEAK = 8e12
+
+
+def run(lib, name, tips, sites, S, repeat, seed):
+    L = lib.lib
+    tree = pc.Tree(tips, seed_topology=seed)
+    codes = pc.simulated_codes(tree, sites, S, seed=seed + 1)
+    inst = pc.Instance(lib, tips, S, sites, 1, attributes=pc.PLL_ATTRIB_PATTERN_TIP, clv_buffers=0,
+                       prob_matrices=1, scalers=False)
+    charmap = pc.state_charmap(S)
+    with inst:
+        for t in range(tips):
+            inst.set_tip_states(t, charmap, (codes[t] + 48).tobytes())
+        t0 = time.perf_counter()
+        p = L.pll_fastparsimony_init(inst.p)
+        init_ms = (time.perf_counter() - t0) * 1e3
+    if not p:
+        raise RuntimeError(lib.errmsg)
+    arr = (C.c_void_p * 1)(p)
+    times, score = [], C.c_uint(0)
+    for r in range(repeat + 1):                  # the first call warms up
+        t0 = time.perf_counter()
+        tr = L.pll_fastparsimony_stepwise(arr, None, C.byref(score), 1, seed + r)
+        dt = (time.perf_counter() - t0) * 1e3
+        if not tr:
+            raise RuntimeError(lib.errmsg)
+        L.pll_utree_destroy(tr, None)
+        if r:
+            times.append(dt)
+    L.pll_parsimony_destroy(p)
+    ms = float(np.median(times))
+    model = float(tips) ** 2 * sites * S / 8
+    return {"shape": name, "tips": tips, "sites": sites, "states": S, "steps": tips - 3, "ms": round(ms, 3),
+            "ms_min": round(min(times), 3), "init_ms": round(init_ms, 3), "score": score.value,
+            "model_bytes": model, "model_frac_of_8TBps": round(model / (ms * 1e-3) / PEAK, 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="c2,c3,c5")
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=17)
+    a = ap.parse_args()
+    lib = pc.PllLib(pc.PRODUCT_LIB)
+    for name in a.shapes.split(","):
+        print(json.dumps(run(lib, name, *SHAPES[name], a.repeat, a.seed)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
