@@ -367,9 +367,9 @@ typedef struct pll_phylip_s
 /* re-entrant PRNG state (src/tree/pll_tree.c:903-1277) */
 typedef struct pll_random_state_s pll_random_state;
 
-/* parsimony container (src/tree/pll_tree.c:1100-1277).  pll_fastparsimony_init / _stepwise and
-   pll_parsimony_destroy run on the device ("Parsimony"); _stepwise_extend and
-   _stepwise_spr_round are B3, not implemented.  The object the engine returns is larger than this
+/* parsimony container (src/tree/pll_tree.c:1100-1277).  pll_fastparsimony_init, _stepwise,
+   _stepwise_extend, _stepwise_spr_round and pll_parsimony_destroy run on the device (INTEGRATION.md,
+   "Parsimony").  The object the engine returns is larger than this
    struct: its device state follows these fields. */
 typedef struct pll_parsimony_s
 {

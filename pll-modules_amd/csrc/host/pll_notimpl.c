@@ -6,8 +6,8 @@
  * that also links those files resolves its symbols.  Every one of them fails
  * loudly: it sets pll_errno = PLL_ERROR_NOT_IMPLEMENTED and returns
  * NULL / PLL_FAILURE.  Nothing on the likelihood path calls them.
- * (pll_fastparsimony_init / _stepwise and pll_parsimony_destroy are real in the product library:
- * pll_parsimony.c; the stubs below are weak and stay for the oracle.)
+ * (pll_fastparsimony_init / _stepwise / _stepwise_extend / _stepwise_spr_round and pll_parsimony_destroy are
+ * real in the product library: pll_parsimony.c; the stubs below are weak and stay for the oracle.)
  * (The SPR / NNI topology primitives that pllmod_algo_spr_round needs are real:
  * pll_utree_moves.c.)
  */
@@ -35,8 +35,8 @@ NI_PTR(pll_rtree_t *, pll_rtree_wraptree, (pll_rnode_t * r, unsigned int t))
 __attribute__((weak)) NI_PTR(pll_parsimony_t *, pll_fastparsimony_init, (const pll_partition_t * p))
 __attribute__((weak)) NI_VOID(pll_parsimony_destroy, (pll_parsimony_t * p))
 __attribute__((weak)) NI_PTR(pll_utree_t *, pll_fastparsimony_stepwise, (pll_parsimony_t ** l, char * const * lab, unsigned int * s, unsigned int c, unsigned int seed))
-NI_INT(pll_fastparsimony_stepwise_extend, (pll_utree_t * t, pll_parsimony_t ** l, unsigned int c, char * const * lab, unsigned int * m, unsigned int seed, unsigned int * s))
-NI_INT(pll_fastparsimony_stepwise_spr_round, (pll_utree_t * t, pll_parsimony_t ** l, unsigned int c, const unsigned int * m, unsigned int seed, const int * v, unsigned int * cost))
+__attribute__((weak)) NI_INT(pll_fastparsimony_stepwise_extend, (pll_utree_t * t, pll_parsimony_t ** l, unsigned int c, char * const * lab, unsigned int * m, unsigned int seed, unsigned int * s))
+__attribute__((weak)) NI_INT(pll_fastparsimony_stepwise_spr_round, (pll_utree_t * t, pll_parsimony_t ** l, unsigned int c, const unsigned int * m, unsigned int seed, const int * v, unsigned int * cost))
 
 NI_PTR(pll_fasta_t *, pll_fasta_open, (const char * f, const unsigned int * m))
 NI_INT(pll_fasta_getnext, (pll_fasta_t * fd, char ** h, long * hl, char ** s, long * sl, long * no))

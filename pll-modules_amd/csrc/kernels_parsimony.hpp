@@ -134,4 +134,76 @@ __global__ __launch_bounds__(PARS_WG) void k_pars_walk(uint32_t * D, uint32_t * 
   }
 }
 
+// SPR scoring of pruned subtrees (pll_fastparsimony_stepwise_spr_round).  One launch scores B pruned subtrees,
+// member m = blockIdx.y; D and U (the current tree's down and up sets) are read-only, every member writes only its
+// own scratch, scr + m * scr_stride: the new down sets of the path above the prune point, then the up sets U' of the
+// pruned tree T'.  members[m] = {first op, ndown, npre, candidate node, first output}.  An operand is
+// (index << 2) | source with source PARS_SRC_D (D[node]), PARS_SRC_U (U[node]) or PARS_SRC_X (scratch slot).
+//   ndown down ops {slot, a, b}: X[slot] = F(a, b)
+//   npre edge ops {xd, a, b, store, count}: the set above the edge's lower node is u = F(a, b) (b < 0: u = a); with
+//     store >= 0 it is kept as X[store]; with count != 0 the edge costs weight x [F(xd, u) & cand = empty], added to
+//     out[first output + number of counted ops before it].
+constexpr unsigned PARS_SRC_D = 0u, PARS_SRC_U = 1u, PARS_SRC_X = 2u;
+constexpr unsigned PARS_SPR_MAX_BATCH = 64u;
+constexpr unsigned PARS_MEMBER_INTS = 5u, PARS_SPR_DOWN_INTS = 3u, PARS_SPR_PRE_INTS = 5u;
+
+__device__ inline const uint32_t * pars_src(int o, const uint32_t * D, const uint32_t * U, const uint32_t * X,
+                                            size_t vec)
+{
+  const unsigned src = (unsigned)o & 3u;
+  const uint32_t * base = src == PARS_SRC_D ? D : src == PARS_SRC_U ? U : X;
+  return base + (size_t)((unsigned)o >> 2) * vec;
+}
+
+__global__ __launch_bounds__(PARS_WG) void k_pars_spr(const uint32_t * D, const uint32_t * U, uint32_t * scr,
+                                                       size_t scr_stride, size_t vec, unsigned S, unsigned nw,
+                                                       const uint32_t * planes, unsigned nplanes, const int * ops,
+                                                       const int * members, unsigned long long * out)
+{
+  const unsigned w = blockIdx.x * PARS_WG + threadIdx.x;    // < nw: nw is a multiple of PARS_WG
+  const int * mem = members + PARS_MEMBER_INTS * blockIdx.y;
+  const int * op = ops + mem[0];
+  const unsigned ndown = (unsigned)mem[1], npre = (unsigned)mem[2];
+  uint32_t * X = scr + (size_t)blockIdx.y * scr_stride;
+  const uint32_t * ct = D + (size_t)mem[3] * vec + w;
+  unsigned long long * o = out + mem[4];
+  for (unsigned k = 0; k < ndown; ++k, op += PARS_SPR_DOWN_INTS)
+  {
+    const uint32_t * x = pars_src(op[1], D, U, X, vec) + w;
+    const uint32_t * y = pars_src(op[2], D, U, X, vec) + w;
+    uint32_t * r = X + (size_t)op[0] * vec + w;
+    uint32_t ne = 0;
+    for (unsigned s = 0; s < S; ++s) ne |= x[(size_t)s * nw] & y[(size_t)s * nw];
+    for (unsigned s = 0; s < S; ++s) r[(size_t)s * nw] = pars_fitch(x[(size_t)s * nw], y[(size_t)s * nw], ne);
+  }
+  for (unsigned e = 0; e < npre; ++e, op += PARS_SPR_PRE_INTS)
+  {
+    const int b = op[2], st = op[3];
+    const uint32_t * xd = pars_src(op[0], D, U, X, vec) + w;
+    const uint32_t * xa = pars_src(op[1], D, U, X, vec) + w;
+    const uint32_t * xb = pars_src(b >= 0 ? b : op[1], D, U, X, vec) + w;
+    uint32_t * uo = st >= 0 ? X + (size_t)st * vec + w : nullptr;
+    uint32_t ne_up = 0;
+    if (b >= 0)
+      for (unsigned s = 0; s < S; ++s) ne_up |= xa[(size_t)s * nw] & xb[(size_t)s * nw];
+    uint32_t ne_edge = 0;
+    for (unsigned s = 0; s < S; ++s)
+    {
+      const uint32_t u = b >= 0 ? pars_fitch(xa[(size_t)s * nw], xb[(size_t)s * nw], ne_up) : xa[(size_t)s * nw];
+      if (uo) uo[(size_t)s * nw] = u;
+      ne_edge |= u & xd[(size_t)s * nw];
+    }
+    if (!op[4]) continue;
+    uint32_t hit = 0;
+    for (unsigned s = 0; s < S; ++s)
+    {
+      const uint32_t u = b >= 0 ? pars_fitch(xa[(size_t)s * nw], xb[(size_t)s * nw], ne_up) : xa[(size_t)s * nw];
+      hit |= pars_fitch(u, xd[(size_t)s * nw], ne_edge) & ct[(size_t)s * nw];
+    }
+    const unsigned long long c = pars_wave_sum(pars_weight(~hit, planes, nplanes, nw, w));
+    if (threadIdx.x == 0 && c) atomicAdd(o, c);
+    ++o;
+  }
+}
+
 } // namespace pllhip

@@ -31,6 +31,22 @@ int pllhip_pars_dev_launch(pllhip_pars_dev_t * dev, const int * ops, unsigned in
    may be NULL). */
 int pllhip_pars_dev_collect(pllhip_pars_dev_t * dev, unsigned long long * edge_acc, unsigned long long * score_acc);
 
+/* SPR rounds (k_pars_spr).  hint: the batch that fills the chip for this object's site count.  reserve: scratch for
+   up to `want` pruned subtrees per launch (at least 1) plus schedule and cost buffers for them; returns
+   the batch the object now holds (<= want), 0 + pll_errno on failure.  launch: `ops` (nops ints) then `nmem`
+   member records {first op, ndown, npre, candidate node, first output}, nout counts in all.  collect: waits and
+   ADDS the nout counts to acc. */
+unsigned pllhip_pars_dev_spr_hint(const pllhip_pars_dev_t * dev);
+unsigned pllhip_pars_dev_spr_reserve(pllhip_pars_dev_t * dev, unsigned want);
+int pllhip_pars_dev_spr_launch(pllhip_pars_dev_t * dev, const int * ops, size_t nops, const int * members,
+                               unsigned nmem, unsigned nout);
+int pllhip_pars_dev_spr_collect(pllhip_pars_dev_t * dev, unsigned long long * acc);
+
+/* operand encoding of the SPR schedule (kernels_parsimony.hpp) */
+#define PLLHIP_PARS_SRC_D 0
+#define PLLHIP_PARS_SRC_U 1
+#define PLLHIP_PARS_SRC_X 2
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,9 @@ struct ParsUnit
   unsigned long long * h_out = nullptr;   // pinned copy of d_out
   int * h_ops = nullptr;                  // pinned staging of the schedule
   unsigned npre = 0;                      // of the last launch
+  uint32_t * d_scr = nullptr;             // SPR scratch: [member][slot][state][nw]
+  unsigned spr_batch = 0;                 // members d_scr holds
+  unsigned nout = 0;                      // counts of the last SPR launch
 };
 
 } // namespace
@@ -51,6 +54,7 @@ static void unit_free(ParsUnit & u)
   (void)hipFree(u.d_planes);
   (void)hipFree(u.d_ops);
   (void)hipFree(u.d_out);
+  (void)hipFree(u.d_scr);
   if (u.h_out) (void)hipHostFree(u.h_out);
   if (u.h_ops) (void)hipHostFree(u.h_ops);
   if (u.stream) (void)hipStreamDestroy(u.stream);
@@ -238,6 +242,150 @@ extern "C" int pllhip_pars_dev_collect(pllhip_pars_dev_t * d, unsigned long long
     if (edge_acc)
       for (unsigned i = 0; i < u.npre; ++i) edge_acc[i] += u.h_out[i];
     if (score_acc) *score_acc += u.h_out[u.npre];
+  }
+  (void)hipSetDevice(saved);
+  return PLL_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// SPR rounds: k_pars_spr
+// ---------------------------------------------------------------------------------------------------------------
+
+// (re)allocates the schedule and cost buffers of one unit for ops_cap / out_cap
+static bool unit_grow_io(pllhip_pars_dev_t * d, ParsUnit & u)
+{
+  (void)hipFree(u.d_ops);
+  (void)hipFree(u.d_out);
+  if (u.h_out) (void)hipHostFree(u.h_out);
+  if (u.h_ops) (void)hipHostFree(u.h_ops);
+  u.d_ops = nullptr; u.d_out = nullptr; u.h_out = nullptr; u.h_ops = nullptr;
+  return pars_alloc(&u.d_ops, d->ops_cap, "parsimony schedule") &&
+         pars_alloc(&u.d_out, d->out_cap, "parsimony costs") &&
+         hip_ok(hipHostMalloc(reinterpret_cast<void **>(&u.h_out), d->out_cap * sizeof(unsigned long long)),
+                "hipHostMalloc costs") &&
+         hip_ok(hipHostMalloc(reinterpret_cast<void **>(&u.h_ops), d->ops_cap * sizeof(int)), "hipHostMalloc schedule");
+}
+
+extern "C" unsigned pllhip_pars_dev_spr_hint(const pllhip_pars_dev_t * d)
+{
+  // about 2048 one-wave workgroups per launch: a few per SIMD of the chip
+  const unsigned blocks = d->units[0].nw / PARS_WG;
+  return std::min(PARS_SPR_MAX_BATCH, std::max(1u, (2048u + blocks - 1u) / blocks));
+}
+
+extern "C" unsigned pllhip_pars_dev_spr_reserve(pllhip_pars_dev_t * d, unsigned want)
+{
+  want = std::max(1u, std::min(want, PARS_SPR_MAX_BATCH));
+  int saved = 0;
+  (void)hipGetDevice(&saved);
+  unsigned batch = want;
+  bool ok = true;
+  for (ParsUnit & u : d->units)
+  {
+    if (u.spr_batch >= want) { batch = std::min(batch, u.spr_batch); continue; }
+    ok = hip_ok(hipSetDevice(u.device), "hipSetDevice") && hip_ok(hipStreamSynchronize(u.stream), "parsimony stream");
+    if (!ok) break;
+    const size_t member_bytes = (size_t)d->nodes * vec_words(d, u) * sizeof(uint32_t);
+    size_t free_b = 0, total_b = 0;
+    unsigned b = want;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)           // at most a quarter of what is free
+      b = (unsigned)std::max<size_t>(1, std::min<size_t>(want, free_b / 4u / member_bytes));
+    (void)hipFree(u.d_scr);
+    u.d_scr = nullptr;
+    u.spr_batch = 0;
+    ok = pars_alloc(&u.d_scr, (size_t)b * d->nodes * vec_words(d, u), "parsimony SPR scratch");
+    if (!ok) break;
+    u.spr_batch = b;
+    batch = std::min(batch, b);
+  }
+  // schedules and costs of `batch` members, each at most one path and one edge op per node
+  const size_t ops_need = (size_t)batch * (PARS_MEMBER_INTS + (size_t)d->nodes * (PARS_SPR_DOWN_INTS + PARS_SPR_PRE_INTS));
+  const size_t out_need = (size_t)batch * d->nodes;
+  if (ok && (ops_need > d->ops_cap || out_need > d->out_cap))
+  {
+    d->ops_cap = std::max(d->ops_cap, ops_need);
+    d->out_cap = std::max(d->out_cap, out_need);
+    for (ParsUnit & u : d->units)
+    {
+      ok = hip_ok(hipSetDevice(u.device), "hipSetDevice") && hip_ok(hipStreamSynchronize(u.stream), "stream") &&
+           unit_grow_io(d, u);
+      if (!ok) break;
+    }
+  }
+  (void)hipSetDevice(saved);
+  return ok ? batch : 0u;
+}
+
+static bool spr_operand_ok(int o, unsigned nodes)
+{
+  if (o < 0) return false;
+  const unsigned src = (unsigned)o & 3u;
+  return src <= PARS_SRC_X && ((unsigned)o >> 2) < nodes;       // node ids and scratch slots are both < nodes
+}
+
+extern "C" int pllhip_pars_dev_spr_launch(pllhip_pars_dev_t * d, const int * ops, size_t nops, const int * members,
+                                          unsigned nmem, unsigned nout)
+{
+  const size_t nint = nops + (size_t)PARS_MEMBER_INTS * nmem;
+  bool ok = nmem > 0 && nint <= d->ops_cap && nout <= d->out_cap;
+  for (ParsUnit & u : d->units) ok = ok && nmem <= u.spr_batch;
+  for (unsigned m = 0; ok && m < nmem; ++m)
+  {
+    const int * mem = members + PARS_MEMBER_INTS * m;
+    const int first = mem[0], ndown = mem[1], npre = mem[2], cand = mem[3], out0 = mem[4];
+    ok = first >= 0 && ndown >= 0 && npre >= 0 && cand >= 0 && (unsigned)cand < d->nodes && out0 >= 0 &&
+         (size_t)first + (size_t)ndown * PARS_SPR_DOWN_INTS + (size_t)npre * PARS_SPR_PRE_INTS <= nops;
+    const int * op = ops + (ok ? first : 0);
+    for (int k = 0; ok && k < ndown; ++k, op += PARS_SPR_DOWN_INTS)
+      ok = op[0] >= 0 && (unsigned)op[0] < d->nodes && spr_operand_ok(op[1], d->nodes) &&
+           spr_operand_ok(op[2], d->nodes);
+    unsigned counted = 0;
+    for (int e = 0; ok && e < npre; ++e, op += PARS_SPR_PRE_INTS)
+    {
+      ok = spr_operand_ok(op[0], d->nodes) && spr_operand_ok(op[1], d->nodes) &&
+           (op[2] < 0 || spr_operand_ok(op[2], d->nodes)) && (op[3] < 0 || (unsigned)op[3] < d->nodes);
+      counted += op[4] ? 1u : 0u;
+    }
+    ok = ok && (size_t)out0 + counted <= nout;
+  }
+  if (!ok)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "Parsimony SPR schedule out of range");
+    return PLL_FAILURE;
+  }
+  int saved = 0;
+  (void)hipGetDevice(&saved);
+  for (ParsUnit & u : d->units)
+  {
+    PLLHIP_TRY(hipSetDevice(u.device));
+    PLLHIP_TRY(hipStreamSynchronize(u.stream));
+    memcpy(u.h_ops, ops, nops * sizeof(int));
+    memcpy(u.h_ops + nops, members, (size_t)PARS_MEMBER_INTS * nmem * sizeof(int));
+    const size_t vec = vec_words(d, u);
+    PLLHIP_TRY(hipMemsetAsync(u.d_out, 0, std::max(1u, nout) * sizeof(unsigned long long), u.stream));
+    PLLHIP_TRY(hipMemcpyAsync(u.d_ops, u.h_ops, nint * sizeof(int), hipMemcpyHostToDevice, u.stream));
+    hipLaunchKernelGGL(k_pars_spr, dim3(u.nw / PARS_WG, nmem), dim3(PARS_WG), 0, u.stream,
+                       (const uint32_t *)u.d_sets, (const uint32_t *)u.d_up, u.d_scr, (size_t)d->nodes * vec, vec,
+                       d->S, u.nw, (const uint32_t *)u.d_planes, u.nplanes, (const int *)u.d_ops,
+                       (const int *)(u.d_ops + nops), u.d_out);
+    PLLHIP_TRY(hipGetLastError());
+    PLLHIP_TRY(hipMemcpyAsync(u.h_out, u.d_out, std::max(1u, nout) * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, u.stream));
+    u.nout = nout;
+  }
+  (void)hipSetDevice(saved);
+  return PLL_SUCCESS;
+}
+
+extern "C" int pllhip_pars_dev_spr_collect(pllhip_pars_dev_t * d, unsigned long long * acc)
+{
+  int saved = 0;
+  (void)hipGetDevice(&saved);
+  for (ParsUnit & u : d->units)
+  {
+    PLLHIP_TRY(hipSetDevice(u.device));
+    PLLHIP_TRY(hipStreamSynchronize(u.stream));
+    for (unsigned i = 0; i < u.nout; ++i) acc[i] += u.h_out[i];
   }
   (void)hipSetDevice(saved);
   return PLL_SUCCESS;

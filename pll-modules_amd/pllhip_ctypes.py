@@ -239,6 +239,10 @@ class PllLib:
         L.pll_fastparsimony_stepwise.restype = tp
         L.pll_fastparsimony_stepwise.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), c_uint_p,
                                                  C.c_uint, C.c_uint]
+        L.pll_fastparsimony_stepwise_extend.argtypes = [tp, C.POINTER(C.c_void_p), C.c_uint, C.POINTER(C.c_char_p),
+                                                        c_uint_p, C.c_uint, c_uint_p]
+        L.pll_fastparsimony_stepwise_spr_round.argtypes = [tp, C.POINTER(C.c_void_p), C.c_uint, c_uint_p, C.c_uint,
+                                                           C.POINTER(C.c_int), c_uint_p]
         if hasattr(L, "pllhip_eval_create"):
             L.pllhip_eval_create.restype = C.c_void_p
             L.pllhip_eval_create.argtypes = [tp, C.c_uint, C.c_uint]

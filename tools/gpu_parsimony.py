@@ -3,7 +3,12 @@ wall time of the stepwise call, the bytes of the traffic model in DESIGN.md ("Pa
 8 TB/s they stand for.  Alignments are simulated along a random tree (pllhip_ctypes.simulated_codes), tips coded
 (PLL_ATTRIB_PATTERN_TIP), unit weights.
 
-usage: python tools/gpu_parsimony.py [--shapes c2,c3,c5] [--repeat N] [--seed S]"""
+With --spr it times, per shape, one unconstrained pll_fastparsimony_stepwise_spr_round on the stepwise tree instead:
+round_ms, prunes, whether the tree changed (the API does not count moves), the batch, the bytes of the round's
+traffic model (about 2N prunes x 2N edges x 5 vectors) and the fraction of 8 TB/s they stand
+for.
+
+usage: python tools/gpu_parsimony.py [--shapes c2,c3,c5] [--repeat N] [--seed S] [--spr]"""
 import argparse
 import ctypes as C
 import json
@@ -55,15 +60,53 @@ def run(lib, name, tips, sites, S, repeat, seed):
             "model_bytes": model, "model_frac_of_8TBps": round(model / (ms * 1e-3) / PEAK, 4)}
 
 
+def run_spr(lib, name, tips, sites, S, seed):
+    L = lib.lib
+    tree = pc.Tree(tips, seed_topology=seed)
+    codes = pc.simulated_codes(tree, sites, S, seed=seed + 1)
+    inst = pc.Instance(lib, tips, S, sites, 1, attributes=pc.PLL_ATTRIB_PATTERN_TIP, clv_buffers=0,
+                       prob_matrices=1, scalers=False)
+    charmap = pc.state_charmap(S)
+    with inst:
+        for t in range(tips):
+            inst.set_tip_states(t, charmap, (codes[t] + 48).tobytes())
+        p = L.pll_fastparsimony_init(inst.p)
+    if not p:
+        raise RuntimeError(lib.errmsg)
+    arr = (C.c_void_p * 1)(p)
+    score, cost = C.c_uint(0), C.c_uint(0)
+    tr = L.pll_fastparsimony_stepwise(arr, None, C.byref(score), 1, seed)
+    if not tr:
+        raise RuntimeError(lib.errmsg)
+    nwk0 = C.string_at(L.pll_utree_export_newick(tr.contents.vroot, None)).decode()
+    t0 = time.perf_counter()
+    ok = L.pll_fastparsimony_stepwise_spr_round(tr, arr, 1, None, seed, None, C.byref(cost))
+    ms = (time.perf_counter() - t0) * 1e3
+    if not ok:
+        raise RuntimeError(lib.errmsg)
+    nwk1 = C.string_at(L.pll_utree_export_newick(tr.contents.vroot, None)).decode()
+    L.pll_utree_destroy(tr, None)
+    L.pll_parsimony_destroy(p)
+    nw = -(-(-(-sites // 32)) // 64) * 64
+    batch = int(os.environ.get("PLLHIP_PARS_SPR_BATCH", "0")) or min(64, -(-2048 // (nw // 64)))
+    prunes = 2 * tips - 4
+    model = float(prunes) * (2 * tips - 2) * 5 * S * nw * 4
+    return {"shape": name, "tips": tips, "sites": sites, "states": S, "round_ms": round(ms, 3), "prunes": prunes,
+            "tree_changed": nwk0 != nwk1, "stepwise_score": score.value, "round_score": cost.value,
+            "batch": batch, "model_bytes": model, "frac": round(model / (ms * 1e-3) / PEAK, 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="c2,c3,c5")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--seed", type=int, default=17)
+    ap.add_argument("--spr", action="store_true")
     a = ap.parse_args()
     lib = pc.PllLib(pc.PRODUCT_LIB)
     for name in a.shapes.split(","):
-        print(json.dumps(run(lib, name, *SHAPES[name], a.repeat, a.seed)), flush=True)
+        res = run_spr(lib, name, *SHAPES[name], a.seed) if a.spr else run(lib, name, *SHAPES[name], a.repeat, a.seed)
+        print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
