@@ -1628,8 +1628,8 @@ static int launch_chains_s20(Engine * e, const ChainBatch & batch, unsigned ncha
 
 // `extent`: site blocks of the largest partition the chains [chain_begin, chain_end) belong to
 static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_doubles, unsigned extent,
-                               unsigned chain_begin, unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu = 0,
-                               bool wide = false, bool transient = false)
+                               unsigned chain_begin, unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu,
+                               bool wide, bool transient)
 {
   const size_t lds = sizeof(double) * lds_doubles;
   const unsigned flags = []() { const char * v = getenv("PLLHIP_S20_NT"); return v ? (unsigned)atoi(v) & 3u : 0u; }();

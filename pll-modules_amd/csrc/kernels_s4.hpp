@@ -709,7 +709,9 @@ static bool chains_supported_s4(const Engine * e)
   return (e->R == 4 || e->R == 2 || e->R == 1) && (!e->coded_tips || e->lut_codes == 16);
 }
 
-static int launch_chains_s4(Engine * e, const ChainBatch & batch, unsigned nchains, unsigned longest)
+// (longest: operations of the longest chain -- every link has an LDS area of the same size; the tip tables are read
+// from memory whatever the codes in use)
+static int launch_chains_s4(Engine * e, const ChainBatch & batch, unsigned nchains, unsigned longest, unsigned /*lut_used*/)
 {
   const unsigned nchunks = (e->N + 63) / 64;
   static const int env_bpc = getenv("PLLHIP_S4_CHAIN_BPC") ? atoi(getenv("PLLHIP_S4_CHAIN_BPC")) : 8;
@@ -726,10 +728,10 @@ static int launch_chains_s4(Engine * e, const ChainBatch & batch, unsigned nchai
   return PLL_SUCCESS;
 }
 
-// `extent`: sites of the largest partition the chains [chain_begin, chain_end) belong to
+// `extent`: sites of the largest partition the chains [chain_begin, chain_end) belong to; `longest`: operations of
+// the longest chain (DevicePlan::lds_doubles of this family)
 static int launch_traverse_s4(Engine * e, const PlanView & plan, unsigned longest, unsigned extent, unsigned chain_begin,
-                              unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu = 0, bool transient = false,
-                              bool wide = false)
+                              unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu, bool wide, bool transient)
 {
   const unsigned nchunks = (extent + 63) / 64;
   const size_t lds = sizeof(double) * longest * s4_chain_op_lds(e->R);

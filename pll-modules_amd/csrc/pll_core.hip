@@ -1098,6 +1098,155 @@ static int launch_partials(Engine * e, const OpBatch & batch, unsigned nops)
   return launch_partials_generic(e, batch, nops);
 }
 
+// ---------------------------------------------------------------------------
+// The families with operation chains (4 states, 2 .. 32 states, 20 states): what the schedules of
+// pll_update_partials and pllhip_update_partials_batch and the class nodes of site repeats need of one.
+// chain_family() is the one place of that path that tells the families apart.
+// ---------------------------------------------------------------------------
+struct ChainFamily
+{
+  bool (*supported)(const Engine * e);                  // chains at the partition's rates, scaling and tip tables
+  unsigned chain_max;                                   // operations per chain
+  unsigned chain_lds;                                   // LDS doubles of one chain's tables (~0u: no limit)
+  // DevicePlan::lds_doubles and the LDS argument of `traverse` / `chains`: the doubles of the largest chain's tables
+  // (child_lds / wide_lds summed over its operations) -- or, with lds_is_length, the operations of the longest chain
+  // (4 states: every link has an area of the same size, s4_chain_op_lds)
+  bool lds_is_length;
+  unsigned (*extent)(const Engine * e);                 // PlanChain::extent: sites (4 states) or site blocks
+  unsigned (*child_lds)(const Engine * e, bool tip, unsigned lut_used);   // LDS doubles of a child's table in a chain
+  // ... of a wide tip with `rows` classes (a class node read through its row table, kernels_repeats.hpp): staged when
+  // they take no more than a coded tip's table may, else gathered from memory (0)
+  unsigned (*wide_lds)(const Engine * e, unsigned rows);
+  bool (*tables_in_lds)(const Engine * e, unsigned lut_used);             // PlanChain::flags bit 0
+  const double * (*pair_pfrag)(const Engine * e, unsigned matrix);        // PairLutJob::pfrag of a branch
+  bool (*fills_chip)(const Engine * e);                 // the site blocks alone keep the chip busy: one launch
+  unsigned (*units)(const Engine * e);                  // workgroups a member of a batch can use side by side
+  unsigned batch_wgs;                                   // workgroups per CU and row of a batch in one launch
+  // a resident schedule (DevicePlan, upload_plan): chains [begin, end) in `rows` grid rows
+  int (*traverse)(Engine * e, const PlanView & view, unsigned lds_doubles, unsigned extent, unsigned begin,
+                  unsigned end, unsigned rows, unsigned wgs, bool wide, bool transient);
+  // chains by value in the kernel arguments (null: none)
+  int (*chains)(Engine * e, const ChainBatch & batch, unsigned nchains, unsigned lds, unsigned lut_used);
+  // class nodes (kernels_repeats.hpp): row tables, class tables, the site-indexed vector of one node
+  void (*pair_lut)(Engine * e, const PairLutJob * jobs, unsigned njobs, unsigned max_rows);
+  void (*class_build)(Engine * e, const CherryJob * jobs, unsigned njobs, unsigned max_classes, unsigned ncodes);
+  void (*class_expand)(Engine * e, const Engine::Cherry & c, double * out);
+};
+
+static const ChainFamily CHAINS_S4 = {
+  .supported = chains_supported_s4, .chain_max = S4_CHAIN_MAX, .chain_lds = ~0u, .lds_is_length = true,
+  .extent = [](const Engine * e) { return e->N; },
+  .child_lds = [](const Engine *, bool, unsigned) { return 0u; },
+  .wide_lds = [](const Engine *, unsigned) { return 0u; },
+  .tables_in_lds = [](const Engine *, unsigned) { return false; },
+  .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pmat + (size_t)m * e->R * 16; },
+  .fills_chip = [](const Engine * e) { return (e->N + 63) / 64 >= 48u * e->cu_count; },
+  .units = [](const Engine * e) { return (e->N + 255u) / 256u; }, .batch_wgs = 3,
+  .traverse = launch_traverse_s4, .chains = launch_chains_s4,
+  .pair_lut = [](Engine * e, const PairLutJob * jobs, unsigned njobs, unsigned max_rows)
+  { hipLaunchKernelGGL(k_pair_lut_s4, dim3((max_rows * e->R + 255) / 256, njobs), dim3(256), 0, e->stream, jobs, e->R); },
+  .class_build = [](Engine * e, const CherryJob * jobs, unsigned njobs, unsigned max_classes, unsigned ncodes)
+  { hipLaunchKernelGGL(k_cherry_build_s4, dim3((max_classes + 255) / 256, njobs), dim3(256), 0, e->stream, jobs, e->R, ncodes); },
+  .class_expand = [](Engine * e, const Engine::Cherry & c, double * out)
+  {
+    hipLaunchKernelGGL(k_cherry_expand_s4, dim3(std::max(1u, std::min((e->N * e->R + 255u) / 256u, e->cu_count * 8u))), dim3(256), 0,
+                       e->stream, c.table, c.pair, e->N, e->R, out);
+  },
+};
+
+static const ChainFamily CHAINS_S16 = {
+  .supported = chains_supported_s16, .chain_max = S16_CHAIN_MAX, .chain_lds = S16_CHAIN_LDS, .lds_is_length = false,
+  .extent = [](const Engine * e) { return e->nblk; },
+  .child_lds = [](const Engine * e, bool tip, unsigned) { return s16_chain_slot(e, tip); },
+  .wide_lds = [](const Engine * e, unsigned rows) { return e->R * rows * e->S <= S16_LUT_LDS ? ((e->R * rows * e->S + 7u) & ~7u) : 0u; },
+  .tables_in_lds = [](const Engine * e, unsigned) { return s16_chain_lut_lds(e); },
+  .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pmat + (size_t)m * e->R * e->S * e->Sp; },
+  .fills_chip = [](const Engine * e) { return e->nblk >= 12u * e->cu_count && e->nblk < 48u * e->cu_count && e->S > 8; },
+  .units = [](const Engine * e) { return (e->nblk + 7u) / 8u; }, .batch_wgs = 1,
+  .traverse = launch_traverse_s16, .chains = nullptr,        // (chains exist in the resident form only)
+  .pair_lut = [](Engine * e, const PairLutJob * jobs, unsigned njobs, unsigned max_rows)
+  {
+    const dim3 gp(((max_rows + S20_BS - 1) / S20_BS + 3) / 4, njobs);
+#define PLLHIP_CALL(KK) \
+    hipLaunchKernelGGL(k_pair_lut_s16<KK>, gp, dim3(256), sizeof(double) * e->R * s16_fr(KK), e->stream, jobs, e->R, e->S, e->Sp)
+    PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_CALL);
+#undef PLLHIP_CALL
+  },
+  .class_build = [](Engine * e, const CherryJob * jobs, unsigned njobs, unsigned max_classes, unsigned ncodes)
+  {
+    const dim3 gb(((max_classes + S20_BS - 1) / S20_BS + 3) / 4, njobs);
+#define PLLHIP_CALL(KK) hipLaunchKernelGGL(k_cherry_build_s16<KK>, gb, dim3(256), 0, e->stream, jobs, ncodes, e->R, e->S)
+    PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_CALL);
+#undef PLLHIP_CALL
+  },
+  .class_expand = [](Engine * e, const Engine::Cherry & c, double * out)
+  {
+#define PLLHIP_CALL(KK) \
+    hipLaunchKernelGGL(k_cherry_expand_s16<KK>, dim3(std::max(1u, std::min((e->nblk + 3) / 4, e->cu_count * 8u))), dim3(256), 0, \
+                       e->stream, c.table, c.pair, e->nblk, e->R, out)
+    PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_CALL);
+#undef PLLHIP_CALL
+  },
+};
+
+static const ChainFamily CHAINS_S20 = {
+  .supported = chains_supported_s20, .chain_max = S20_CHAIN_MAX, .chain_lds = S20_CHAIN_LDS, .lds_is_length = false,
+  .extent = [](const Engine * e) { return e->nblk; },
+  .child_lds = s20_chain_slot,
+  .wide_lds = [](const Engine * e, unsigned rows) { return e->R * rows * S20_LUT_RS <= 2560u ? ((e->R * rows * S20_LUT_RS + 7u) & ~7u) : 0u; },
+  .tables_in_lds = s20_chain_lut_lds,
+  .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pfrag + (size_t)m * e->R * 400; },
+  .fills_chip = [](const Engine * e) { return e->nblk >= 6u * e->cu_count && e->nblk < 24u * e->cu_count; },
+  .units = [](const Engine * e) { return (e->nblk + 7u) / 8u; }, .batch_wgs = 1,
+  .traverse = launch_traverse_s20, .chains = launch_chains_s20,
+  .pair_lut = [](Engine * e, const PairLutJob * jobs, unsigned njobs, unsigned max_rows)
+  {
+    const dim3 gp(((max_rows + S20_BS - 1) / S20_BS + 3) / 4, njobs);
+    const size_t lds = sizeof(double) * e->R * S20_CFRAGS;
+    if (e->R == 4) hipLaunchKernelGGL(k_pair_lut<4>, gp, dim3(256), lds, e->stream, jobs);
+    else if (e->R == 2) hipLaunchKernelGGL(k_pair_lut<2>, gp, dim3(256), lds, e->stream, jobs);
+    else hipLaunchKernelGGL(k_pair_lut<1>, gp, dim3(256), lds, e->stream, jobs);
+  },
+  .class_build = [](Engine * e, const CherryJob * jobs, unsigned njobs, unsigned max_classes, unsigned ncodes)
+  {
+    const dim3 gb(((max_classes + S20_BS - 1) / S20_BS + 3) / 4, njobs);
+    if (e->R == 4) hipLaunchKernelGGL(k_cherry_build<4>, gb, dim3(256), 0, e->stream, jobs, ncodes);
+    else if (e->R == 2) hipLaunchKernelGGL(k_cherry_build<2>, gb, dim3(256), 0, e->stream, jobs, ncodes);
+    else hipLaunchKernelGGL(k_cherry_build<1>, gb, dim3(256), 0, e->stream, jobs, ncodes);
+  },
+  .class_expand = [](Engine * e, const Engine::Cherry & c, double * out)
+  {
+    hipLaunchKernelGGL(k_cherry_expand, dim3(std::max(1u, std::min((e->nblk + 3) / 4, e->cu_count * 8u))), dim3(256), 0,
+                       e->stream, c.table, c.pair, e->nblk, e->R, out);
+  },
+};
+
+// the family's entry whatever the partition's shape (class nodes exist for these families only)
+static const ChainFamily * family_entry(KernelFamily f)
+{
+  return f == KernelFamily::S4 ? &CHAINS_S4 : f == KernelFamily::S16 ? &CHAINS_S16 : f == KernelFamily::S20 ? &CHAINS_S20
+                                                                                                          : nullptr;
+}
+
+// the chains of this partition, or null: none in its family or at its shape, or PLLHIP_CHAINS=0 (the plain level
+// schedule)
+static const ChainFamily * chain_family(const Engine * e)
+{
+  static const int use_chains = getenv("PLLHIP_CHAINS") ? atoi(getenv("PLLHIP_CHAINS")) : 1;
+  const ChainFamily * f = family_entry(e->family);
+  return use_chains && f && f->supported(e) ? f : nullptr;
+}
+
+// a tip that is read through byte codes and the partition's lookup tables (PLL_ATTRIB_PATTERN_TIP); without the
+// attribute a tip is a vector -- and, when it came through pll_set_tip_states, a class node as well (upload_tip_classes)
+static bool coded_tip(const Engine * e, unsigned idx) { return e->coded_tips && idx < e->tips; }
+
+// LDS doubles of the table of child `idx` in a chain kernel; wide: the child is read as a wide tip
+static unsigned child_table_lds(const Engine * e, const ChainFamily & f, unsigned idx, unsigned lut_used, bool wide)
+{
+  return wide ? f.wide_lds(e, e->cherries[idx].nclasses) : f.child_lds(e, coded_tip(e, idx), lut_used);
+}
+
 // Chain schedule of an operation list (see ChainBatch, engine.h).  Accepted only for
 // lists with the shape of a tree traversal -- every vector written once, read by at
 // most one later operation, nothing overwritten after it was read, child scalers
@@ -1111,32 +1260,9 @@ struct ChainPlan
   int rounds = 0;
 };
 
-// LDS doubles of the rows of a wide tip (a class node read through its row table, kernels_repeats.hpp) with `rows`
-// classes: staged when they take no more than a coded tip's table may, else gathered from memory (0)
-static unsigned wide_slot(const Engine * e, unsigned rows)
-{
-  if (e->family == KernelFamily::S20)
-    return e->R * rows * S20_LUT_RS <= 2560u ? ((e->R * rows * S20_LUT_RS + 7u) & ~7u) : 0u;
-  if (e->family == KernelFamily::S16)
-    return e->R * rows * e->S <= S16_LUT_LDS ? ((e->R * rows * e->S + 7u) & ~7u) : 0u;
-  return 0u;
-}
-
-// LDS doubles the tables of operation `op` take in a chain kernel (20 states; 0 otherwise)
-// wide1 / wide2: the child is read as a wide tip
-static unsigned chain_op_lds(const Engine * e, const pll_operation_t & op, unsigned lut_used, bool wide1 = false, bool wide2 = false)
-{
-  const bool t1 = e->coded_tips && op.child1_clv_index < e->tips;
-  const bool t2 = e->coded_tips && op.child2_clv_index < e->tips;
-  if (e->family != KernelFamily::S16 && e->family != KernelFamily::S20) return 0u;
-  const bool s16 = e->family == KernelFamily::S16;
-  const unsigned a = wide1 ? wide_slot(e, e->cherries[op.child1_clv_index].nclasses) : s16 ? s16_chain_slot(e, t1) : s20_chain_slot(e, t1, lut_used);
-  const unsigned b = wide2 ? wide_slot(e, e->cherries[op.child2_clv_index].nclasses) : s16 ? s16_chain_slot(e, t2) : s20_chain_slot(e, t2, lut_used);
-  return a + b;
-}
-
+// f: the family whose tables count against lds_cap (null: no tables, the shape alone)
 // wide: [2 * count] which children are read as wide tips (null: none)
-static bool plan_chains(const Engine * e, const pll_operation_t * ops, unsigned count, unsigned max_len,
+static bool plan_chains(const Engine * e, const ChainFamily * f, const pll_operation_t * ops, unsigned count, unsigned max_len,
                         unsigned lds_cap, unsigned lut_used, ChainPlan & plan, const std::vector<unsigned char> * wide = nullptr)
 {
   std::vector<int> producer(e->nodes, -1), sc_writer(e->nscalers, -1), chain_of(count, -1);
@@ -1180,7 +1306,9 @@ static bool plan_chains(const Engine * e, const pll_operation_t * ops, unsigned 
     int heavy = -1;                               // which child (0 / 1) continues a chain
     if (pr[0] >= 0 && (pr[1] < 0 || size[pr[0]] >= size[pr[1]])) heavy = 0;
     else if (pr[1] >= 0) heavy = 1;
-    const unsigned cost = chain_op_lds(e, op, lut_used, wide && !wide->empty() && (*wide)[2 * k], wide && !wide->empty() && (*wide)[2 * k + 1]);
+    const bool w = wide && !wide->empty();
+    const unsigned cost = !f ? 0u : child_table_lds(e, *f, op.child1_clv_index, lut_used, w && (*wide)[2 * k]) +
+                                    child_table_lds(e, *f, op.child2_clv_index, lut_used, w && (*wide)[2 * k + 1]);
     if (heavy >= 0 && (plan.chains[chain_of[pr[heavy]]].size() >= max_len ||
                        plan.lds[chain_of[pr[heavy]]] + cost > lds_cap)) heavy = -1;
     int round = 0;
@@ -1289,20 +1417,7 @@ static int need_clv(Engine * e, unsigned idx)
   if (c.valid && c.scaler_index >= 0 && (size_t)c.scaler_index < e->scaler_lazy.size() && e->scaler_lazy[c.scaler_index] == (int)idx &&
       !need_scaler(e, c.scaler_index)) return PLL_FAILURE;
   if (!c.valid || c.materialized) return PLL_SUCCESS;
-  if (e->family == KernelFamily::S4)
-    hipLaunchKernelGGL(k_cherry_expand_s4, dim3(std::max(1u, std::min((e->N * e->R + 255u) / 256u, e->cu_count * 8u))), dim3(256), 0,
-                       e->stream, c.table, c.pair, e->N, e->R, e->d_clv[idx]);
-  else if (e->family == KernelFamily::S16)
-  {
-#define PLLHIP_CALL(KK) \
-    hipLaunchKernelGGL(k_cherry_expand_s16<KK>, dim3(std::max(1u, std::min((e->nblk + 3) / 4, e->cu_count * 8u))), dim3(256), 0, \
-                       e->stream, c.table, c.pair, e->nblk, e->R, e->d_clv[idx])
-    PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_CALL);
-#undef PLLHIP_CALL
-  }
-  else
-    hipLaunchKernelGGL(k_cherry_expand, dim3(std::max(1u, std::min((e->nblk + 3) / 4, e->cu_count * 8u))), dim3(256), 0,
-                       e->stream, c.table, c.pair, e->nblk, e->R, e->d_clv[idx]);
+  family_entry(e->family)->class_expand(e, c, e->d_clv[idx]);
   PLLHIP_TRY(hipGetLastError());
   c.materialized = true;
   e->repeat_stats.expansions++;
@@ -1357,10 +1472,6 @@ static unsigned long long class_child_version(const Engine * e, unsigned idx)
 {
   return idx < e->tips ? e->tip_version[idx] : e->cherries[idx].version;
 }
-
-// a tip that is read through byte codes and the partition's lookup tables (PLL_ATTRIB_PATTERN_TIP); without the
-// attribute a tip is a vector -- and, when it came through pll_set_tip_states, a class node as well (upload_tip_classes)
-static bool coded_tip(const Engine * e, unsigned idx) { return e->coded_tips && idx < e->tips; }
 
 // the class table of a child was made under the code table in use (a tip's own classes do not depend on it)
 static bool class_codes_match(const Engine * e, unsigned idx, unsigned lut_used)
@@ -1639,437 +1750,421 @@ static void fill_desc(const Engine * e, const pll_operation_t & op, OpDesc & d, 
 // the shape of a tree traversal (plan_chains).
 static std::atomic<unsigned long long> plan_generation{0};
 
-static bool prepare_schedule(Engine * e, const pll_partition_t * p, const pll_operation_t * ops, unsigned count,
-                             unsigned mode, const RepeatPlan * rp = nullptr,
-                             const pll_operation_t * all_ops = nullptr, unsigned all_count = 0, bool transient = false)
+struct ScheduleRequest
 {
-  const bool chains20 = e->family == KernelFamily::S20, chains16 = e->family == KernelFamily::S16;
-  const bool chains4 = e->family == KernelFamily::S4;
-  const unsigned lut_used = std::max(1u, std::min(codes_in_use(e, p), e->lut_codes));
-  const unsigned chain_max = chains20 ? S20_CHAIN_MAX : chains16 ? S16_CHAIN_MAX : S4_CHAIN_MAX;
-  const unsigned chain_lds = chains20 ? S20_CHAIN_LDS : chains16 ? S16_CHAIN_LDS : ~0u;
-  DevicePlan & dp = e->plan;
-  const bool by_rounds = mode == 0;
-  ChainPlan plan;
-  // site repeats: children that are cherries kept per class are read as wide tips (kernels_repeats.hpp)
-  std::vector<unsigned char> wide(e->cherries.empty() ? 0 : 2 * (size_t)count, 0);
-  unsigned nwide = 0;
-  if (!wide.empty())
+  const pll_operation_t * ops;                   // the list as the caller passed it
+  unsigned count;
+  unsigned mode;
+  bool transient;                                // an evaluate-only traversal (pllhip_set_transient)
+  const RepeatPlan * rp;                         // site repeats: the class operations and the rest (null: none)
+};
+
+struct ScheduleBuild                             // the schedule being built (DevicePlan::bytes)
+{
+  std::vector<PlanOp> pops;
+  std::vector<PlanChain> pchains;
+  std::vector<PairLutJob> pair_jobs;             // row tables of the wide tips of the chains
+  std::vector<CherryJob> cherry_jobs;            // class operations, by level
+  std::vector<PairLutJob> level_pairs;           // row tables of class children, by level of their parent
+  size_t pairlut_used = 0;                       // doubles of e->d_pairlut handed out
+  unsigned nops = 0, lds_max = 0;
+};
+
+// site repeats: children that are cherries kept per class are read as wide tips (kernels_repeats.hpp);
+// wide[2 k + x] for child x of operation k
+static bool mark_wide_tips(Engine * e, const pll_operation_t * ops, unsigned count, unsigned lut_used,
+                           std::vector<unsigned char> & wide, unsigned & nwide)
+{
+  wide.assign(e->cherries.empty() ? 0 : 2 * (size_t)count, 0);
+  nwide = 0;
+  if (wide.empty()) return true;
+  std::vector<char> made(e->nodes, 0);
+  for (unsigned k = 0; k < count; ++k)
   {
-    std::vector<char> made(e->nodes, 0);
-    for (unsigned k = 0; k < count; ++k)
+    const unsigned child[2] = {ops[k].child1_clv_index, ops[k].child2_clv_index};
+    const int child_scaler[2] = {ops[k].child1_scaler_index, ops[k].child2_scaler_index};
+    for (int x = 0; x < 2; ++x)
+    {
+      // (counts of a buffer that another class node stands for: written out first)
+      if (child_scaler[x] >= 0 && e->scaler_lazy[child_scaler[x]] >= 0 && e->scaler_lazy[child_scaler[x]] != (int)child[x] &&
+          !need_scaler(e, child_scaler[x])) return false;
+      if (coded_tip(e, child[x]) || made[child[x]] || !e->cherries[child[x]].valid) continue;
+      // (a cherry built under another code table -- a tip has taken a new ambiguity code since -- is read
+      // through its expanded vector: its classes are not the ones this schedule indexes; so is a class node whose
+      // counts are asked for under another scale buffer than the one its operation wrote)
+      const Engine::Cherry & cc = e->cherries[child[x]];
+      if (class_codes_match(e, child[x], lut_used) && (child_scaler[x] == cc.scaler_index)) { wide[2 * k + x] = 1; ++nwide; }
+      else if (!need_clv(e, child[x])) return false;
+    }
+    made[ops[k].parent_clv_index] = 1;
+  }
+  return true;
+}
+
+// the cache key: the list as the caller passed it (the cherries taken out of it are part of the schedule), the codes
+// in use, the mode, the wide tips, and which operations are kept per class (the same list can meet other class nodes
+// of earlier calls)
+static std::vector<unsigned char> schedule_key(const ScheduleRequest & rq, unsigned lut_used, const std::vector<unsigned char> & wide)
+{
+  std::vector<unsigned char> tracked(rq.rp ? rq.count : 0, 0);
+  if (rq.rp) for (unsigned k : rq.rp->cherry_ops) tracked[k] = 1;
+  const size_t list_bytes = (size_t)rq.count * sizeof(pll_operation_t);
+  std::vector<unsigned char> key(3 * sizeof(unsigned) + list_bytes + wide.size() + tracked.size());
+  const unsigned mode_key = rq.mode | (rq.transient ? 0x100u : 0u);
+  memcpy(key.data(), &rq.count, sizeof(unsigned));
+  memcpy(key.data() + sizeof(unsigned), &lut_used, sizeof(unsigned));
+  memcpy(key.data() + 2 * sizeof(unsigned), &mode_key, sizeof(unsigned));
+  memcpy(key.data() + 3 * sizeof(unsigned), rq.ops, list_bytes);
+  if (!wide.empty()) memcpy(key.data() + 3 * sizeof(unsigned) + list_bytes, wide.data(), wide.size());
+  if (!tracked.empty()) memcpy(key.data() + key.size() - tracked.size(), tracked.data(), tracked.size());
+  return key;
+}
+
+// room in e->d_pairlut for the row tables of the schedule: one per (class node, branch above it) -- the wide tips of
+// the chains and the class children of the class operations
+static bool reserve_pair_tables(Engine * e, const ScheduleRequest & rq, const pll_operation_t * ops, unsigned count,
+                                const std::vector<unsigned char> & wide)
+{
+  size_t rows = 0;
+  for (unsigned k = 0; k < count && !wide.empty(); ++k)
+  {
+    if (wide[2 * k]) rows += e->cherries[ops[k].child1_clv_index].nclasses;
+    if (wide[2 * k + 1]) rows += e->cherries[ops[k].child2_clv_index].nclasses;
+  }
+  if (rq.rp)
+    for (unsigned k : rq.rp->cherry_ops)
+    {
+      if (!coded_tip(e, rq.ops[k].child1_clv_index)) rows += e->cherries[rq.ops[k].child1_clv_index].nclasses;
+      if (!coded_tip(e, rq.ops[k].child2_clv_index)) rows += e->cherries[rq.ops[k].child2_clv_index].nclasses;
+    }
+  const size_t need = rows * e->R * e->S;
+  if (need <= e->pairlut_cap) return true;
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return false;
+  (void)hipFree(e->d_pairlut);
+  e->d_pairlut = nullptr;
+  e->pairlut_cap = 0;
+  if (!dev_alloc(&e->d_pairlut, 2 * need, "wide-tip lookup tables")) return false;
+  e->pairlut_cap = 2 * need;
+  return true;
+}
+
+// Order of the chains.  By rounds: round by round, longest chains first within a round (their workgroups are
+// dispatched first).  Otherwise depth first, so that a vector is consumed soon after it was written (the kernel
+// walks slabs of sites through ALL chains: what a slab wrote a few chains ago is still in L2 / the memory-side
+// cache).  The chains form a tree -- chain c feeds the chain that reads c's last vector as a child from memory --
+// and the larger feeder goes first, which keeps the number of results waiting for their consumer small.
+static std::vector<size_t> chain_order(const Engine * e, const pll_operation_t * ops, unsigned count, const ChainPlan & plan,
+                                       bool by_rounds)
+{
+  const size_t nch = plan.chains.size();
+  std::vector<size_t> order;
+  order.reserve(nch);
+  if (by_rounds)
+  {
+    for (size_t c = 0; c < nch; ++c) order.push_back(c);
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b)
+    {
+      if (plan.launch[a] != plan.launch[b]) return plan.launch[a] < plan.launch[b];
+      return plan.chains[a].size() > plan.chains[b].size();
+    });
+    return order;
+  }
+  std::vector<int> chain_at(count, -1), producer_op(e->nodes, -1);
+  std::vector<unsigned> weight(nch, 0);
+  std::vector<std::vector<size_t>> feeders(nch);
+  std::vector<char> is_feeder(nch, 0);
+  for (size_t c = 0; c < nch; ++c)
+    for (unsigned k : plan.chains[c]) { chain_at[k] = (int)c; producer_op[ops[k].parent_clv_index] = (int)k; }
+  for (size_t c = 0; c < nch; ++c)                  // chains are numbered in creation order: feeders first
+  {
+    weight[c] += (unsigned)plan.chains[c].size();
+    for (unsigned k : plan.chains[c])
     {
       const unsigned child[2] = {ops[k].child1_clv_index, ops[k].child2_clv_index};
-      const int child_scaler[2] = {ops[k].child1_scaler_index, ops[k].child2_scaler_index};
       for (int x = 0; x < 2; ++x)
       {
-        // (counts of a buffer that another class node stands for: written out first)
-        if (child_scaler[x] >= 0 && e->scaler_lazy[child_scaler[x]] >= 0 && e->scaler_lazy[child_scaler[x]] != (int)child[x] &&
-            !need_scaler(e, child_scaler[x])) return false;
-        if (coded_tip(e, child[x]) || made[child[x]] || !e->cherries[child[x]].valid) continue;
-        // (a cherry built under another code table -- a tip has taken a new ambiguity code since -- is read
-        // through its expanded vector: its classes are not the ones this schedule indexes; so is a class node whose
-        // counts are asked for under another scale buffer than the one its operation wrote)
-        const Engine::Cherry & cc = e->cherries[child[x]];
-        if (class_codes_match(e, child[x], lut_used) && (child_scaler[x] == cc.scaler_index)) { wide[2 * k + x] = 1; ++nwide; }
-        else if (!need_clv(e, child[x])) return false;
+        const int pk = producer_op[child[x]];
+        if (pk < 0 || pk >= (int)k || chain_at[pk] == (int)c) continue;
+        feeders[c].push_back((size_t)chain_at[pk]);
+        is_feeder[chain_at[pk]] = 1;
+        weight[c] += weight[chain_at[pk]];
       }
-      made[ops[k].parent_clv_index] = 1;
     }
   }
-  // (the key holds the list as the caller passed it: the cherries taken out of it are part of the schedule)
-  const pll_operation_t * key_ops = all_ops ? all_ops : ops;
-  const unsigned key_count = all_ops ? all_count : count;
-  // (... and which of its operations are kept per class: the same list can meet other class nodes of earlier calls)
-  std::vector<unsigned char> tracked(rp && rp->active ? key_count : 0, 0);
-  if (!tracked.empty()) for (unsigned k : rp->cherry_ops) tracked[k] = 1;
-  std::vector<unsigned char> key(3 * sizeof(unsigned) + (size_t)key_count * sizeof(pll_operation_t) + wide.size() + tracked.size());
-  memcpy(key.data(), &key_count, sizeof(unsigned));
-  memcpy(key.data() + sizeof(unsigned), &lut_used, sizeof(unsigned));
-  const unsigned mode_key = mode | (transient ? 0x100u : 0u);
-  memcpy(key.data() + 2 * sizeof(unsigned), &mode_key, sizeof(unsigned));
-  memcpy(key.data() + 3 * sizeof(unsigned), key_ops, (size_t)key_count * sizeof(pll_operation_t));
-  if (!wide.empty()) memcpy(key.data() + 3 * sizeof(unsigned) + (size_t)key_count * sizeof(pll_operation_t), wide.data(), wide.size());
-  if (!tracked.empty()) memcpy(key.data() + key.size() - tracked.size(), tracked.data(), tracked.size());
-  bool have = !dp.key.empty() && dp.key == key;
-  const unsigned rep_codes = lut_used;
-  if (!have && (nwide || (rp && rp->active)))
+  std::vector<std::pair<size_t, size_t>> stack;   // (chain, next feeder)
+  for (size_t root = 0; root < nch; ++root)
   {
-    // the row tables of the schedule: one per (class node, branch above it) -- the wide tips of the chains and the
-    // class children of the class operations
-    size_t rows = 0;
-    for (unsigned k = 0; k < count && !wide.empty(); ++k)
+    if (is_feeder[root]) continue;
+    stack.emplace_back(root, 0);
+    while (!stack.empty())
     {
-      if (wide[2 * k]) rows += e->cherries[ops[k].child1_clv_index].nclasses;
-      if (wide[2 * k + 1]) rows += e->cherries[ops[k].child2_clv_index].nclasses;
-    }
-    if (rp && rp->active)
-      for (unsigned k : rp->cherry_ops)
-      {
-        if (!coded_tip(e, all_ops[k].child1_clv_index)) rows += e->cherries[all_ops[k].child1_clv_index].nclasses;
-        if (!coded_tip(e, all_ops[k].child2_clv_index)) rows += e->cherries[all_ops[k].child2_clv_index].nclasses;
-      }
-    const size_t need = rows * e->R * e->S;
-    if (need > e->pairlut_cap)
-    {
-      if (hipStreamSynchronize(e->stream) != hipSuccess) return false;
-      (void)hipFree(e->d_pairlut);
-      e->d_pairlut = nullptr;
-      e->pairlut_cap = 0;
-      if (!dev_alloc(&e->d_pairlut, 2 * need, "wide-tip lookup tables")) return false;
-      e->pairlut_cap = 2 * need;
+      const size_t c = stack.back().first;
+      if (stack.back().second == 0)
+        std::stable_sort(feeders[c].begin(), feeders[c].end(), [&](size_t a, size_t b) { return weight[a] > weight[b]; });
+      if (stack.back().second < feeders[c].size()) { const size_t f = feeders[c][stack.back().second++]; stack.emplace_back(f, 0); }
+      else { order.push_back(c); stack.pop_back(); }
     }
   }
-  std::vector<PairLutJob> pair_jobs;             // row tables of the wide tips of the chains
-  size_t pairlut_used = 0;
-  if (!have && plan_chains(e, ops, count, chain_max, chain_lds, lut_used, plan, &wide))
+  return order;
+}
+
+// the row table of class node `c` through matrix `matrix` (the branch above it): its job, and where it will be
+static const double * push_pair_job(const Engine * e, const ChainFamily & f, const Engine::Cherry & c, unsigned matrix,
+                                    ScheduleBuild & sb, std::vector<PairLutJob> & jobs)
+{
+  PairLutJob job;
+  job.table = c.table;
+  job.pfrag = f.pair_pfrag(e, matrix);
+  job.out = e->d_pairlut + sb.pairlut_used;
+  job.nrows = c.nclasses;
+  sb.pairlut_used += (size_t)e->R * c.nclasses * e->S;
+  jobs.push_back(job);
+  return job.out;
+}
+
+// the last launch of the schedule ends here: its running totals become its own share
+static void close_launch(DevicePlan & dp, const ScheduleBuild & sb)
+{
+  if (dp.launches.empty()) return;
+  DevicePlan::Launch & done = dp.launches.back();
+  done.end = (unsigned)sb.pchains.size();
+  done.ops = sb.nops - done.ops;
+  done.bytes = dp.algo_bytes - done.bytes; done.flops = dp.algo_flops - done.flops; done.min_bytes = dp.min_bytes - done.min_bytes;
+}
+
+// the PlanOp / PlanChain entries of the chains in `order`, and the launches they fall into (the last one left open)
+static void emit_chains(const Engine * e, const ChainFamily & f, const pll_operation_t * ops, const ChainPlan & plan,
+                        const std::vector<size_t> & order, const std::vector<unsigned char> & wide, unsigned lut_used,
+                        const ScheduleRequest & rq, DevicePlan & dp, ScheduleBuild & sb)
+{
+  const bool by_rounds = rq.mode == 0;
+  dp.algo_bytes = dp.algo_flops = dp.min_bytes = 0.0;
+  dp.launches.clear();
+  int cur_round = -1;
+  const unsigned chain_flags = f.tables_in_lds(e, lut_used) ? 1u : 0u;
+  for (size_t c : order)
   {
-    // Order of the chains: depth first, so that a vector is consumed soon after it was written
-    // (the kernel walks slabs of sites through ALL chains: what a slab wrote a few chains ago
-    // is still in L2 / the memory-side cache).  The chains form a tree -- chain c feeds the
-    // chain that reads c's last vector as a child from memory -- and the larger feeder goes
-    // first, which keeps the number of results waiting for their consumer small.
-    const size_t nch = plan.chains.size();
-    std::vector<int> chain_at(count, -1), producer_op(e->nodes, -1);
-    std::vector<unsigned> weight(nch, 0);
-    std::vector<std::vector<size_t>> feeders(nch);
-    std::vector<char> is_feeder(nch, 0);
-    for (size_t c = 0; c < nch; ++c)
-      for (unsigned k : plan.chains[c]) { chain_at[k] = (int)c; producer_op[ops[k].parent_clv_index] = (int)k; }
-    for (size_t c = 0; c < nch; ++c)                  // chains are numbered in creation order: feeders first
+    const std::vector<unsigned> & ch = plan.chains[c];
+    if (dp.launches.empty() || (by_rounds && plan.launch[c] != cur_round))
     {
-      weight[c] += (unsigned)plan.chains[c].size();
-      for (unsigned k : plan.chains[c])
+      close_launch(dp, sb);
+      const unsigned at = (unsigned)sb.pchains.size();     // (ops, bytes, ...: running totals until the launch is closed)
+      dp.launches.push_back({at, at, 1, sb.nops, dp.algo_bytes, dp.algo_flops, dp.min_bytes});
+      cur_round = plan.launch[c];
+    }
+    sb.pchains.push_back({sb.nops, (unsigned)ch.size(), f.extent(e), e->lut_codes, lut_used, chain_flags});
+    unsigned off = 0;
+    for (size_t i = 0; i < ch.size(); ++i)
+    {
+      const pll_operation_t & o = ops[ch[i]];
+      PlanOp & po = sb.pops[sb.nops++];
+      memset(&po, 0, sizeof(po));
+      const double before = dp.algo_bytes;
+      fill_desc(e, o, po.d, dp.algo_bytes, dp.algo_flops);
+      po.carried = i ? plan.carried[ch[i]] : 0;
+      // an evaluate-only traversal: the vectors inside a chain are handed on in registers only
+      po.flags = (rq.transient && i + 1 < ch.size()) ? 1u : 0u;
+      double wide_saved = (po.flags & 1u) ? (double)e->N * e->R * 8.0 * e->S : 0.0;
+      const bool w[2] = {!wide.empty() && wide[2 * ch[i]], !wide.empty() && wide[2 * ch[i] + 1]};
+      for (int x = 0; x < 2; ++x)
       {
-        const unsigned child[2] = {ops[k].child1_clv_index, ops[k].child2_clv_index};
-        for (int x = 0; x < 2; ++x)
-        {
-          const int pk = producer_op[child[x]];
-          if (pk < 0 || pk >= (int)k || chain_at[pk] == (int)c) continue;
-          feeders[c].push_back((size_t)chain_at[pk]);
-          is_feeder[chain_at[pk]] = 1;
-          weight[c] += weight[chain_at[pk]];
-        }
+        if (!w[x]) continue;
+        const Engine::Cherry & cc = e->cherries[x ? o.child2_clv_index : o.child1_clv_index];
+        const double * rows = push_pair_job(e, f, cc, x ? o.child2_matrix_index : o.child1_matrix_index, sb, sb.pair_jobs);
+        // wide tip: no vector, no byte codes; pfrag = class codes, lut = its table, childN_index = table rows
+        // (... and its scaler counts per class)
+        // (bit 1 / 2 of the flags: few rows, staged in LDS by the chain kernels of the 20- and 2 .. 32-state families)
+        if (f.wide_lds(e, cc.nclasses)) po.flags |= 2u << x;
+        if (x) { po.d.clv2 = nullptr; po.d.codes2 = nullptr; po.d.pfrag2 = reinterpret_cast<const double *>(cc.pair); po.d.lut2 = rows; po.d.child2_index = cc.nclasses;
+                 if (po.d.scaler2) po.d.scaler2 = cc.counts; }
+        else   { po.d.clv1 = nullptr; po.d.codes1 = nullptr; po.d.pfrag1 = reinterpret_cast<const double *>(cc.pair); po.d.lut1 = rows; po.d.child1_index = cc.nclasses;
+                 if (po.d.scaler1) po.d.scaler1 = cc.counts; }
+        wide_saved += (double)e->N * e->R * 8.0 * e->S - 4.0 * e->N;      // class codes instead of the vector
       }
+      // the handed-over child stays in registers: neither its vector nor its scaler counts are read
+      dp.min_bytes += dp.algo_bytes - before - wide_saved;
+      if (po.carried)
+        dp.min_bytes -= (double)e->N * e->R * 8.0 * e->S +
+                        ((po.carried == 1 ? po.d.scaler1 : po.d.scaler2) ? 4.0 * (double)e->N * (e->rate_scalers ? e->R : 1) : 0.0);
+      po.slot1 = off;
+      off += child_table_lds(e, f, o.child1_clv_index, lut_used, w[0]);
+      po.slot2 = off;
+      off += child_table_lds(e, f, o.child2_clv_index, lut_used, w[1]);
     }
-    std::vector<size_t> order;
-    order.reserve(nch);
-    if (by_rounds)
+    sb.lds_max = std::max(sb.lds_max, f.lds_is_length ? (unsigned)ch.size() : off);
+  }
+}
+
+// site repeats: the operations the schedule keeps per class (taken out of the list by the caller), by level, with the
+// row tables of their class children
+static void emit_repeat_levels(const Engine * e, const ChainFamily & f, const ScheduleRequest & rq, DevicePlan & dp,
+                               ScheduleBuild & sb)
+{
+  dp.repeat_levels.clear();
+  dp.repeat_classes = 0;
+  if (!rq.rp) return;
+  const size_t lut_stride = (size_t)e->R * e->lut_codes * e->S;
+  const size_t nrp = rq.rp->cherry_ops.size();
+  std::vector<int> node_level(e->nodes, -1);
+  std::vector<unsigned> lvl(nrp, 0), order(nrp);
+  unsigned max_level = 0;
+  for (size_t x = 0; x < nrp; ++x)
+  {
+    const pll_operation_t & o = rq.ops[rq.rp->cherry_ops[x]];
+    unsigned l = 0;
+    if (o.child1_clv_index >= e->tips) l = std::max(l, 1u + (unsigned)std::max(node_level[o.child1_clv_index], 0));
+    if (o.child2_clv_index >= e->tips) l = std::max(l, 1u + (unsigned)std::max(node_level[o.child2_clv_index], 0));
+    lvl[x] = l;
+    node_level[o.parent_clv_index] = (int)l;
+    max_level = std::max(max_level, l);
+    order[x] = (unsigned)x;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](unsigned a, unsigned b) { return lvl[a] < lvl[b]; });
+  size_t at = 0;
+  for (unsigned l = 0; l <= max_level; ++l)
+  {
+    DevicePlan::RepeatLevel L = {(unsigned)sb.cherry_jobs.size(), 0, (unsigned)sb.level_pairs.size(), 0, 0, 0};
+    for (; at < nrp && lvl[order[at]] == l; ++at)
     {
-      // round by round, longest chains first within a round (their workgroups are dispatched first)
-      for (size_t c = 0; c < nch; ++c) order.push_back(c);
-      std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b)
+      const pll_operation_t & o = rq.ops[rq.rp->cherry_ops[order[at]]];
+      const Engine::Cherry & c = e->cherries[o.parent_clv_index];
+      CherryJob j;
+      memset(&j, 0, sizeof(j));
+      const unsigned child[2] = {o.child1_clv_index, o.child2_clv_index};
+      const unsigned matrix[2] = {o.child1_matrix_index, o.child2_matrix_index};
+      const int child_scaler[2] = {o.child1_scaler_index, o.child2_scaler_index};
+      for (int x = 0; x < 2; ++x)
       {
-        if (plan.launch[a] != plan.launch[b]) return plan.launch[a] < plan.launch[b];
-        return plan.chains[a].size() > plan.chains[b].size();
-      });
-    }
-    else
-    {
-      std::vector<std::pair<size_t, size_t>> stack;   // (chain, next feeder)
-      for (size_t root = 0; root < nch; ++root)
-      {
-        if (is_feeder[root]) continue;
-        stack.emplace_back(root, 0);
-        while (!stack.empty())
-        {
-          const size_t c = stack.back().first;
-          if (stack.back().second == 0)
-            std::stable_sort(feeders[c].begin(), feeders[c].end(), [&](size_t a, size_t b) { return weight[a] > weight[b]; });
-          if (stack.back().second < feeders[c].size()) { const size_t f = feeders[c][stack.back().second++]; stack.emplace_back(f, 0); }
-          else { order.push_back(c); stack.pop_back(); }
-        }
-      }
-    }
-    std::vector<PlanOp> pops(count);
-    std::vector<PlanChain> pchains;
-    unsigned nops = 0, lds_max = 0, nops_virtual = 0;
-    dp.algo_bytes = dp.algo_flops = dp.min_bytes = 0.0;
-    dp.launches.clear();
-    int cur_round = -1;
-    const unsigned extent = chains4 ? e->N : e->nblk;
-    const unsigned chain_flags = (chains20 ? s20_chain_lut_lds(e, lut_used) : chains16 ? s16_chain_lut_lds(e) : false) ? 1u : 0u;
-    for (size_t c : order)
-    {
-      const std::vector<unsigned> & ch = plan.chains[c];
-      if (dp.launches.empty() || (by_rounds && plan.launch[c] != cur_round))
-      {
-        if (!dp.launches.empty())
-        {
-          DevicePlan::Launch & done = dp.launches.back();
-          done.end = (unsigned)pchains.size();
-          done.ops = nops - done.ops;
-          done.bytes = dp.algo_bytes - done.bytes;
-          done.flops = dp.algo_flops - done.flops;
-          done.min_bytes = dp.min_bytes - done.min_bytes;
-        }
-        DevicePlan::Launch l;
-        l.rows = 1;
-        l.begin = (unsigned)pchains.size();
-        l.end = l.begin;
-        l.ops = nops;                     // running totals until the launch is closed
-        l.bytes = dp.algo_bytes;
-        l.flops = dp.algo_flops;
-        l.min_bytes = dp.min_bytes;
-        dp.launches.push_back(l);
-        cur_round = plan.launch[c];
-      }
-      PlanChain pc;
-      pc.first = nops;
-      pc.len = (unsigned)ch.size();
-      pc.extent = extent;
-      pc.lut_codes = e->lut_codes;
-      pc.lut_used = lut_used;
-      pc.flags = chain_flags;
-      pchains.push_back(pc);
-      unsigned off = 0;
-      for (size_t i = 0; i < ch.size(); ++i)
-      {
-        const pll_operation_t & o = ops[ch[i]];
-        PlanOp & po = pops[nops++];
-        memset(&po, 0, sizeof(po));
-        const double before = dp.algo_bytes;
-        fill_desc(e, o, po.d, dp.algo_bytes, dp.algo_flops);
-        po.carried = i ? plan.carried[ch[i]] : 0;
-        // an evaluate-only traversal: the vectors inside a chain are handed on in registers only
-        po.flags = (transient && i + 1 < ch.size()) ? 1u : 0u;
-        double wide_saved = (po.flags & 1u) ? (double)e->N * e->R * 8.0 * e->S : 0.0;
-        for (int x = 0; x < 2 && !wide.empty(); ++x)
-        {
-          if (!wide[2 * ch[i] + x]) continue;
-          const unsigned cidx = x ? o.child2_clv_index : o.child1_clv_index;
-          const unsigned midx = x ? o.child2_matrix_index : o.child1_matrix_index;
-          const Engine::Cherry & c = e->cherries[cidx];
-          PairLutJob job;
-          job.table = c.table;
-          job.pfrag = chains4 ? e->d_pmat + (size_t)midx * e->R * 16
-                    : chains16 ? e->d_pmat + (size_t)midx * e->R * e->S * e->Sp : e->d_pfrag + (size_t)midx * e->R * 400;
-          job.out = e->d_pairlut + pairlut_used;
-          job.nrows = c.nclasses;
-          pairlut_used += (size_t)e->R * c.nclasses * e->S;
-          pair_jobs.push_back(job);
-          // wide tip: no vector, no byte codes; pfrag = class codes, lut = its table, childN_index = table rows
-          // (... and its scaler counts per class)
-          // (bit 1 / 2 of the flags: few rows, staged in LDS by the chain kernels of the 20- and 2 .. 32-state families)
-          if (wide_slot(e, c.nclasses)) po.flags |= 2u << x;
-          if (x) { po.d.clv2 = nullptr; po.d.codes2 = nullptr; po.d.pfrag2 = reinterpret_cast<const double *>(c.pair); po.d.lut2 = job.out; po.d.child2_index = c.nclasses;
-                   if (po.d.scaler2) po.d.scaler2 = c.counts; }
-          else   { po.d.clv1 = nullptr; po.d.codes1 = nullptr; po.d.pfrag1 = reinterpret_cast<const double *>(c.pair); po.d.lut1 = job.out; po.d.child1_index = c.nclasses;
-                   if (po.d.scaler1) po.d.scaler1 = c.counts; }
-          wide_saved += (double)e->N * e->R * 8.0 * e->S - 4.0 * e->N;      // class codes instead of the vector
-        }
-        // the handed-over child stays in registers: neither its vector nor its scaler counts are read
-        dp.min_bytes += dp.algo_bytes - before - wide_saved;
-        if (po.carried)
-          dp.min_bytes -= (double)e->N * e->R * 8.0 * e->S +
-                          ((po.carried == 1 ? po.d.scaler1 : po.d.scaler2) ? 4.0 * (double)e->N * (e->rate_scalers ? e->R : 1) : 0.0);
-        const bool t1 = e->coded_tips && o.child1_clv_index < e->tips;
-        const bool t2 = e->coded_tips && o.child2_clv_index < e->tips;
-        if (chains20 || chains16)
-        {
-          const bool w1 = !wide.empty() && wide[2 * ch[i]], w2 = !wide.empty() && wide[2 * ch[i] + 1];
-          po.slot1 = off;
-          off += w1 ? wide_slot(e, e->cherries[o.child1_clv_index].nclasses) : chains20 ? s20_chain_slot(e, t1, lut_used) : s16_chain_slot(e, t1);
-          po.slot2 = off;
-          off += w2 ? wide_slot(e, e->cherries[o.child2_clv_index].nclasses) : chains20 ? s20_chain_slot(e, t2, lut_used) : s16_chain_slot(e, t2);
-        }
-      }
-      lds_max = std::max(lds_max, chains4 ? (unsigned)ch.size() : off);   // 4 states: the longest chain
-    }
-    // site repeats: the operations the schedule keeps per class (taken out of the list by the caller), by level
-    std::vector<CherryJob> cherry_jobs;
-    std::vector<PairLutJob> level_pairs;           // row tables of class children, by level of their parent
-    dp.repeat_levels.clear();
-    dp.repeat_classes = 0;
-    if (rp && rp->active)
-    {
-      const size_t lut_stride = (size_t)e->R * e->lut_codes * e->S;
-      const size_t nrp = rp->cherry_ops.size();
-      std::vector<int> node_level(e->nodes, -1);
-      std::vector<unsigned> lvl(nrp, 0), order(nrp);
-      unsigned max_level = 0;
-      for (size_t x = 0; x < nrp; ++x)
-      {
-        const pll_operation_t & o = all_ops[rp->cherry_ops[x]];
-        unsigned l = 0;
-        if (o.child1_clv_index >= e->tips) l = std::max(l, 1u + (unsigned)std::max(node_level[o.child1_clv_index], 0));
-        if (o.child2_clv_index >= e->tips) l = std::max(l, 1u + (unsigned)std::max(node_level[o.child2_clv_index], 0));
-        lvl[x] = l;
-        node_level[o.parent_clv_index] = (int)l;
-        max_level = std::max(max_level, l);
-        order[x] = (unsigned)x;
-      }
-      std::stable_sort(order.begin(), order.end(), [&](unsigned a, unsigned b) { return lvl[a] < lvl[b]; });
-      size_t at = 0;
-      for (unsigned l = 0; l <= max_level; ++l)
-      {
-        DevicePlan::RepeatLevel L = {(unsigned)cherry_jobs.size(), 0, (unsigned)level_pairs.size(), 0, 0, 0};
-        for (; at < nrp && lvl[order[at]] == l; ++at)
-        {
-          const pll_operation_t & o = all_ops[rp->cherry_ops[order[at]]];
-          const Engine::Cherry & c = e->cherries[o.parent_clv_index];
-          CherryJob j;
-          memset(&j, 0, sizeof(j));
-          const unsigned child[2] = {o.child1_clv_index, o.child2_clv_index};
-          const unsigned matrix[2] = {o.child1_matrix_index, o.child2_matrix_index};
-          const int child_scaler[2] = {o.child1_scaler_index, o.child2_scaler_index};
-          for (int x = 0; x < 2; ++x)
-          {
-            const double * rows;
-            unsigned nrows;
-            if (coded_tip(e, child[x])) { rows = e->d_lut + lut_stride * matrix[x]; nrows = e->lut_codes; }
-            else
-            {
-              const Engine::Cherry & cc = e->cherries[child[x]];
-              PairLutJob pj;
-              pj.table = cc.table;
-              pj.pfrag = chains4 ? e->d_pmat + (size_t)matrix[x] * e->R * 16
-                       : chains16 ? e->d_pmat + (size_t)matrix[x] * e->R * e->S * e->Sp : e->d_pfrag + (size_t)matrix[x] * e->R * 400;
-              pj.out = e->d_pairlut + pairlut_used;
-              pj.nrows = cc.nclasses;
-              pairlut_used += (size_t)e->R * cc.nclasses * e->S;
-              level_pairs.push_back(pj);
-              L.max_rows = std::max(L.max_rows, cc.nclasses);
-              rows = pj.out; nrows = cc.nclasses;
-            }
-            const unsigned * cnt = (child[x] >= e->tips && child_scaler[x] >= 0) ? e->cherries[child[x]].counts : nullptr;
-            if (x) { j.lut2 = rows; j.rows2 = nrows; j.cnt2 = cnt; }
-            else   { j.lut1 = rows; j.rows1 = nrows; j.cnt1 = cnt; }
-          }
-          j.rep = c.rep;
-          j.nclasses = c.nclasses;
-          j.table = c.table; j.flags = c.flags;
-          j.counts = o.parent_scaler_index >= 0 ? c.counts : nullptr;
-          cherry_jobs.push_back(j);
-          L.max_classes = std::max(L.max_classes, c.nclasses);
-          dp.repeat_classes += c.nclasses;
-          // what SURVEY.md 8d counts for the operation / what it moves now
-          OpDesc dummy;
-          double ab = 0.0;
-          fill_desc(e, o, dummy, ab, dp.algo_flops);
-          dp.algo_bytes += ab;
-          dp.min_bytes += 2.0 * e->N + 4.0 * e->N;            // (tip codes in once per topology; a class code per site for the consumer)
-          ++nops_virtual;
-        }
-        L.job_end = (unsigned)cherry_jobs.size();
-        L.pair_end = (unsigned)level_pairs.size();
-        dp.repeat_levels.push_back(L);
-      }
-    }
-    if (!cherry_jobs.empty() || !pair_jobs.empty())
-    {
-      // ... and the row tables of the wide tips, after the last level
-      DevicePlan::RepeatLevel L = {(unsigned)cherry_jobs.size(), (unsigned)cherry_jobs.size(), (unsigned)level_pairs.size(),
-                                   (unsigned)(level_pairs.size() + pair_jobs.size()), 0, 0};
-      for (const PairLutJob & pj : pair_jobs) L.max_rows = std::max(L.max_rows, pj.nrows);
-      dp.repeat_levels.push_back(L);
-      level_pairs.insert(level_pairs.end(), pair_jobs.begin(), pair_jobs.end());
-    }
-    pair_jobs.swap(level_pairs);
-    dp.ncherry_jobs = (unsigned)cherry_jobs.size();
-    dp.npair_jobs = (unsigned)pair_jobs.size();
-    dp.repeat_codes = rep_codes;
-    dp.off_cherry_jobs = pops.size() * sizeof(PlanOp) + pchains.size() * sizeof(PlanChain);
-    dp.off_pair_jobs = dp.off_cherry_jobs + cherry_jobs.size() * sizeof(CherryJob);
-    dp.bytes.resize(dp.off_pair_jobs + pair_jobs.size() * sizeof(PairLutJob));
-    memcpy(dp.bytes.data(), pops.data(), pops.size() * sizeof(PlanOp));
-    memcpy(dp.bytes.data() + pops.size() * sizeof(PlanOp), pchains.data(), pchains.size() * sizeof(PlanChain));
-    if (!cherry_jobs.empty()) memcpy(dp.bytes.data() + dp.off_cherry_jobs, cherry_jobs.data(), cherry_jobs.size() * sizeof(CherryJob));
-    if (!pair_jobs.empty()) memcpy(dp.bytes.data() + dp.off_pair_jobs, pair_jobs.data(), pair_jobs.size() * sizeof(PairLutJob));
-    if (!dp.launches.empty())
-    {
-      DevicePlan::Launch & done = dp.launches.back();
-      done.end = (unsigned)pchains.size();
-      done.ops = nops - done.ops;
-      done.bytes = dp.algo_bytes - done.bytes;
-      done.flops = dp.algo_flops - done.flops;
-      done.min_bytes = dp.min_bytes - done.min_bytes;
-    }
-    (void)nops_virtual;
-    // rounds of ONE chain each that follow one another (the spine towards the root) need no launch
-    // boundary between them: one workgroup row walks them in turn, exactly as in a one-launch traversal
-    if (by_rounds)
-    {
-      std::vector<DevicePlan::Launch> merged;
-      for (const DevicePlan::Launch & l : dp.launches)
-      {
-        if (!merged.empty() && l.end - l.begin == 1 && merged.back().rows == 1)
-        {
-          DevicePlan::Launch & m = merged.back();
-          m.end = l.end;
-          m.ops += l.ops;
-          m.bytes += l.bytes;
-          m.flops += l.flops;
-          m.min_bytes += l.min_bytes;
-        }
+        const double * rows;
+        unsigned nrows;
+        if (coded_tip(e, child[x])) { rows = e->d_lut + lut_stride * matrix[x]; nrows = e->lut_codes; }
         else
         {
-          merged.push_back(l);
-          merged.back().rows = l.end - l.begin;
+          const Engine::Cherry & cc = e->cherries[child[x]];
+          rows = push_pair_job(e, f, cc, matrix[x], sb, sb.level_pairs);
+          nrows = cc.nclasses;
+          L.max_rows = std::max(L.max_rows, cc.nclasses);
         }
+        const unsigned * cnt = (child[x] >= e->tips && child_scaler[x] >= 0) ? e->cherries[child[x]].counts : nullptr;
+        if (x) { j.lut2 = rows; j.rows2 = nrows; j.cnt2 = cnt; }
+        else   { j.lut1 = rows; j.rows1 = nrows; j.cnt1 = cnt; }
       }
-      dp.launches.swap(merged);
+      j.rep = c.rep;
+      j.nclasses = c.nclasses;
+      j.table = c.table; j.flags = c.flags;
+      j.counts = o.parent_scaler_index >= 0 ? c.counts : nullptr;
+      sb.cherry_jobs.push_back(j);
+      L.max_classes = std::max(L.max_classes, c.nclasses);
+      dp.repeat_classes += c.nclasses;
+      // what SURVEY.md 8d counts for the operation / what it moves now
+      OpDesc dummy;
+      double ab = 0.0;
+      fill_desc(e, o, dummy, ab, dp.algo_flops);
+      dp.algo_bytes += ab;
+      dp.min_bytes += 2.0 * e->N + 4.0 * e->N;            // (tip codes in once per topology; a class code per site for the consumer)
+    }
+    L.job_end = (unsigned)sb.cherry_jobs.size();
+    L.pair_end = (unsigned)sb.level_pairs.size();
+    dp.repeat_levels.push_back(L);
+  }
+}
+
+// DevicePlan::bytes: [PlanOp][PlanChain][CherryJob][PairLutJob]; the row tables of the wide tips of the chains go after
+// the last level of class operations
+static void pack_schedule(DevicePlan & dp, ScheduleBuild & sb, unsigned lut_used)
+{
+  if (!sb.cherry_jobs.empty() || !sb.pair_jobs.empty())
+  {
+    DevicePlan::RepeatLevel L = {(unsigned)sb.cherry_jobs.size(), (unsigned)sb.cherry_jobs.size(), (unsigned)sb.level_pairs.size(),
+                                 (unsigned)(sb.level_pairs.size() + sb.pair_jobs.size()), 0, 0};
+    for (const PairLutJob & pj : sb.pair_jobs) L.max_rows = std::max(L.max_rows, pj.nrows);
+    dp.repeat_levels.push_back(L);
+    sb.level_pairs.insert(sb.level_pairs.end(), sb.pair_jobs.begin(), sb.pair_jobs.end());
+  }
+  const std::vector<PairLutJob> & pairs = sb.level_pairs;
+  dp.ncherry_jobs = (unsigned)sb.cherry_jobs.size();
+  dp.npair_jobs = (unsigned)pairs.size();
+  dp.repeat_codes = lut_used;
+  dp.off_cherry_jobs = sb.pops.size() * sizeof(PlanOp) + sb.pchains.size() * sizeof(PlanChain);
+  dp.off_pair_jobs = dp.off_cherry_jobs + sb.cherry_jobs.size() * sizeof(CherryJob);
+  dp.bytes.resize(dp.off_pair_jobs + pairs.size() * sizeof(PairLutJob));
+  memcpy(dp.bytes.data(), sb.pops.data(), sb.pops.size() * sizeof(PlanOp));
+  memcpy(dp.bytes.data() + sb.pops.size() * sizeof(PlanOp), sb.pchains.data(), sb.pchains.size() * sizeof(PlanChain));
+  if (!sb.cherry_jobs.empty()) memcpy(dp.bytes.data() + dp.off_cherry_jobs, sb.cherry_jobs.data(), sb.cherry_jobs.size() * sizeof(CherryJob));
+  if (!pairs.empty()) memcpy(dp.bytes.data() + dp.off_pair_jobs, pairs.data(), pairs.size() * sizeof(PairLutJob));
+}
+
+// rounds of ONE chain each that follow one another (the spine towards the root) need no launch boundary between
+// them: one workgroup row walks them in turn, exactly as in a one-launch traversal
+static void merge_single_chain_rounds(DevicePlan & dp)
+{
+  std::vector<DevicePlan::Launch> merged;
+  for (const DevicePlan::Launch & l : dp.launches)
+  {
+    if (!merged.empty() && l.end - l.begin == 1 && merged.back().rows == 1)
+    {
+      DevicePlan::Launch & m = merged.back();
+      m.end = l.end;
+      m.ops += l.ops; m.bytes += l.bytes; m.flops += l.flops; m.min_bytes += l.min_bytes;
     }
     else
-      for (DevicePlan::Launch & l : dp.launches) l.rows = 1;
-    dp.nops = nops;
-    dp.nchains = (unsigned)pchains.size();
-    dp.lds_doubles = lds_max;
-    dp.max_extent = extent;
-    dp.generation = ++plan_generation;
-    dp.key.swap(key);
-    have = true;
+    {
+      merged.push_back(l);
+      merged.back().rows = l.end - l.begin;
+    }
   }
-  return have;
+  dp.launches.swap(merged);
+}
+
+static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainFamily & f, const ScheduleRequest & rq)
+{
+  const unsigned lut_used = std::max(1u, std::min(codes_in_use(e, p), e->lut_codes));
+  const pll_operation_t * ops = rq.rp ? rq.rp->ops.data() : rq.ops;
+  const unsigned count = rq.rp ? (unsigned)rq.rp->ops.size() : rq.count;
+  DevicePlan & dp = e->plan;
+  std::vector<unsigned char> wide;
+  unsigned nwide = 0;
+  if (!mark_wide_tips(e, ops, count, lut_used, wide, nwide)) return false;
+  std::vector<unsigned char> key = schedule_key(rq, lut_used, wide);
+  if (!dp.key.empty() && dp.key == key) return true;
+  if ((nwide || rq.rp) && !reserve_pair_tables(e, rq, ops, count, wide)) return false;
+  ChainPlan plan;
+  if (!plan_chains(e, &f, ops, count, f.chain_max, f.chain_lds, lut_used, plan, &wide)) return false;
+  ScheduleBuild sb;
+  sb.pops.resize(count);
+  emit_chains(e, f, ops, plan, chain_order(e, ops, count, plan, rq.mode == 0), wide, lut_used, rq, dp, sb);
+  emit_repeat_levels(e, f, rq, dp, sb);
+  pack_schedule(dp, sb, lut_used);
+  close_launch(dp, sb);                           // (the last launch also carries the class operations' bytes)
+  if (rq.mode == 0) merge_single_chain_rounds(dp);
+  else for (DevicePlan::Launch & l : dp.launches) l.rows = 1;
+  dp.nops = sb.nops;
+  dp.nchains = (unsigned)sb.pchains.size();
+  dp.lds_doubles = sb.lds_max;
+  dp.max_extent = f.extent(e);
+  dp.generation = ++plan_generation;
+  dp.key.swap(key);
+  return true;
 }
 
 // the class operations and row tables of a resident schedule (kernels_repeats.hpp), on the engine's stream; the
 // schedule's job arrays are on the device (upload_plan)
-static int launch_class_levels(Engine * e, const DevicePlan & dp)
+static int launch_class_levels(Engine * e, const ChainFamily & f, const DevicePlan & dp)
 {
-  const bool chains4 = e->family == KernelFamily::S4, chains16 = e->family == KernelFamily::S16;
   // level by level: the row tables of the class children of a level, then the tables of the level (with the
   // scaler counts per class); the last entry holds the row tables of the wide tips of the chains
   const CherryJob * cj = reinterpret_cast<const CherryJob *>(dp.d_buf + dp.off_cherry_jobs);
   const PairLutJob * pj = reinterpret_cast<const PairLutJob *>(dp.d_buf + dp.off_pair_jobs);
-  for (size_t lv = 0; lv < dp.repeat_levels.size(); ++lv)
+  for (const DevicePlan::RepeatLevel & L : dp.repeat_levels)
   {
-    const DevicePlan::RepeatLevel & L = dp.repeat_levels[lv];
     if (L.pair_end > L.pair_begin)
     {
-      const unsigned njobs = L.pair_end - L.pair_begin, npblk = (L.max_rows + S20_BS - 1) / S20_BS;
-      const PairLutJob * jobs = pj + L.pair_begin;
-      const dim3 gp((npblk + 3) / 4, njobs);
-      const size_t lds = sizeof(double) * e->R * S20_CFRAGS;
-      if (chains4) hipLaunchKernelGGL(k_pair_lut_s4, dim3((L.max_rows * e->R + 255) / 256, njobs), dim3(256), 0, e->stream, jobs, e->R);
-      else if (chains16)
-      {
-#define PLLHIP_CALL(KK) \
-        hipLaunchKernelGGL(k_pair_lut_s16<KK>, gp, dim3(256), sizeof(double) * e->R * s16_fr(KK), e->stream, jobs, e->R, e->S, e->Sp)
-        PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_CALL);
-#undef PLLHIP_CALL
-      }
-      else if (e->R == 4) hipLaunchKernelGGL(k_pair_lut<4>, gp, dim3(256), lds, e->stream, jobs);
-      else if (e->R == 2) hipLaunchKernelGGL(k_pair_lut<2>, gp, dim3(256), lds, e->stream, jobs);
-      else hipLaunchKernelGGL(k_pair_lut<1>, gp, dim3(256), lds, e->stream, jobs);
+      f.pair_lut(e, pj + L.pair_begin, L.pair_end - L.pair_begin, L.max_rows);
       PLLHIP_TRY(hipGetLastError());
     }
     if (L.job_end > L.job_begin)
     {
-      const unsigned njobs = L.job_end - L.job_begin, npblk = (L.max_classes + S20_BS - 1) / S20_BS;
-      const CherryJob * jobs = cj + L.job_begin;
-      const dim3 gb((npblk + 3) / 4, njobs);
-      if (chains4) hipLaunchKernelGGL(k_cherry_build_s4, dim3((L.max_classes + 255) / 256, njobs), dim3(256), 0, e->stream, jobs, e->R, dp.repeat_codes);
-      else if (chains16)
-      {
-#define PLLHIP_CALL(KK) \
-        hipLaunchKernelGGL(k_cherry_build_s16<KK>, gb, dim3(256), 0, e->stream, jobs, dp.repeat_codes, e->R, e->S)
-        PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_CALL);
-#undef PLLHIP_CALL
-      }
-      else if (e->R == 4) hipLaunchKernelGGL(k_cherry_build<4>, gb, dim3(256), 0, e->stream, jobs, dp.repeat_codes);
-      else if (e->R == 2) hipLaunchKernelGGL(k_cherry_build<2>, gb, dim3(256), 0, e->stream, jobs, dp.repeat_codes);
-      else hipLaunchKernelGGL(k_cherry_build<1>, gb, dim3(256), 0, e->stream, jobs, dp.repeat_codes);
+      f.class_build(e, cj + L.job_begin, L.job_end - L.job_begin, L.max_classes, dp.repeat_codes);
       PLLHIP_TRY(hipGetLastError());
     }
   }
@@ -2103,9 +2198,47 @@ static int validate_ops(const Engine * e, const pll_operation_t * ops, unsigned 
   return PLL_SUCCESS;
 }
 
-static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops, unsigned count)
+// profiling (pllhip_profile_*) and counting of one launch of the partials path: `launch` runs between the two events
+// of a pair when profiling is on; bytes / flops / min_bytes / nops: what the launch stands for
+template <class Launch>
+static int counted_launch(Engine * e, double bytes, double flops, unsigned nops, double min_bytes, Launch && launch)
 {
-  Engine * e = engine_of(p);
+  hipEvent_t ev1 = nullptr;
+  if (e->profiling)
+  {
+    if (e->prof_used == e->prof_events.size())
+    {
+      hipEvent_t x, y;
+      PLLHIP_TRY(hipEventCreate(&x));
+      PLLHIP_TRY(hipEventCreate(&y));
+      e->prof_events.emplace_back(x, y);
+    }
+    ev1 = e->prof_events[e->prof_used].second;
+    PLLHIP_TRY(hipEventRecord(e->prof_events[e->prof_used++].first, e->stream));
+  }
+  if (!launch()) return PLL_FAILURE;
+  if (e->profiling)
+  {
+    PLLHIP_TRY(hipEventRecord(ev1, e->stream));
+    e->prof_bytes += bytes;
+    e->prof_min_bytes += min_bytes;
+    e->prof_flops += flops;
+    e->prof_ops += nops;
+  }
+  e->counters.partial_launches++;
+  return PLL_SUCCESS;
+}
+
+static void count_list(Engine * e, unsigned count)
+{
+  e->counters.partial_ops += count;
+  e->counters.site_updates += (unsigned long long)count * e->N * e->R;
+}
+
+// what comes before any schedule of a list: index checks, vectors of evaluate-only traversals, P-matrices and lookup
+// tables, and the class nodes the list overwrites
+static int begin_list(Engine * e, pll_partition_t * p, const pll_operation_t * ops, unsigned count)
+{
   PLLHIP_TRY(hipSetDevice(e->device));
   if (!validate_ops(e, ops, count)) return PLL_FAILURE;
   // (before the queued P-matrices are launched: vectors that were not stored and that this list overwrites are given
@@ -2116,37 +2249,329 @@ static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops
     for (unsigned k = 0; k < count; ++k)
       if (ops[k].parent_clv_index < e->tips) e->tip_has_codes[ops[k].parent_clv_index] = 0;    // (a tip vector is overwritten)
   if ((!e->transient_busy && !flush_pmatrices(p)) || !ensure_luts(p)) return PLL_FAILURE;
-
-  // dependency levels: an op runs after the producers of its children and
-  // after every earlier op that touched its output buffers
-  std::vector<int> clv_level(e->nodes, -1), sc_level(e->nscalers, -1), level(count, 0);
-  int max_level = 0;
-  if (!e->cherries.empty())
+  if (e->cherries.empty()) return PLL_SUCCESS;
+  // every vector this list writes stops being the cherry it may have been; one that the list reads first
+  // (and that exists per class only) is expanded before it goes
+  // ... and the same for scale buffers whose counts exist per class only
+  std::vector<char> read(e->nodes, 0), sread(e->nscalers, 0);
+  for (unsigned k = 0; k < count; ++k)
   {
-    // every vector this list writes stops being the cherry it may have been; one that the list reads first
-    // (and that exists per class only) is expanded before it goes
-    // ... and the same for scale buffers whose counts exist per class only
-    std::vector<char> read(e->nodes, 0), sread(e->nscalers, 0);
-    for (unsigned k = 0; k < count; ++k)
+    read[ops[k].child1_clv_index] = read[ops[k].child2_clv_index] = 1;
+    if (ops[k].child1_scaler_index >= 0) sread[ops[k].child1_scaler_index] = 1;
+    if (ops[k].child2_scaler_index >= 0) sread[ops[k].child2_scaler_index] = 1;
+    Engine::Cherry & c = e->cherries[ops[k].parent_clv_index];
+    if (c.valid && read[ops[k].parent_clv_index] && !need_clv(e, ops[k].parent_clv_index)) return PLL_FAILURE;
+    // the node stops being a class node: counts it stands for under a buffer this operation does not rewrite
+    // are written out while its table still describes them
+    if (c.valid && c.scaler_index >= 0 && e->scaler_lazy[c.scaler_index] == (int)ops[k].parent_clv_index &&
+        c.scaler_index != ops[k].parent_scaler_index && !need_scaler(e, c.scaler_index)) return PLL_FAILURE;
+    c.valid = false;
+    const int sp = ops[k].parent_scaler_index;
+    if (sp >= 0 && e->scaler_lazy[sp] >= 0)
     {
-      read[ops[k].child1_clv_index] = read[ops[k].child2_clv_index] = 1;
-      if (ops[k].child1_scaler_index >= 0) sread[ops[k].child1_scaler_index] = 1;
-      if (ops[k].child2_scaler_index >= 0) sread[ops[k].child2_scaler_index] = 1;
-      Engine::Cherry & c = e->cherries[ops[k].parent_clv_index];
-      if (c.valid && read[ops[k].parent_clv_index] && !need_clv(e, ops[k].parent_clv_index)) return PLL_FAILURE;
-      // the node stops being a class node: counts it stands for under a buffer this operation does not rewrite
-      // are written out while its table still describes them
-      if (c.valid && c.scaler_index >= 0 && e->scaler_lazy[c.scaler_index] == (int)ops[k].parent_clv_index &&
-          c.scaler_index != ops[k].parent_scaler_index && !need_scaler(e, c.scaler_index)) return PLL_FAILURE;
-      c.valid = false;
-      const int sp = ops[k].parent_scaler_index;
-      if (sp >= 0 && e->scaler_lazy[sp] >= 0)
-      {
-        if (sread[sp] && !need_scaler(e, sp)) return PLL_FAILURE;
-        e->scaler_lazy[sp] = -1;
-      }
+      if (sread[sp] && !need_scaler(e, sp)) return PLL_FAILURE;
+      e->scaler_lazy[sp] = -1;
     }
   }
+  return PLL_SUCCESS;
+}
+
+// the paths that read child scaler counts per site (everything but the resident schedules, whose wide tips read
+// them per class): counts that exist per class only are written out first
+static int plain_scalers(Engine * e, const pll_operation_t * ops, unsigned count)
+{
+  if (e->scaler_lazy.empty()) return PLL_SUCCESS;
+  for (unsigned k = 0; k < count; ++k)
+    if (!need_scaler(e, ops[k].child1_scaler_index) || !need_scaler(e, ops[k].child2_scaler_index)) return PLL_FAILURE;
+  return PLL_SUCCESS;
+}
+
+// Device-resident schedules serve two forms: the whole traversal in one launch (1), or (lists of six operations and
+// more) one launch per round with the chains of the round as grid rows (0); -1: neither.  In one launch a workgroup
+// walks ALL chains one after the other and no launch boundary is paid; by rounds the chains run side by side (which
+// is what a partition needs that does not fill the chip with its site blocks) and the workgroups of a round are
+// shared out dynamically (which wins again on very large partitions).  Measured per traversal, rounds / one launch:
+//   20 states, 200 taxa:  32 k sites 1.55 / 2.14 ms, 64 k 2.64 / 2.59, 125 k 4.83 / 4.66,
+//                         250 k 8.66 / 8.93, 500 k 16.4 / 17.2, 1 M 32.4 / 33.0
+//    4 states, 100 taxa:  100 k 0.52 / 0.58, 250 k 1.08 / 1.18, 500 k 1.94 / 1.99, 1 M 3.64 / 3.52
+//   16 states,  50 taxa:  8 k 0.23 / 0.38, 32 k 0.36 / 0.44, 128 k 1.03 / 0.94, 500 k 3.22 / 3.17
+//    2 states,  50 taxa:  1 M 2.20 / 2.74
+// A repeated list is neither planned nor copied again (2.5 us of host time per launch), its kernels read their
+// descriptors from device memory, a round is never split at 24 operations and rounds of single operations stay on
+// the chain kernel: 72 -> 21 us and 212 -> 23 us per full-traversal call of a 2 000-site partition at 4 / 20 states
+// against the by-value form (run_chains_by_value).  Short lists (the 1 - 3 operations of an SPR insertion) keep their
+// descriptors in the kernel arguments: a schedule would have to be copied to the device first (W3 at C2 size: 165
+// against 178 us per iteration) -- except in a family without the by-value form.
+static int resident_mode(const Engine * e, const ChainFamily & f, unsigned count)
+{
+  // PLLHIP_TRAVERSE=1 / 0: whole traversals always / never in one launch (default: by size; never when several
+  // partitions share the device, each on its own stream: long-lived workgroups with a fixed share of the sites
+  // interleave worse than rounds -- two DNA + two protein partitions: 7.7 against 7.1 ms).
+  static const int env_traverse = getenv("PLLHIP_TRAVERSE") ? atoi(getenv("PLLHIP_TRAVERSE")) : -1;
+  const bool use_traverse = env_traverse >= 0 ? env_traverse != 0
+                          : (engines_on_device[e->device & 63].load() <= 1 && f.fills_chip(e) && (count >= 6 || !f.chains));
+  return use_traverse ? 1 : count >= 6 ? 0 : -1;
+}
+
+// site repeats: the cherries of the list that an operation of the list consumes are kept per class
+// (kernels_repeats.hpp) and leave the list (rp.ops); their consumers read them as wide tips
+static int select_class_ops(Engine * e, const pll_operation_t * ops, unsigned count, unsigned lut_used, RepeatPlan & rp)
+{
+  if (!e->site_repeats || lut_used > 64) return PLL_SUCCESS;
+  // an operation is kept per class if an operation of the list consumes it and both children are known per
+  // class: coded tips, class operations earlier in the list, or class nodes of earlier calls whose tables
+  // still are their vectors
+  std::vector<int> consumer(e->nodes, -1);
+  std::vector<char> now(e->nodes, 0);
+  for (unsigned k = 0; k < count; ++k) { consumer[ops[k].child1_clv_index] = (int)k; consumer[ops[k].child2_clv_index] = (int)k; }
+  for (unsigned k = 0; k < count; ++k)
+  {
+    const pll_operation_t & o = ops[k];
+    const unsigned child[2] = {o.child1_clv_index, o.child2_clv_index};
+    const int child_scaler[2] = {o.child1_scaler_index, o.child2_scaler_index};
+    bool ok = consumer[o.parent_clv_index] > (int)k && child[0] != child[1];
+    for (int x = 0; x < 2 && ok; ++x)
+    {
+      if (coded_tip(e, child[x])) ok = child_scaler[x] == PLL_SCALE_BUFFER_NONE;
+      else
+      {
+        const Engine::Cherry & cc = e->cherries[child[x]];
+        ok = (now[child[x]] || cc.valid) && cc.map_valid && cc.trackable && class_codes_match(e, child[x], lut_used) &&
+             child_scaler[x] == cc.scaler_index;          // (its counts per class are the ones asked for)
+      }
+    }
+    if (ok)
+    {
+      bool failed = false;
+      ok = class_map(e, o.parent_clv_index, child[0], child[1], lut_used, failed);
+      if (failed) return PLL_FAILURE;
+    }
+    if (ok)
+    {
+      Engine::Cherry & c = e->cherries[o.parent_clv_index];
+      if (!cherry_storage(e, o.parent_clv_index, c.nclasses)) return PLL_FAILURE;
+      c.valid = true;
+      c.materialized = false;
+      c.scaler_index = o.parent_scaler_index;
+      now[o.parent_clv_index] = 1;
+      rp.cherry_ops.push_back(k);
+    }
+    else rp.ops.push_back(o);
+  }
+  if (!rp.cherry_ops.empty() && !rp.ops.empty())
+  {
+    rp.active = true;
+    rp.ncodes = lut_used;
+  }
+  else
+    for (unsigned k : rp.cherry_ops) e->cherries[ops[k].parent_clv_index].valid = false;
+  return PLL_SUCCESS;
+}
+
+// the launches of resident schedule `dp` on e's stream (wgs: workgroups per CU and row, 0: the launcher's choice)
+static int launch_resident(Engine * e, const ChainFamily & f, const DevicePlan & dp, const PlanView & view, unsigned wgs,
+                           bool wide, bool transient)
+{
+  for (const DevicePlan::Launch & l : dp.launches)
+    if (!counted_launch(e, l.bytes, l.flops, l.ops, l.min_bytes, [&]()
+        { return f.traverse(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, l.rows, wgs, wide, transient); }))
+      return PLL_FAILURE;
+  return PLL_SUCCESS;
+}
+
+// the list through the resident schedule prepare_schedule made for it: class operations and row tables, then the
+// chains
+static int run_resident(Engine * e, const ChainFamily & f, const pll_operation_t * ops, unsigned count, const RepeatPlan & rp,
+                        bool transient)
+{
+  DevicePlan & dp = e->plan;
+  PlanView view;
+  if (!upload_plan(dp, e->stream, view)) return PLL_FAILURE;
+  if (dp.ncherry_jobs || dp.npair_jobs)
+  {
+    if (!launch_class_levels(e, f, dp)) return PLL_FAILURE;
+    // the scale buffers of the class operations hold their counts per class from now on (need_scaler)
+    if (rp.active)
+      for (unsigned k : rp.cherry_ops)
+        if (ops[k].parent_scaler_index >= 0) e->scaler_lazy[ops[k].parent_scaler_index] = (int)ops[k].parent_clv_index;
+    e->repeat_stats.cherries += dp.ncherry_jobs;
+    e->repeat_stats.classes += dp.repeat_classes;
+    e->repeat_stats.sites += (unsigned long long)dp.ncherry_jobs * e->N;
+  }
+  if (!launch_resident(e, f, dp, view, 0, !e->cherries.empty(), transient)) return PLL_FAILURE;
+  if (transient) transient_after_list(e, ops, count, dp);
+  count_list(e, count);
+  return PLL_SUCCESS;
+}
+
+// the chains by value (ChainBatch, in the kernel arguments): one launch per round, longest chains first (their
+// workgroups are dispatched first, which keeps the tail of the launch short)
+static int run_chains_by_value(Engine * e, const ChainFamily & f, const pll_operation_t * ops, unsigned count,
+                               unsigned lut_used, const ChainPlan & plan)
+{
+  for (int round = 0; round < plan.rounds; ++round)
+  {
+    ChainBatch cb;
+    unsigned nops = 0, nchains = 0, longest = 0, lds = 0;
+    double bytes = 0.0, flops = 0.0, minb = 0.0;
+    auto flush = [&]() -> int
+    {
+      if (!nchains) return PLL_SUCCESS;
+      if (!counted_launch(e, bytes, flops, nops, bytes - minb, [&]() -> int
+          {
+            if (longest > 1) return f.chains(e, cb, nchains, lds, lut_used);
+            OpBatch ob;                       // nothing to hand over: the plain kernel
+            for (unsigned i = 0; i < nops; ++i) ob.op[i] = cb.op[i];
+            return launch_partials(e, ob, nops);
+          }))
+        return PLL_FAILURE;
+      nops = nchains = longest = lds = 0;
+      bytes = flops = minb = 0.0;
+      return PLL_SUCCESS;
+    };
+    std::vector<size_t> order;
+    for (size_t c = 0; c < plan.chains.size(); ++c)
+      if (plan.launch[c] == round) order.push_back(c);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](size_t a, size_t b) { return plan.chains[a].size() > plan.chains[b].size(); });
+    for (size_t c : order)
+    {
+      const std::vector<unsigned> & ch = plan.chains[c];
+      if (nops + ch.size() > MAX_OPS_PER_LAUNCH && !flush()) return PLL_FAILURE;
+      cb.first[nchains] = (unsigned char)nops;
+      cb.len[nchains] = (unsigned char)ch.size();
+      unsigned off = 0;
+      for (size_t i = 0; i < ch.size(); ++i)
+      {
+        const pll_operation_t & o = ops[ch[i]];
+        if (!need_clv(e, o.child1_clv_index) || !need_clv(e, o.child2_clv_index)) return PLL_FAILURE;
+        fill_desc(e, o, cb.op[nops], bytes, flops);
+        cb.carried[nops] = i ? plan.carried[ch[i]] : 0;
+        if (cb.carried[nops])       // handed over in registers: not read
+          minb += (double)e->N * e->R * 8.0 * e->S +
+                  ((cb.carried[nops] == 1 ? cb.op[nops].scaler1 : cb.op[nops].scaler2) ? 4.0 * (double)e->N * (e->rate_scalers ? e->R : 1) : 0.0);
+        cb.slot1[nops] = (unsigned short)off;
+        off += child_table_lds(e, f, o.child1_clv_index, lut_used, false);
+        cb.slot2[nops] = (unsigned short)off;
+        off += child_table_lds(e, f, o.child2_clv_index, lut_used, false);
+        ++nops;
+      }
+      lds = std::max(lds, f.lds_is_length ? (unsigned)ch.size() : off);
+      ++nchains;
+      longest = std::max<unsigned>(longest, (unsigned)ch.size());
+    }
+    if (!flush()) return PLL_FAILURE;
+  }
+  count_list(e, count);
+  return PLL_SUCCESS;
+}
+
+struct LevelPlan
+{
+  std::vector<int> level;                        // per op (-1: folded into its consumer)
+  int max_level = 0;
+  std::vector<char> light;                       // per op: runs behind the matrix-bound operations of its launch
+  std::vector<int> cherry_of;                    // consumer -> the cherry folded into it
+  std::vector<const uint8_t *> cherry_table;     // per folded cherry with a scale buffer: its scaling per pair of tip codes
+  bool folding = false;
+};
+
+// 61 states.  (1) Cherries -- tip x tip operations, bound by HBM writes while the matrix cores
+// idle -- are folded into the operation that consumes them (kernels_s61.hpp, k_partials_s61v4).
+// (2) Those that stay (their consumer already folds its other child) run as LATE as the consumer
+// allows, so that they share a launch with matrix-bound operations.  Both only for lists with the
+// shape of a tree traversal (plan_chains' test); PLLHIP_S61_CHERRIES=0 / PLLHIP_S61_ALAP=0 switch
+// them off.
+static int fold_s61_cherries(Engine * e, const pll_operation_t * ops, unsigned count, LevelPlan & lp)
+{
+  static const int use_alap = getenv("PLLHIP_S61_ALAP") ? atoi(getenv("PLLHIP_S61_ALAP")) : 1;
+  ChainPlan shape;
+  if (!plan_chains(e, nullptr, ops, count, 1, ~0u, 1u, shape)) return PLL_SUCCESS;
+  std::vector<int> producer(e->nodes, -1), consumer(count, -1), prod1(count, -1), prod2(count, -1);
+  for (unsigned k = 0; k < count; ++k)
+  {
+    prod1[k] = producer[ops[k].child1_clv_index];
+    prod2[k] = producer[ops[k].child2_clv_index];
+    if (prod1[k] >= 0) consumer[prod1[k]] = (int)k;
+    if (prod2[k] >= 0) consumer[prod2[k]] = (int)k;
+    producer[ops[k].parent_clv_index] = (int)k;
+  }
+  auto is_cherry = [&](unsigned k) { return tip_coded(e, ops[k].child1_clv_index) && tip_coded(e, ops[k].child2_clv_index); };
+  std::vector<char> folded(count, 0);
+  if (s61_cherries_supported(e))
+  {
+    for (unsigned k = 0; k < count; ++k)
+      if (is_cherry(k) && consumer[k] >= 0 && lp.cherry_of[consumer[k]] < 0)
+      {
+        lp.cherry_of[consumer[k]] = (int)k;
+        folded[k] = 1;
+        lp.folding = true;
+      }
+  }
+  if (lp.folding)
+  {
+    // levels from the remaining dependencies alone (the list is a tree traversal: every vector
+    // is written once and read by one later operation)
+    lp.max_level = 0;
+    for (unsigned k = 0; k < count; ++k)
+    {
+      if (folded[k]) { lp.level[k] = -1; continue; }
+      int l = 0;
+      if (prod1[k] >= 0 && !folded[prod1[k]]) l = std::max(l, lp.level[prod1[k]] + 1);
+      if (prod2[k] >= 0 && !folded[prod2[k]]) l = std::max(l, lp.level[prod2[k]] + 1);
+      lp.level[k] = l;
+      lp.max_level = std::max(lp.max_level, l);
+    }
+    // scaling decision of every folded cherry per pair of tip codes
+    std::vector<unsigned> need;
+    for (unsigned k = 0; k < count; ++k)
+      if (folded[k] && ops[k].parent_scaler_index != PLL_SCALE_BUFFER_NONE) need.push_back(k);
+    const size_t tab = (size_t)e->lut_codes * e->lut_codes;
+    const size_t lut_stride = (size_t)e->R * e->lut_codes * e->S;
+    if (need.size() * tab > e->s61_ttscale_cap)
+    {
+      PLLHIP_TRY(hipStreamSynchronize(e->stream));
+      (void)hipFree(e->d_s61_ttscale);
+      e->d_s61_ttscale = nullptr;
+      e->s61_ttscale_cap = 0;
+      if (!dev_alloc(&e->d_s61_ttscale, 2 * need.size() * tab, "cherry scaling tables")) return PLL_FAILURE;
+      e->s61_ttscale_cap = 2 * need.size() * tab;
+    }
+    for (size_t i0 = 0; i0 < need.size(); i0 += 32)
+    {
+      CherryScaleBatch cs;
+      memset(&cs, 0, sizeof(cs));
+      const unsigned nc = (unsigned)std::min<size_t>(32, need.size() - i0);
+      for (unsigned i = 0; i < nc; ++i)
+      {
+        const pll_operation_t & o = ops[need[i0 + i]];
+        cs.lut1[i] = e->d_lut + lut_stride * o.child1_matrix_index;
+        cs.lut2[i] = e->d_lut + lut_stride * o.child2_matrix_index;
+        cs.out[i] = e->d_s61_ttscale + (i0 + i) * tab;
+        lp.cherry_table[need[i0 + i]] = cs.out[i];
+      }
+      if (!launch_cherry_scale_s61(e, cs, nc)) return PLL_FAILURE;
+    }
+  }
+  if (use_alap)
+    for (unsigned k = 0; k < count; ++k)
+    {
+      if (folded[k] || !is_cherry(k)) continue;
+      if (consumer[k] >= 0 && lp.level[consumer[k]] - 1 > lp.level[k]) lp.level[k] = lp.level[consumer[k]] - 1;
+      lp.light[k] = 1;
+    }
+  return PLL_SUCCESS;
+}
+
+// dependency levels: an op runs after the producers of its children and after every earlier op that touched its
+// output buffers (61 states: then fold_s61_cherries)
+static int plan_levels(Engine * e, const pll_operation_t * ops, unsigned count, LevelPlan & lp)
+{
+  std::vector<int> clv_level(e->nodes, -1), sc_level(e->nscalers, -1);
+  lp.level.assign(count, 0);
+  lp.light.assign(count, 0);
+  lp.cherry_of.assign(count, -1);
+  lp.cherry_table.assign(count, nullptr);
   for (unsigned k = 0; k < count; ++k)
   {
     const pll_operation_t & op = ops[k];
@@ -2161,7 +2586,7 @@ static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops
     // later op that touches it again runs in a later launch.  In a tree
     // traversal a CLV is touched by its producer and its single consumer only,
     // so this costs no parallelism and covers RAW, WAR and WAW alike.
-    level[k] = l;
+    lp.level[k] = l;
     clv_level[op.parent_clv_index] = l;
     clv_level[op.child1_clv_index] = std::max(clv_level[op.child1_clv_index], l);
     clv_level[op.child2_clv_index] = std::max(clv_level[op.child2_clv_index], l);
@@ -2170,380 +2595,38 @@ static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops
       sc_level[op.child1_scaler_index] = std::max(sc_level[op.child1_scaler_index], l);
     if (op.child2_scaler_index >= 0)
       sc_level[op.child2_scaler_index] = std::max(sc_level[op.child2_scaler_index], l);
-    max_level = std::max(max_level, l);
+    lp.max_level = std::max(lp.max_level, l);
   }
+  if (e->family == KernelFamily::S61 && lut_active(e) && count >= 2) return fold_s61_cherries(e, ops, count, lp);
+  return PLL_SUCCESS;
+}
 
-  auto prof_begin = [&](hipEvent_t & ev1) -> int
-  {
-    ev1 = nullptr;
-    if (!e->profiling) return PLL_SUCCESS;
-    if (e->prof_used == e->prof_events.size())
-    {
-      hipEvent_t x, y;
-      PLLHIP_TRY(hipEventCreate(&x));
-      PLLHIP_TRY(hipEventCreate(&y));
-      e->prof_events.emplace_back(x, y);
-    }
-    hipEvent_t ev0 = e->prof_events[e->prof_used].first;
-    ev1 = e->prof_events[e->prof_used].second;
-    e->prof_used++;
-    PLLHIP_TRY(hipEventRecord(ev0, e->stream));
-    return PLL_SUCCESS;
-  };
-  auto prof_end = [&](hipEvent_t ev1, double bytes, double flops, unsigned nops, double min_bytes = -1.0) -> int
-  {
-    if (!e->profiling) return PLL_SUCCESS;
-    PLLHIP_TRY(hipEventRecord(ev1, e->stream));
-    e->prof_bytes += bytes;
-    e->prof_min_bytes += (min_bytes >= 0.0) ? min_bytes : bytes;
-    e->prof_flops += flops;
-    e->prof_ops += nops;
-    return PLL_SUCCESS;
-  };
-
-  // the paths that read child scaler counts per site (everything but the resident schedules, whose wide tips read
-  // them per class): counts that exist per class only are written out first
-  auto plain_scalers = [&]() -> int
-  {
-    if (e->scaler_lazy.empty()) return PLL_SUCCESS;
-    for (unsigned k = 0; k < count; ++k)
-      if (!need_scaler(e, ops[k].child1_scaler_index) || !need_scaler(e, ops[k].child2_scaler_index)) return PLL_FAILURE;
-    return PLL_SUCCESS;
-  };
-
-  // chain schedule (4- and 20-state families, four rates): one launch per round of chains,
-  // the vector of a link stays in registers.  PLLHIP_CHAINS=0 keeps the plain level schedule.
-  static const int use_chains = getenv("PLLHIP_CHAINS") ? atoi(getenv("PLLHIP_CHAINS")) : 1;
-  const bool chains20 = e->family == KernelFamily::S20 && chains_supported_s20(e);
-  const bool chains4 = e->family == KernelFamily::S4 && chains_supported_s4(e);
-  // 2..16 states: chains exist in the one-launch form only
-  const bool chains16 = e->family == KernelFamily::S16 && chains_supported_s16(e);
-  if (use_chains && count >= 2 && (chains20 || chains4 || chains16))
-  {
-    ChainPlan plan;
-    // tip tables are staged with the codes in use (at least one: an untouched partition)
-    const unsigned lut_used = std::max(1u, std::min(codes_in_use(e, p), e->lut_codes));
-    // PLLHIP_TRAVERSE=1 / 0: whole traversals always / never in one launch (default: by size, below; never
-    // when several partitions share the device, each on its own stream: long-lived workgroups with a fixed
-    // share of the sites interleave worse than rounds -- two DNA + two protein partitions: 7.7 against 7.1 ms).
-    static const int env_traverse = getenv("PLLHIP_TRAVERSE") ? atoi(getenv("PLLHIP_TRAVERSE")) : -1;
-    // One launch for the whole traversal, or one launch per round with the chains of the round as grid
-    // rows (both from the device-resident schedule)?  In one launch a workgroup walks ALL chains one
-    // after the other and no launch boundary is paid; by rounds the chains run side by side (which is
-    // what a partition needs that does not fill the chip with its site blocks) and the workgroups of
-    // a round are shared out dynamically (which wins again on very large partitions).  Measured per
-    // traversal, rounds / one launch:
-    //   20 states, 200 taxa:  32 k sites 1.55 / 2.14 ms, 64 k 2.64 / 2.59, 125 k 4.83 / 4.66,
-    //                         250 k 8.66 / 8.93, 500 k 16.4 / 17.2, 1 M 32.4 / 33.0
-    //    4 states, 100 taxa:  100 k 0.52 / 0.58, 250 k 1.08 / 1.18, 500 k 1.94 / 1.99, 1 M 3.64 / 3.52
-    //   16 states,  50 taxa:  8 k 0.23 / 0.38, 32 k 0.36 / 0.44, 128 k 1.03 / 0.94, 500 k 3.22 / 3.17
-    //    2 states,  50 taxa:  1 M 2.20 / 2.74
-    const bool fills_chip = chains4 ? (e->N + 63) / 64 >= 48u * e->cu_count
-                          : chains16 ? (e->nblk >= 12u * e->cu_count && e->nblk < 48u * e->cu_count && e->S > 8)
-                                     : (e->nblk >= 6u * e->cu_count && e->nblk < 24u * e->cu_count);
-    const bool use_traverse = env_traverse >= 0 ? env_traverse != 0
-                            : (engines_on_device[e->device & 63].load() <= 1 && fills_chip && (count >= 6 || chains16));
-    const unsigned chain_max = chains20 ? S20_CHAIN_MAX : chains16 ? S16_CHAIN_MAX : S4_CHAIN_MAX;
-    const unsigned chain_lds = chains20 ? S20_CHAIN_LDS : chains16 ? S16_CHAIN_LDS : ~0u;
-    // Device-resident schedules serve both forms: the whole traversal in one launch, or (lists of six
-    // operations and more) one launch per round with the chains of the round as grid rows.  A repeated
-    // list is neither planned nor copied again (2.5 us of host time per launch), its kernels read their
-    // descriptors from device memory, a round is never split at 24 operations and rounds of single
-    // operations stay on the chain kernel: 72 -> 21 us and 212 -> 23 us per full-traversal call of a
-    // 2 000-site partition at 4 / 20 states against the by-value form below.
-    // Short lists (the 1 - 3 operations of an SPR insertion) keep their descriptors in the kernel
-    // arguments: a schedule would have to be copied to the device first (W3 at C2 size: 165 against
-    // 178 us per iteration).
-    const bool by_rounds = !use_traverse && count >= 6;
-    if (use_traverse || by_rounds)
-    {
-      const unsigned mode = use_traverse ? 1u : 0u;
-      DevicePlan & dp = e->plan;
-      // site repeats: the cherries of the list that an operation of the list consumes are kept per class
-      // (kernels_repeats.hpp) and leave the list; their consumers read them as wide tips
-      RepeatPlan rp;
-      if (e->site_repeats && (chains20 || chains4 || chains16) && lut_used <= 64)
-      {
-        // an operation is kept per class if an operation of the list consumes it and both children are known per
-        // class: coded tips, class operations earlier in the list, or class nodes of earlier calls whose tables
-        // still are their vectors
-        std::vector<int> consumer(e->nodes, -1);
-        std::vector<char> now(e->nodes, 0);
-        for (unsigned k = 0; k < count; ++k) { consumer[ops[k].child1_clv_index] = (int)k; consumer[ops[k].child2_clv_index] = (int)k; }
-        for (unsigned k = 0; k < count; ++k)
-        {
-          const pll_operation_t & o = ops[k];
-          const unsigned child[2] = {o.child1_clv_index, o.child2_clv_index};
-          const int child_scaler[2] = {o.child1_scaler_index, o.child2_scaler_index};
-          bool ok = consumer[o.parent_clv_index] > (int)k && child[0] != child[1];
-          for (int x = 0; x < 2 && ok; ++x)
-          {
-            if (coded_tip(e, child[x])) ok = child_scaler[x] == PLL_SCALE_BUFFER_NONE;
-            else
-            {
-              const Engine::Cherry & cc = e->cherries[child[x]];
-              ok = (now[child[x]] || cc.valid) && cc.map_valid && cc.trackable && class_codes_match(e, child[x], lut_used) &&
-                   child_scaler[x] == cc.scaler_index;          // (its counts per class are the ones asked for)
-            }
-          }
-          if (ok)
-          {
-            bool failed = false;
-            ok = class_map(e, o.parent_clv_index, child[0], child[1], lut_used, failed);
-            if (failed) return PLL_FAILURE;
-          }
-          if (ok)
-          {
-            Engine::Cherry & c = e->cherries[o.parent_clv_index];
-            if (!cherry_storage(e, o.parent_clv_index, c.nclasses)) return PLL_FAILURE;
-            c.valid = true;
-            c.materialized = false;
-            c.scaler_index = o.parent_scaler_index;
-            now[o.parent_clv_index] = 1;
-            rp.cherry_ops.push_back(k);
-          }
-          else rp.ops.push_back(o);
-        }
-        if (!rp.cherry_ops.empty() && !rp.ops.empty())
-        {
-          rp.active = true;
-          rp.ncodes = lut_used;
-        }
-        else
-          for (unsigned k : rp.cherry_ops) e->cherries[ops[k].parent_clv_index].valid = false;
-      }
-      // (evaluate-only traversals: not together with site repeats, whose class operations leave the list)
-      const bool transient = e->transient_mode && !e->site_repeats;
-      const bool have = rp.active ? prepare_schedule(e, p, rp.ops.data(), (unsigned)rp.ops.size(), mode, &rp, ops, count)
-                                  : prepare_schedule(e, p, ops, count, mode, nullptr, nullptr, 0, transient);
-      if (!have && rp.active)
-        for (unsigned k : rp.cherry_ops) e->cherries[ops[k].parent_clv_index].valid = false;     // the plain paths below compute them
-      if (have)
-      {
-        PlanView view;
-        if (!upload_plan(e->plan, e->stream, view)) return PLL_FAILURE;
-        if (dp.ncherry_jobs || dp.npair_jobs)
-        {
-          if (!launch_class_levels(e, dp)) return PLL_FAILURE;
-          // the scale buffers of the class operations hold their counts per class from now on (need_scaler)
-          if (rp.active)
-            for (unsigned k : rp.cherry_ops)
-              if (ops[k].parent_scaler_index >= 0) e->scaler_lazy[ops[k].parent_scaler_index] = (int)ops[k].parent_clv_index;
-          e->repeat_stats.cherries += dp.ncherry_jobs;
-          e->repeat_stats.classes += dp.repeat_classes;
-          e->repeat_stats.sites += (unsigned long long)dp.ncherry_jobs * e->N;
-        }
-        for (const DevicePlan::Launch & l : dp.launches)
-        {
-          const unsigned rows = l.rows;
-          hipEvent_t ev1;
-          if (!prof_begin(ev1)) return PLL_FAILURE;
-          if (chains20 ? !launch_traverse_s20(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, rows, 0, !e->cherries.empty(), transient)
-                       : chains16 ? !launch_traverse_s16(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, rows, 0, !e->cherries.empty())
-                                  : !launch_traverse_s4(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, rows, 0, transient, !e->cherries.empty()))
-            return PLL_FAILURE;
-          if (!prof_end(ev1, l.bytes, l.flops, l.ops, l.min_bytes)) return PLL_FAILURE;
-          e->counters.partial_launches++;
-        }
-        if (transient) transient_after_list(e, ops, count, dp);
-        e->counters.partial_ops += count;
-        e->counters.site_updates += (unsigned long long)count * e->N * e->R;
-        return PLL_SUCCESS;
-      }
-      plan = ChainPlan();
-    }
-    if (!plain_scalers()) return PLL_FAILURE;
-    if (!chains16 && plan_chains(e, ops, count, chain_max, chain_lds, lut_used, plan))
-    {
-      for (int round = 0; round < plan.rounds; ++round)
-      {
-        ChainBatch cb;
-        unsigned nops = 0, nchains = 0, longest = 0, lds_max = 0;
-        double bytes = 0.0, flops = 0.0, minb = 0.0;
-        auto flush = [&]() -> int
-        {
-          if (!nchains) return PLL_SUCCESS;
-          hipEvent_t ev1;
-          if (!prof_begin(ev1)) return PLL_FAILURE;
-          if (longest == 1)
-          {
-            OpBatch ob;                       // nothing to hand over: the plain kernel
-            for (unsigned i = 0; i < nops; ++i) ob.op[i] = cb.op[i];
-            if (!launch_partials(e, ob, nops)) return PLL_FAILURE;
-          }
-          else if (chains20 ? !launch_chains_s20(e, cb, nchains, lds_max, lut_used)
-                            : !launch_chains_s4(e, cb, nchains, longest))
-            return PLL_FAILURE;
-          if (!prof_end(ev1, bytes, flops, nops, bytes - minb)) return PLL_FAILURE;
-          e->counters.partial_launches++;
-          nops = nchains = longest = lds_max = 0;
-          bytes = flops = minb = 0.0;
-          return PLL_SUCCESS;
-        };
-        // longest chains first: their workgroups are dispatched first, which keeps the tail
-        // of the launch short
-        std::vector<size_t> order;
-        for (size_t c = 0; c < plan.chains.size(); ++c)
-          if (plan.launch[c] == round) order.push_back(c);
-        std::stable_sort(order.begin(), order.end(),
-                         [&](size_t a, size_t b) { return plan.chains[a].size() > plan.chains[b].size(); });
-        for (size_t c : order)
-        {
-          const std::vector<unsigned> & ch = plan.chains[c];
-          if (nops + ch.size() > MAX_OPS_PER_LAUNCH && !flush()) return PLL_FAILURE;
-          cb.first[nchains] = (unsigned char)nops;
-          cb.len[nchains] = (unsigned char)ch.size();
-          unsigned off = 0;
-          for (size_t i = 0; i < ch.size(); ++i)
-          {
-            const pll_operation_t & o = ops[ch[i]];
-            if (!need_clv(e, o.child1_clv_index) || !need_clv(e, o.child2_clv_index)) return PLL_FAILURE;
-            fill_desc(e, o, cb.op[nops], bytes, flops);
-            cb.carried[nops] = i ? plan.carried[ch[i]] : 0;
-            if (cb.carried[nops])       // handed over in registers: not read
-              minb += (double)e->N * e->R * 8.0 * e->S +
-                      ((cb.carried[nops] == 1 ? cb.op[nops].scaler1 : cb.op[nops].scaler2) ? 4.0 * (double)e->N * (e->rate_scalers ? e->R : 1) : 0.0);
-            if (chains20)
-            {
-              const bool t1 = e->coded_tips && o.child1_clv_index < e->tips;
-              const bool t2 = e->coded_tips && o.child2_clv_index < e->tips;
-              cb.slot1[nops] = (unsigned short)off;
-              off += s20_chain_slot(e, t1, lut_used);
-              cb.slot2[nops] = (unsigned short)off;
-              off += s20_chain_slot(e, t2, lut_used);
-            }
-            else cb.slot1[nops] = cb.slot2[nops] = 0;
-            ++nops;
-          }
-          lds_max = std::max(lds_max, off);
-          ++nchains;
-          longest = std::max<unsigned>(longest, (unsigned)ch.size());
-        }
-        if (!flush()) return PLL_FAILURE;
-      }
-      e->counters.partial_ops += count;
-      e->counters.site_updates += (unsigned long long)count * e->N * e->R;
-      return PLL_SUCCESS;
-    }
-  }
-
-  if (!plain_scalers()) return PLL_FAILURE;
-
-  // 61 states.  (1) Cherries -- tip x tip operations, bound by HBM writes while the matrix cores
-  // idle -- are folded into the operation that consumes them (kernels_s61.hpp, k_partials_s61v4).
-  // (2) Those that stay (their consumer already folds its other child) run as LATE as the consumer
-  // allows, so that they share a launch with matrix-bound operations.  Both only for lists with the
-  // shape of a tree traversal (plan_chains' test); PLLHIP_S61_CHERRIES=0 / PLLHIP_S61_ALAP=0 switch
-  // them off.
-  static const int use_alap = getenv("PLLHIP_S61_ALAP") ? atoi(getenv("PLLHIP_S61_ALAP")) : 1;
-  std::vector<char> light(count, 0);
-  std::vector<int> cherry_of(count, -1);          // consumer -> the cherry folded into it
-  std::vector<const uint8_t *> cherry_table(count, nullptr);
-  bool folding = false;
-  if (e->family == KernelFamily::S61 && lut_active(e) && count >= 2)
-  {
-    ChainPlan shape;
-    if (plan_chains(e, ops, count, 1, ~0u, 1u, shape))
-    {
-      std::vector<int> producer(e->nodes, -1), consumer(count, -1), prod1(count, -1), prod2(count, -1);
-      for (unsigned k = 0; k < count; ++k)
-      {
-        prod1[k] = producer[ops[k].child1_clv_index];
-        prod2[k] = producer[ops[k].child2_clv_index];
-        if (prod1[k] >= 0) consumer[prod1[k]] = (int)k;
-        if (prod2[k] >= 0) consumer[prod2[k]] = (int)k;
-        producer[ops[k].parent_clv_index] = (int)k;
-      }
-      auto is_cherry = [&](unsigned k) { return tip_coded(e, ops[k].child1_clv_index) && tip_coded(e, ops[k].child2_clv_index); };
-      std::vector<char> folded(count, 0);
-      if (s61_cherries_supported(e))
-      {
-        for (unsigned k = 0; k < count; ++k)
-          if (is_cherry(k) && consumer[k] >= 0 && cherry_of[consumer[k]] < 0)
-          {
-            cherry_of[consumer[k]] = (int)k;
-            folded[k] = 1;
-            folding = true;
-          }
-      }
-      if (folding)
-      {
-        // levels from the remaining dependencies alone (the list is a tree traversal: every vector
-        // is written once and read by one later operation)
-        max_level = 0;
-        for (unsigned k = 0; k < count; ++k)
-        {
-          if (folded[k]) { level[k] = -1; continue; }
-          int l = 0;
-          if (prod1[k] >= 0 && !folded[prod1[k]]) l = std::max(l, level[prod1[k]] + 1);
-          if (prod2[k] >= 0 && !folded[prod2[k]]) l = std::max(l, level[prod2[k]] + 1);
-          level[k] = l;
-          max_level = std::max(max_level, l);
-        }
-        // scaling decision of every folded cherry per pair of tip codes
-        std::vector<unsigned> need;
-        for (unsigned k = 0; k < count; ++k)
-          if (folded[k] && ops[k].parent_scaler_index != PLL_SCALE_BUFFER_NONE) need.push_back(k);
-        const size_t tab = (size_t)e->lut_codes * e->lut_codes;
-        const size_t lut_stride = (size_t)e->R * e->lut_codes * e->S;
-        if (need.size() * tab > e->s61_ttscale_cap)
-        {
-          PLLHIP_TRY(hipStreamSynchronize(e->stream));
-          (void)hipFree(e->d_s61_ttscale);
-          e->d_s61_ttscale = nullptr;
-          e->s61_ttscale_cap = 0;
-          if (!dev_alloc(&e->d_s61_ttscale, 2 * need.size() * tab, "cherry scaling tables")) return PLL_FAILURE;
-          e->s61_ttscale_cap = 2 * need.size() * tab;
-        }
-        for (size_t i0 = 0; i0 < need.size(); i0 += 32)
-        {
-          CherryScaleBatch cs;
-          memset(&cs, 0, sizeof(cs));
-          const unsigned nc = (unsigned)std::min<size_t>(32, need.size() - i0);
-          for (unsigned i = 0; i < nc; ++i)
-          {
-            const pll_operation_t & o = ops[need[i0 + i]];
-            cs.lut1[i] = e->d_lut + lut_stride * o.child1_matrix_index;
-            cs.lut2[i] = e->d_lut + lut_stride * o.child2_matrix_index;
-            cs.out[i] = e->d_s61_ttscale + (i0 + i) * tab;
-            cherry_table[need[i0 + i]] = cs.out[i];
-          }
-          if (!launch_cherry_scale_s61(e, cs, nc)) return PLL_FAILURE;
-        }
-      }
-      if (use_alap)
-        for (unsigned k = 0; k < count; ++k)
-        {
-          if (folded[k] || !is_cherry(k)) continue;
-          if (consumer[k] >= 0 && level[consumer[k]] - 1 > level[k]) level[k] = level[consumer[k]] - 1;
-          light[k] = 1;
-        }
-    }
-  }
-
-  for (int l = 0; l <= max_level; ++l)
+// one launch per level, at most MAX_OPS_PER_LAUNCH operations (S61_V4_OPS when cherries are folded) each
+static int run_levels(Engine * e, const pll_operation_t * ops, unsigned count, const LevelPlan & lp)
+{
+  for (int l = 0; l <= lp.max_level; ++l)
   {
     OpBatch batch, cherries;
     const uint8_t * tables[MAX_OPS_PER_LAUNCH];
     unsigned nb = 0, nfolded = 0;
     bool any_cherry = false;
     double batch_bytes = 0.0, batch_flops = 0.0;
-    const unsigned cap = folding ? S61_V4_OPS : MAX_OPS_PER_LAUNCH;
+    const unsigned cap = lp.folding ? S61_V4_OPS : MAX_OPS_PER_LAUNCH;
     // matrix-bound operations first, the light ones behind them (their workgroups fill the tail)
     for (unsigned pass = 0; pass < 2; ++pass)
     for (unsigned k = 0; k <= count; ++k)
     {
-      if (k < count && (light[k] != (char)pass)) continue;
+      if (k < count && (lp.light[k] != (char)pass)) continue;
       if (k == count && pass == 0) continue;
-      if (k < count && level[k] == l)
+      if (k < count && lp.level[k] == l)
       {
         pll_operation_t o = ops[k];
         if (!need_clv(e, o.child1_clv_index) || !need_clv(e, o.child2_clv_index)) return PLL_FAILURE;
         memset(&cherries.op[nb], 0, sizeof(OpDesc));
         tables[nb] = nullptr;
-        if (cherry_of[k] >= 0)
+        if (lp.cherry_of[k] >= 0)
         {
-          const pll_operation_t & c = ops[cherry_of[k]];
+          const pll_operation_t & c = ops[lp.cherry_of[k]];
           if (o.child2_clv_index == c.parent_clv_index)      // the folded cherry is child 1 (products commute)
           {
             std::swap(o.child1_clv_index, o.child2_clv_index);
@@ -2551,7 +2634,7 @@ static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops
             std::swap(o.child1_scaler_index, o.child2_scaler_index);
           }
           fill_desc(e, c, cherries.op[nb], batch_bytes, batch_flops);
-          tables[nb] = cherry_table[cherry_of[k]];
+          tables[nb] = lp.cherry_table[lp.cherry_of[k]];
           any_cherry = true;
           ++nfolded;
         }
@@ -2559,15 +2642,15 @@ static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops
       }
       if (nb == cap || (k == count && nb))
       {
-        hipEvent_t ev1;
-        if (!prof_begin(ev1)) return PLL_FAILURE;
         // (with cherries folded somewhere in the traversal, every launch takes the 512-thread kernel: 0.5 - 3 % faster
         // than switching to the 256-thread one for launches without a cherry)
         static const int all_v4 = getenv("PLLHIP_S61_ALLV4") ? atoi(getenv("PLLHIP_S61_ALLV4")) : 1;
-        if ((any_cherry || (all_v4 && folding)) ? !launch_partials_s61_cherries(e, batch, cherries, tables, nb) : !launch_partials(e, batch, nb))
+        if (!counted_launch(e, batch_bytes, batch_flops, nb + nfolded, batch_bytes, [&]()
+            {
+              return (any_cherry || (all_v4 && lp.folding)) ? launch_partials_s61_cherries(e, batch, cherries, tables, nb)
+                                                            : launch_partials(e, batch, nb);
+            }))
           return PLL_FAILURE;
-        if (!prof_end(ev1, batch_bytes, batch_flops, nb + nfolded)) return PLL_FAILURE;
-        e->counters.partial_launches++;
         nb = nfolded = 0;
         any_cherry = false;
         batch_bytes = 0.0;
@@ -2575,11 +2658,38 @@ static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops
       }
     }
   }
-  e->counters.partial_ops += count;
-  e->counters.site_updates += (unsigned long long)count * e->N * e->R;
+  count_list(e, count);
   return PLL_SUCCESS;
 }
 
+static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops, unsigned count)
+{
+  Engine * e = engine_of(p);
+  if (!begin_list(e, p, ops, count)) return PLL_FAILURE;
+  // chain schedules (ChainFamily): the vector of a link stays in registers
+  const ChainFamily * f = count >= 2 ? chain_family(e) : nullptr;
+  // (tip tables are staged with the codes in use: at least one, an untouched partition)
+  const unsigned lut_used = f ? std::max(1u, std::min(codes_in_use(e, p), e->lut_codes)) : 0u;
+  const int mode = f ? resident_mode(e, *f, count) : -1;
+  if (mode >= 0)
+  {
+    RepeatPlan rp;
+    if (!select_class_ops(e, ops, count, lut_used, rp)) return PLL_FAILURE;
+    // (evaluate-only traversals: not together with site repeats, whose class operations leave the list)
+    const bool transient = e->transient_mode && !e->site_repeats;
+    if (prepare_schedule(e, p, *f, {ops, count, (unsigned)mode, transient, rp.active ? &rp : nullptr}))
+      return run_resident(e, *f, ops, count, rp, transient);
+    if (rp.active)
+      for (unsigned k : rp.cherry_ops) e->cherries[ops[k].parent_clv_index].valid = false;     // the plain paths below compute them
+  }
+  if (!plain_scalers(e, ops, count)) return PLL_FAILURE;
+  ChainPlan plan;
+  if (f && f->chains && plan_chains(e, f, ops, count, f->chain_max, f->chain_lds, lut_used, plan))
+    return run_chains_by_value(e, *f, ops, count, lut_used, plan);
+  LevelPlan lp;
+  if (!plan_levels(e, ops, count, lp)) return PLL_FAILURE;
+  return run_levels(e, ops, count, lp);
+}
 } // namespace pllhip
 
 
@@ -2598,12 +2708,9 @@ namespace pllhip {
 // ---------------------------------------------------------------------------
 static bool batch_family(const Engine * e)
 {
-  static const int use_chains = getenv("PLLHIP_CHAINS") ? atoi(getenv("PLLHIP_CHAINS")) : 1;
   static const int use_batch = getenv("PLLHIP_BATCH") ? atoi(getenv("PLLHIP_BATCH")) : 1;
-  if (!use_chains || !use_batch || !e->shards.empty() || e->site_repeats) return false;
-  return (e->family == KernelFamily::S20 && chains_supported_s20(e)) ||
-         (e->family == KernelFamily::S4 && chains_supported_s4(e)) ||
-         (e->family == KernelFamily::S16 && chains_supported_s16(e));
+  if (!use_batch || !e->shards.empty() || e->site_repeats) return false;
+  return chain_family(e) != nullptr;
 }
 
 static bool batch_compatible(const Engine * a, const Engine * b)
@@ -2628,6 +2735,7 @@ static void batch_free(BatchPlan * b)
 static int update_partials_group(const std::vector<pll_partition_t *> & g, const pll_operation_t * ops, unsigned count)
 {
   Engine * lead = engine_of(g[0]);
+  const ChainFamily & f = *chain_family(lead);       // (the members': batch_family, batch_compatible)
   const size_t M = g.size();
   if (hipSetDevice(lead->device) != hipSuccess) { set_error(PLL_ERROR_HIP_RUNTIME, "hipSetDevice"); return -1; }
   // One launch for the whole list (every member gets grid rows of its own, whose workgroups walk ALL chains
@@ -2636,11 +2744,7 @@ static int update_partials_group(const std::vector<pll_partition_t *> & g, const
   // site blocks in the group to fill the chip without the parallelism of the chains.  PLLHIP_BATCH_MODE=1 / 0.
   static const int env_mode = getenv("PLLHIP_BATCH_MODE") ? atoi(getenv("PLLHIP_BATCH_MODE")) : -1;
   unsigned long long units = 0;       // workgroups the members could use side by side
-  for (pll_partition_t * p : g)
-  {
-    const Engine * e = engine_of(p);
-    units += e->family == KernelFamily::S4 ? (e->N + 255u) / 256u : (e->nblk + 7u) / 8u;
-  }
+  for (pll_partition_t * p : g) units += f.units(engine_of(p));
   const unsigned mode = env_mode >= 0 ? (env_mode ? 1u : 0u) : (units >= 2ull * lead->cu_count && count >= 2) ? 1u : 0u;
   for (pll_partition_t * p : g)
   {
@@ -2651,7 +2755,7 @@ static int update_partials_group(const std::vector<pll_partition_t *> & g, const
     // parents; the vectors this list writes stop being whatever class node they were)
     if (!e->cherries.empty())
       for (unsigned k = 0; k < count; ++k) e->cherries[ops[k].parent_clv_index].valid = false;
-    if (!prepare_schedule(e, p, ops, count, mode, nullptr, nullptr, 0, e->transient_mode && !e->site_repeats)) return 0;
+    if (!prepare_schedule(e, p, f, {ops, count, mode, e->transient_mode && !e->site_repeats, nullptr})) return 0;
   }
   // launches can be shared when every member's schedule has the same shape (same list, same family: always,
   // unless the tables of one member fill the LDS earlier and cut its chains elsewhere)
@@ -2751,7 +2855,7 @@ static int update_partials_group(const std::vector<pll_partition_t *> & g, const
     any_wide = any_wide || !e->cherries.empty();
     if (!e->plan.npair_jobs) continue;
     PlanView own;
-    if (hipSetDevice(e->device) != hipSuccess || !upload_plan(e->plan, e->stream, own) || !launch_class_levels(e, e->plan)) return -1;
+    if (hipSetDevice(e->device) != hipSuccess || !upload_plan(e->plan, e->stream, own) || !launch_class_levels(e, f, e->plan)) return -1;
   }
   // the members' streams have issued what the traversal reads (P-matrices, tables, tip data)
   for (size_t m = 1; m < M; ++m)
@@ -2760,41 +2864,13 @@ static int update_partials_group(const std::vector<pll_partition_t *> & g, const
       return -1;
   PlanView view;
   if (!upload_plan(b.plan, lead->stream, view)) return -1;
-  for (const DevicePlan::Launch & l : b.plan.launches)
-  {
-    hipEvent_t ev1 = nullptr;
-    if (lead->profiling)
-    {
-      if (lead->prof_used == lead->prof_events.size())
-      {
-        hipEvent_t x, y;
-        if (!hip_ok(hipEventCreate(&x), "hipEventCreate") || !hip_ok(hipEventCreate(&y), "hipEventCreate")) return -1;
-        lead->prof_events.emplace_back(x, y);
-      }
-      ev1 = lead->prof_events[lead->prof_used].second;
-      if (!hip_ok(hipEventRecord(lead->prof_events[lead->prof_used].first, lead->stream), "hipEventRecord")) return -1;
-      lead->prof_used++;
-    }
-    // one launch for the whole list: the rows are the members, every workgroup has the same long walk in front
-    // of it, so exactly the workgroups that are resident at once (one per CU; three at 4 states)
-    static const int env_walk = getenv("PLLHIP_BATCH_WGS") ? atoi(getenv("PLLHIP_BATCH_WGS")) : 0;
-    const unsigned wgs = mode ? (env_walk > 0 ? (unsigned)env_walk : lead->family == KernelFamily::S4 ? 3u : 1u) : 0u;
-    bool any_transient = false;
-    for (pll_partition_t * p : g) any_transient = any_transient || (engine_of(p)->transient_mode && !engine_of(p)->site_repeats);
-    const int ok = lead->family == KernelFamily::S20 ? launch_traverse_s20(lead, view, b.plan.lds_doubles, b.plan.max_extent, l.begin, l.end, l.rows, wgs, any_wide, any_transient)
-                 : lead->family == KernelFamily::S16 ? launch_traverse_s16(lead, view, b.plan.lds_doubles, b.plan.max_extent, l.begin, l.end, l.rows, wgs, any_wide)
-                                                     : launch_traverse_s4(lead, view, b.plan.lds_doubles, b.plan.max_extent, l.begin, l.end, l.rows, wgs, any_transient, any_wide);
-    if (!ok) return -1;
-    if (lead->profiling)
-    {
-      if (!hip_ok(hipEventRecord(ev1, lead->stream), "hipEventRecord")) return -1;
-      lead->prof_bytes += l.bytes;
-      lead->prof_min_bytes += l.min_bytes;
-      lead->prof_flops += l.flops;
-      lead->prof_ops += l.ops;
-    }
-    lead->counters.partial_launches++;
-  }
+  // one launch for the whole list: the rows are the members, every workgroup has the same long walk in front
+  // of it, so exactly the workgroups that are resident at once (ChainFamily::batch_wgs per CU)
+  static const int env_walk = getenv("PLLHIP_BATCH_WGS") ? atoi(getenv("PLLHIP_BATCH_WGS")) : 0;
+  const unsigned wgs = mode ? (env_walk > 0 ? (unsigned)env_walk : f.batch_wgs) : 0u;
+  bool any_transient = false;
+  for (pll_partition_t * p : g) any_transient = any_transient || (engine_of(p)->transient_mode && !engine_of(p)->site_repeats);
+  if (!launch_resident(lead, f, b.plan, view, wgs, any_wide, any_transient)) return -1;
   // whatever a member's stream does next comes after the traversal
   if (!hip_ok(hipEventRecord(b.done, lead->stream), "hipEventRecord")) return -1;
   for (size_t m = 1; m < M; ++m)
@@ -2803,8 +2879,7 @@ static int update_partials_group(const std::vector<pll_partition_t *> & g, const
   {
     Engine * e = engine_of(p);
     if (e->transient_mode && !e->site_repeats) transient_after_list(e, ops, count, e->plan);
-    e->counters.partial_ops += count;
-    e->counters.site_updates += (unsigned long long)count * e->N * e->R;
+    count_list(e, count);
   }
   return 1;
 }
