@@ -171,6 +171,21 @@ typedef struct pllhip_repeat_stats
 PLL_EXPORT int pllhip_repeat_stats(const pll_partition_t * partition, pllhip_repeat_stats_t * out);
 PLL_EXPORT int pllhip_profile_read(pll_partition_t * partition, pllhip_profile_t * out);
 
+/* What the scheduler made of the last operation list that went through a resident schedule (operation chains in
+   device memory; all zero when the partition has none).  An operation chain hands its vector on in registers; the
+   vector next to it comes back from memory -- except a lone cherry (a tip x tip operation), which the 20-state
+   family builds in registers inside the chain that reads it, from the two tip tables ("folded"; per-site scalers,
+   coded tips, no site repeats; PLLHIP_FOLD=0 in the environment plans without folds).  A folded cherry's vector and
+   scaler counts are stored like any other's. */
+typedef struct pllhip_schedule_stats
+{
+  unsigned int chains;                 /* operation chains of the schedule */
+  unsigned int operations;             /* operations in them, folded cherries included */
+  unsigned int inner_reads;            /* inner vectors that the chains read from memory */
+  unsigned int folded_cherries;        /* cherries built in registers by the operation that reads them */
+} pllhip_schedule_stats_t;
+PLL_EXPORT int pllhip_schedule_stats(const pll_partition_t * partition, pllhip_schedule_stats_t * out);
+
 /* Evaluate-only traversals.  The model-parameter optimisers of pll-modules evaluate the whole tree after every
    parameter poke (src/algorithm/algo_callback.c:338, 465, 568, 678: pllmod_treeinfo_compute_loglh(treeinfo, 0);
    src/optimize/opt_algorithms.c:734-773: nmax + 1 of them per L-BFGS-B iteration): every vector is recomputed by

@@ -101,11 +101,16 @@ struct PlanOp
   unsigned slot1, slot2; // 20 states: LDS offsets (doubles) of the two children's tables
   unsigned flags;        // bit 0: the parent vector is not stored (an evaluate-only traversal hands it to the next
                          // operation of its chain in registers; pllhip_set_transient)
+                         // bit 1 / 2: the rows of wide tip 1 / 2 are staged in LDS
+                         // bit 3: a cherry that the NEXT entry builds in registers instead of reading its vector
+                         // (20 states; slot1 / slot2 = its tip tables, the scaling decisions per code pair behind them)
+                         // bit 4: child 2 of this entry is the folded cherry in front of it
 };
 // operations [first, first + len) of PlanOp[], and what the kernels need to know about the partition
 // the chain belongs to (a batched schedule -- pllhip_update_partials_batch -- holds chains of several
 // partitions): extent = site blocks (blocked families) or sites (4-state family), the row count of its
-// tip lookup tables in memory, the rows staged in LDS, flags (bit 0: tip tables are staged in LDS)
+// tip lookup tables in memory, the rows staged in LDS, flags (bit 0: tip tables are staged in LDS; bit 1: the chain
+// holds folded cherries)
 struct PlanChain { unsigned first, len, extent, lut_codes, lut_used, flags; };
 // A schedule of a few operations (the single-operation updates of a branch-length pass or of an SPR insertion) travels
 // in the kernel arguments instead of being copied to the device first: inline_ops != 0 = bytes of the PlanOp array at the
@@ -131,6 +136,8 @@ struct DevicePlan                                 // the schedule resident on th
   std::vector<unsigned char> key;                 // operation list + settings it was built from
   std::vector<unsigned char> bytes;               // serialised [PlanOp ...][PlanChain ...]
   unsigned nops = 0, nchains = 0, lds_doubles = 0;
+  unsigned nfolds = 0;                            // lone cherries folded into the chains that read them (PlanOp::flags bit 3)
+  unsigned inner_reads = 0;                       // inner vectors that the chains read from memory
   double algo_bytes = 0.0, algo_flops = 0.0;      // algorithmic traffic / work of the traversal
   double min_bytes = 0.0;                         // traffic without the child vectors handed over in registers
   // launches of the schedule: one for a whole traversal, or one per round of chains (chains

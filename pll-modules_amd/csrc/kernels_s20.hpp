@@ -465,6 +465,65 @@ __device__ inline void s20_child_inner_c(const double * unit, const double * cfr
   s20_child_regs_c(b, cfrag_r, lane, t);
 }
 
+// LDS doubles of a tip table staged with the codes in use (s20_chain_slot on the host)
+__host__ __device__ inline unsigned s20_tip_slot(unsigned R, unsigned lut_used)
+{
+  return (R * lut_used * S20_LUT_RS + 7u) & ~7u;
+}
+
+// LDS doubles of the scaling decisions of a folded cherry: one bit per pair of tip codes
+__host__ __device__ inline unsigned s20_fold_bits_lds(unsigned lut_used)
+{
+  return ((lut_used * lut_used + 63u) / 64u + 7u) & ~7u;
+}
+
+// Folded cherries: whether a site of the cherry is scaled depends on its pair of tip codes alone, so the vote over all
+// rates and states is taken once per pair, on the two staged tables: bit a * lut_used + b is set when every product
+// tableA[r][a][s] * tableB[r][b][s] is below the threshold -- the products and the comparison of the vote in
+// s20_chain_op.  A wave writes whole 64-bit words (one ballot each); the workgroup's barrier follows.
+template <unsigned RT>
+__device__ inline void s20_fold_bits(const double * ta, const double * tb, unsigned long long * bits, unsigned lut_used)
+{
+  const unsigned npairs = lut_used * lut_used, lane = threadIdx.x & 63;
+  for (unsigned base = threadIdx.x & ~63u; base < npairs; base += blockDim.x)
+  {
+    const unsigned p = base + lane;
+    int small = 0;
+    if (p < npairs)
+    {
+      const unsigned a = p / lut_used, b = p - a * lut_used;
+      small = 1;
+      for (unsigned r = 0; r < RT; ++r)
+      {
+        const double * ra = ta + (r * lut_used + a) * S20_LUT_RS, * rb = tb + (r * lut_used + b) * S20_LUT_RS;
+#pragma unroll
+        for (unsigned s = 0; s < 20; ++s) small &= (ra[s] * rb[s] < SCALE_THRESHOLD);
+      }
+    }
+    const unsigned long long m = __ballot(small);
+    if (lane == 0) bits[base >> 6] = m;
+  }
+}
+
+// the block of a folded cherry for one rate, in the B layout (= the D layout its own operation would store):
+// b = tableA[code a] * tableB[code b], times its scale factor
+__device__ inline void s20_fold_block(const double * ta_r, const double * tb_r, unsigned codes, unsigned small, unsigned q,
+                                      double2 b[5])
+{
+  const double * ae = ta_r + (codes & 255u) * S20_LUT_RS, * ao = ta_r + ((codes >> 8) & 255u) * S20_LUT_RS;
+  const double * be = tb_r + ((codes >> 16) & 255u) * S20_LUT_RS, * bo = tb_r + (codes >> 24) * S20_LUT_RS;
+  const double fe = (small & 1u) ? SCALE_FACTOR : 1.0, fo = (small & 2u) ? SCALE_FACTOR : 1.0;
+#pragma unroll
+  for (unsigned k = 0; k < 5; ++k)
+  {
+    const unsigned i = s20_row(k, q);
+    b[k].x = ae[i] * be[i];
+    b[k].y = ao[i] * bo[i];
+    b[k].x *= fe;
+    b[k].y *= fo;
+  }
+}
+
 __device__ inline const unsigned * s20_wide_codes(const double * clv, const uint8_t * codes, const double * pfrag)
 {
   return (!clv && !codes) ? reinterpret_cast<const unsigned *>(pfrag) : nullptr;
@@ -479,17 +538,56 @@ __device__ inline const unsigned * s20_wide_codes(const double * clv, const uint
 // pointers and branches (the attribute-off kernel is the round-2 one: 13 instead of 19 spilled registers).
 // store: false = the result is handed to the next operation of the chain in registers only (an evaluate-only
 // traversal, PlanOp::flags bit 0); its scaler counts are written either way.
-template <unsigned RT, bool RS, bool WIDE>
+// FOLD: child 2 may be a cherry (tip x tip operation) built in registers (`fold`; the scheduler puts a folded cherry
+// on that side: products commute).  fentry is the cherry's own entry of the schedule (its tip codes, the LDS offsets
+// from `lds` of its two tip tables with the scaling decisions per pair of codes behind them: s20_fold_bits; bit 0 of
+// its flags counts with ftrans).  The cherry's vector and scaler buffer are the consumer's clv2 / scaler2.  Vector and
+// counts are what the cherry's own operation would have stored (the same product, the same factor), and they are
+// stored -- only never read back.  (Only what is needed of the entry is fetched, and only in front of a fold: both entries in scalar
+// registers at once spilled over a hundred of them.)
+template <unsigned RT, bool RS, bool WIDE, bool FOLD = false>
 __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2 X[RT][5],
                                     const double * s1, const double * s2,
                                     unsigned lut_codes, unsigned lut_used, bool lut_lds,
                                     unsigned blk, unsigned lane, bool nt_ld, bool nt_st,
                                     unsigned (&xe)[RS ? RT : 1], unsigned (&xo)[RS ? RT : 1], bool store = true,
-                                    unsigned wide_lds = 0)
+                                    unsigned wide_lds = 0, bool fold = false, const PlanOp * fentry = nullptr,
+                                    const double * lds = nullptr, bool ftrans = false)
 {
+  static_assert(!FOLD || (!RS && !WIDE), "cherries are folded with per-site scalers and without wide tips only");
   // wide_lds: PlanOp::flags -- bit 1 / 2: the rows of wide tip 1 / 2 are staged in LDS (s1 / s2, rows of S20_LUT_RS)
   const unsigned q = lane >> 4, n = lane & 15;
   const size_t site0 = (size_t)blk * S20_BS + 2 * n;
+  // the folded cherry: its four tip codes in one register, its scaling decisions in another (bit 0 / 1: even / odd site)
+  unsigned fcodes = 0, fsmall = 0;
+  const double * fa = nullptr, * fb = nullptr;
+  bool fstore = true;
+  if (FOLD && fold)
+  {
+    const uint8_t * ca = as_global(plan_fetch(&fentry->d.codes1)), * cb = as_global(plan_fetch(&fentry->d.codes2));
+    struct Tail { unsigned carried, slot1, slot2, flags; };      // what follows PlanOp::d
+    static_assert(offsetof(PlanOp, carried) % 8 == 0 && offsetof(PlanOp, flags) == offsetof(PlanOp, carried) + 12, "PlanOp layout");
+    const Tail tail = plan_fetch(reinterpret_cast<const Tail *>(&fentry->carried));
+    fa = lds + tail.slot1;
+    fb = lds + tail.slot2;
+    if (ftrans) fstore = !(tail.flags & 1u);
+    const unsigned ae = ca[site0], ao = ca[site0 + 1], be = cb[site0], bo = cb[site0 + 1];
+    fcodes = ae | (ao << 8) | (be << 16) | (bo << 24);
+    // (one register through the rate loop, not four: without the fence the optimiser sees through the packing)
+    asm volatile("" : "+v"(fcodes));
+    unsigned * fscaler = const_cast<unsigned *>(op.scaler2);
+    if (fscaler)
+    {
+      const unsigned * bits = reinterpret_cast<const unsigned *>(fb + s20_tip_slot(RT, lut_used));
+      const unsigned pe = ae * lut_used + be, po = ao * lut_used + bo;
+      fsmall = ((bits[pe >> 5] >> (pe & 31u)) & 1u) | (((bits[po >> 5] >> (po & 31u)) & 1u) << 1);
+      if (q == 0)
+      {
+        fscaler[site0] = fsmall & 1u;
+        fscaler[site0 + 1] = fsmall >> 1;
+      }
+    }
+  }
   unsigned c1e = 0, c1o = 0, c2e = 0, c2o = 0;
   // a "wide tip" (kernels_repeats.hpp: a cherry known per class of sites): neither vector nor byte codes; the
   // pfrag field holds its class codes (32 bits each), lut its table, childN_index the rows of that table
@@ -501,18 +599,47 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
   else if (w2) { c2e = w2[site0]; c2o = w2[site0 + 1]; }
   const bool scaling = op.parent_scaler != nullptr;
   int small_e = 1, small_o = 1;
+  // (FOLD: the tips' codes share a register too -- the instantiation has none to spare)
+  unsigned cpack = 0;
+  if (FOLD)
+  {
+    cpack = c1e | (c1o << 8) | (c2e << 16) | (c2o << 24);
+    asm volatile("" : "+v"(cpack));
+  }
 #pragma unroll
   for (unsigned r = 0; r < RT; ++r)
   {
     const size_t ubase = ((size_t)blk * RT + r) * S20_UNIT;
     double2 t1[5], t2[5];
+    if (FOLD) { c1e = cpack & 255u; c1o = (cpack >> 8) & 255u; c2e = (cpack >> 16) & 255u; c2o = cpack >> 24; }
     if (carried == 1) s20_child_regs_c(X[r], s1 + r * S20_CFRAGS, lane, t1);
     else if (w1 && (wide_lds & 2u)) s20_child_tip(s1 + r * op.child1_index * S20_LUT_RS, c1e, c1o, q, t1, S20_LUT_RS);
     else if (w1) s20_child_tip(op.lut1 + (size_t)r * op.child1_index * 20, c1e, c1o, q, t1);
     else if (!op.codes1) s20_child_inner_c(op.clv1 + ubase, s1 + r * S20_CFRAGS, lane, t1, nt_ld);
     else if (lut_lds) s20_child_tip(s1 + r * lut_used * S20_LUT_RS, c1e, c1o, q, t1, S20_LUT_RS);
     else s20_child_tip(op.lut1 + (size_t)r * lut_codes * 20, c1e, c1o, q, t1);
-    if (carried == 2) s20_child_regs_c(X[r], s2 + r * S20_CFRAGS, lane, t2);
+    if (FOLD)
+    {
+      if (carried == 2) s20_child_regs_c(X[r], s2 + r * S20_CFRAGS, lane, t2);
+      else if (op.codes2) s20_child_tip(s2 + r * lut_used * S20_LUT_RS, c2e, c2o, q, t2, S20_LUT_RS);
+      else
+      {
+        // the operand block: built from the cherry's tables (and stored), or read from memory -- one product either way
+        double2 b[5];
+        if (fold)
+        {
+          s20_fold_block(fa + r * lut_used * S20_LUT_RS, fb + r * lut_used * S20_LUT_RS, fcodes, fsmall, q, b);
+          if (fstore) s20_store_d(const_cast<double *>(op.clv2) + ubase, lane, b, nt_st);
+        }
+        else
+        {
+#pragma unroll
+          for (int ks = 0; ks < 5; ++ks) b[ks] = s20_ld(op.clv2 + ubase + ks * 128 + lane * 2, nt_ld);
+        }
+        s20_child_regs_c(b, s2 + r * S20_CFRAGS, lane, t2);
+      }
+    }
+    else if (carried == 2) s20_child_regs_c(X[r], s2 + r * S20_CFRAGS, lane, t2);
     else if (w2 && (wide_lds & 4u)) s20_child_tip(s2 + r * op.child2_index * S20_LUT_RS, c2e, c2o, q, t2, S20_LUT_RS);
     else if (w2) s20_child_tip(op.lut2 + (size_t)r * op.child2_index * 20, c2e, c2o, q, t2);
     else if (!op.codes2) s20_child_inner_c(op.clv2 + ubase, s2 + r * S20_CFRAGS, lane, t2, nt_ld);
@@ -604,6 +731,7 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
     if (op.scaler2)
     {
       if (carried == 2) { ce += xe[0]; co += xo[0]; }
+      else if (FOLD && fold) { ce += fsmall & 1u; co += fsmall >> 1; }
       else if (w2) { ce += op.scaler2[c2e]; co += op.scaler2[c2o]; }
       else { ce += op.scaler2[site0]; co += op.scaler2[site0 + 1]; }
     }
@@ -697,7 +825,11 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_chain_s20(ChainBatc
 // grid = gx, block = 512, dynamic LDS = the largest chain area of the schedule.
 // TRANS: an evaluate-only traversal -- operations whose PlanOp::flags bit 0 is set hand their result on in registers only
 // (a compile-time switch: as a run-time flag in front of every store it cost the storing traversal 3.5 %)
-template <unsigned RT, bool RS, bool WIDE, bool TRANS>
+// FOLD: the schedule holds folded cherries -- PlanOp::flags bit 3: the entry is a cherry whose block the NEXT entry
+// builds in registers (bit 4 there: its child 2 is that cherry).  Its tip tables are staged like any other entry's, the
+// scaling decisions per pair of codes go behind them (PlanChain::flags bit 1: the chain has such entries), and the
+// operation loop passes it over.  Schedules without folds run the instantiation without the flag.
+template <unsigned RT, bool RS, bool WIDE, bool TRANS, bool FOLD>
 __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_traverse_s20(PlanView plan, unsigned chain_begin,
                                                                            unsigned chain_end, unsigned nblk,
                                                                            unsigned slab, unsigned flags)
@@ -738,6 +870,17 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_traverse_s20(PlanVi
           s20_fill_slot(lds + po.slot2, nullptr, nullptr, po.d.lut2, RT, po.d.child2_index, po.d.child2_index, true);
       }
       __syncthreads();
+      if (FOLD && (ch.flags & 2u))
+      {
+        for (unsigned i = 0; i < ch.len; ++i)
+        {
+          const PlanOp po = plan_fetch_op(plan_ops_ + ch.first + i);
+          if ((po.flags & 8u) && po.d.parent_scaler)
+            s20_fold_bits<RT>(lds + po.slot1, lds + po.slot2,
+                              reinterpret_cast<unsigned long long *>(lds + po.slot2 + s20_tip_slot(RT, lut_used)), lut_used);
+        }
+        __syncthreads();
+      }
 
       for (unsigned blk = s0 + blockIdx.x * S20_CHAIN_WAVES + wave; blk < s1; blk += wstride)
       {
@@ -747,6 +890,15 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_traverse_s20(PlanVi
         for (unsigned i = 0; i < ch.len; ++i)
         {
           const PlanOp po = plan_fetch_op(plan_ops_ + ch.first + i);
+          if (FOLD)
+          {
+            if (po.flags & 8u) continue;                // built by the next entry
+            // (tip tables are staged wherever cherries are folded: s20_fold_lds)
+            s20_chain_op<RT, RS, WIDE, FOLD>(po.d, po.carried, X, lds + po.slot1, lds + po.slot2, lut_codes, lut_used, true,
+                                             blk, lane, nt_ld, nt_st, xe, xo, TRANS ? !(po.flags & 1u) : true, 0u,
+                                             (po.flags & 16u) != 0, plan_ops_ + ch.first + i - 1, lds, TRANS);
+            continue;
+          }
           s20_chain_op<RT, RS, WIDE>(po.d, i ? po.carried : 0u, X, lds + po.slot1, lds + po.slot2,
                                      lut_codes, lut_used, lut_lds, blk, lane, nt_ld, nt_st, xe, xo, TRANS ? !(po.flags & 1u) : true,
                                      WIDE ? po.flags : 0u);
@@ -1568,6 +1720,14 @@ static unsigned s20_chain_slot(const Engine * e, bool tip, unsigned lut_used)
   return s20_chain_lut_lds(e, lut_used) ? ((e->R * lut_used * S20_LUT_RS + 7u) & ~7u) : 0u;
 }
 
+// LDS doubles of a folded cherry in its consumer's chain: its two tip tables and the scaling decisions per pair of
+// codes (0: no folds -- per-rate scalers, class nodes, tip tables that are not staged)
+static unsigned s20_fold_lds(const Engine * e, unsigned lut_used)
+{
+  if (e->rate_scalers || !e->cherries.empty() || !s20_chain_lut_lds(e, lut_used) || lut_used > 255u) return 0u;
+  return 2u * s20_tip_slot(e->R, lut_used) + s20_fold_bits_lds(lut_used);
+}
+
 // (A second geometry for small slices -- chains of two, two 256-thread workgroups per CU, so
 // that one workgroup's fragment fill overlaps the other's streaming -- was measured at
 // 125 k / 250 k / 500 k sites and is 13 % / 15 % / 0 % slower than this one: the extra
@@ -1629,7 +1789,7 @@ static int launch_chains_s20(Engine * e, const ChainBatch & batch, unsigned ncha
 // `extent`: site blocks of the largest partition the chains [chain_begin, chain_end) belong to
 static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_doubles, unsigned extent,
                                unsigned chain_begin, unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu,
-                               bool wide, bool transient)
+                               bool wide, bool transient, bool fold)
 {
   const size_t lds = sizeof(double) * lds_doubles;
   const unsigned flags = []() { const char * v = getenv("PLLHIP_S20_NT"); return v ? (unsigned)atoi(v) & 3u : 0u; }();
@@ -1637,10 +1797,11 @@ static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_d
   bool & attr_set = attr_set_dev[e->device & 63];
   if (!attr_set)
   {
-#define PLLHIP_ALLOW(RS_, W_, T_) (s20_allow_full_lds(k_traverse_s20<4, RS_, W_, T_>) && s20_allow_full_lds(k_traverse_s20<2, RS_, W_, T_>) && \
-                                   s20_allow_full_lds(k_traverse_s20<1, RS_, W_, T_>))
-    if (!PLLHIP_ALLOW(false, false, false) || !PLLHIP_ALLOW(true, false, false) || !PLLHIP_ALLOW(false, true, false) ||
-        !PLLHIP_ALLOW(false, false, true) || !PLLHIP_ALLOW(true, false, true) || !PLLHIP_ALLOW(false, true, true))
+#define PLLHIP_ALLOW(RS_, W_, T_, F_) (s20_allow_full_lds(k_traverse_s20<4, RS_, W_, T_, F_>) && s20_allow_full_lds(k_traverse_s20<2, RS_, W_, T_, F_>) && \
+                                       s20_allow_full_lds(k_traverse_s20<1, RS_, W_, T_, F_>))
+    if (!PLLHIP_ALLOW(false, false, false, false) || !PLLHIP_ALLOW(true, false, false, false) || !PLLHIP_ALLOW(false, true, false, false) ||
+        !PLLHIP_ALLOW(false, false, true, false) || !PLLHIP_ALLOW(true, false, true, false) || !PLLHIP_ALLOW(false, true, true, false) ||
+        !PLLHIP_ALLOW(false, false, false, true) || !PLLHIP_ALLOW(false, false, true, true))
       return PLL_FAILURE;
 #undef PLLHIP_ALLOW
     attr_set = true;
@@ -1658,16 +1819,23 @@ static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_d
   slab = std::max(per_pass, (slab + per_pass - 1) / per_pass * per_pass);   // whole passes of the grid
   const dim3 grid(gx, std::max(1u, rows)), block(64 * S20_CHAIN_WAVES);
 #define PLLHIP_CALL(K) hipLaunchKernelGGL(K, grid, block, lds, e->stream, plan, chain_begin, chain_end, extent, slab, flags)
-#define PLLHIP_BY_RATES(RS_, W_, T_)                                              \
+#define PLLHIP_BY_RATES(RS_, W_, T_, F_)                                          \
   do {                                                                           \
-    if (e->R == 4) { PLLHIP_CALL((k_traverse_s20<4, RS_, W_, T_>)); }             \
-    else if (e->R == 2) { PLLHIP_CALL((k_traverse_s20<2, RS_, W_, T_>)); }        \
-    else { PLLHIP_CALL((k_traverse_s20<1, RS_, W_, T_>)); }                       \
+    if (e->R == 4) { PLLHIP_CALL((k_traverse_s20<4, RS_, W_, T_, F_>)); }         \
+    else if (e->R == 2) { PLLHIP_CALL((k_traverse_s20<2, RS_, W_, T_, F_>)); }    \
+    else { PLLHIP_CALL((k_traverse_s20<1, RS_, W_, T_, F_>)); }                   \
   } while (0)
+  // (a schedule with folded cherries is planned without wide tips and with per-site scaling only: s20_fold_lds)
+  if (fold && (wide || e->rate_scalers))
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "folded cherries in a schedule with wide tips or per-rate scalers");
+    return PLL_FAILURE;
+  }
   // (wide tips -- site repeats, tips kept per class -- exist with per-site scaling only)
-  if (wide && !e->rate_scalers) { if (transient) PLLHIP_BY_RATES(false, true, true); else PLLHIP_BY_RATES(false, true, false); }
-  else if (e->rate_scalers) { if (transient) PLLHIP_BY_RATES(true, false, true); else PLLHIP_BY_RATES(true, false, false); }
-  else { if (transient) PLLHIP_BY_RATES(false, false, true); else PLLHIP_BY_RATES(false, false, false); }
+  if (fold) { if (transient) PLLHIP_BY_RATES(false, false, true, true); else PLLHIP_BY_RATES(false, false, false, true); }
+  else if (wide && !e->rate_scalers) { if (transient) PLLHIP_BY_RATES(false, true, true, false); else PLLHIP_BY_RATES(false, true, false, false); }
+  else if (e->rate_scalers) { if (transient) PLLHIP_BY_RATES(true, false, true, false); else PLLHIP_BY_RATES(true, false, false, false); }
+  else { if (transient) PLLHIP_BY_RATES(false, false, true, false); else PLLHIP_BY_RATES(false, false, false, false); }
 #undef PLLHIP_BY_RATES
 #undef PLLHIP_CALL
   PLLHIP_TRY(hipGetLastError());

@@ -1118,13 +1118,16 @@ struct ChainFamily
   // they take no more than a coded tip's table may, else gathered from memory (0)
   unsigned (*wide_lds)(const Engine * e, unsigned rows);
   bool (*tables_in_lds)(const Engine * e, unsigned lut_used);             // PlanChain::flags bit 0
+  // the family folds lone cherries into the chain that reads them (plan_folds): LDS doubles of one fold in its
+  // consumer's chain (null: the family has no folds; 0: none at this partition's shape)
+  unsigned (*fold_lds)(const Engine * e, unsigned lut_used);
   const double * (*pair_pfrag)(const Engine * e, unsigned matrix);        // PairLutJob::pfrag of a branch
   bool (*fills_chip)(const Engine * e);                 // the site blocks alone keep the chip busy: one launch
   unsigned (*units)(const Engine * e);                  // workgroups a member of a batch can use side by side
   unsigned batch_wgs;                                   // workgroups per CU and row of a batch in one launch
   // a resident schedule (DevicePlan, upload_plan): chains [begin, end) in `rows` grid rows
   int (*traverse)(Engine * e, const PlanView & view, unsigned lds_doubles, unsigned extent, unsigned begin,
-                  unsigned end, unsigned rows, unsigned wgs, bool wide, bool transient);
+                  unsigned end, unsigned rows, unsigned wgs, bool wide, bool transient, bool fold);
   // chains by value in the kernel arguments (null: none)
   int (*chains)(Engine * e, const ChainBatch & batch, unsigned nchains, unsigned lds, unsigned lut_used);
   // class nodes (kernels_repeats.hpp): row tables, class tables, the site-indexed vector of one node
@@ -1139,6 +1142,7 @@ static const ChainFamily CHAINS_S4 = {
   .child_lds = [](const Engine *, bool, unsigned) { return 0u; },
   .wide_lds = [](const Engine *, unsigned) { return 0u; },
   .tables_in_lds = [](const Engine *, unsigned) { return false; },
+  .fold_lds = nullptr,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pmat + (size_t)m * e->R * 16; },
   .fills_chip = [](const Engine * e) { return (e->N + 63) / 64 >= 48u * e->cu_count; },
   .units = [](const Engine * e) { return (e->N + 255u) / 256u; }, .batch_wgs = 3,
@@ -1160,6 +1164,7 @@ static const ChainFamily CHAINS_S16 = {
   .child_lds = [](const Engine * e, bool tip, unsigned) { return s16_chain_slot(e, tip); },
   .wide_lds = [](const Engine * e, unsigned rows) { return e->R * rows * e->S <= S16_LUT_LDS ? ((e->R * rows * e->S + 7u) & ~7u) : 0u; },
   .tables_in_lds = [](const Engine * e, unsigned) { return s16_chain_lut_lds(e); },
+  .fold_lds = nullptr,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pmat + (size_t)m * e->R * e->S * e->Sp; },
   .fills_chip = [](const Engine * e) { return e->nblk >= 12u * e->cu_count && e->nblk < 48u * e->cu_count && e->S > 8; },
   .units = [](const Engine * e) { return (e->nblk + 7u) / 8u; }, .batch_wgs = 1,
@@ -1195,6 +1200,7 @@ static const ChainFamily CHAINS_S20 = {
   .child_lds = s20_chain_slot,
   .wide_lds = [](const Engine * e, unsigned rows) { return e->R * rows * S20_LUT_RS <= 2560u ? ((e->R * rows * S20_LUT_RS + 7u) & ~7u) : 0u; },
   .tables_in_lds = s20_chain_lut_lds,
+  .fold_lds = s20_fold_lds,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pfrag + (size_t)m * e->R * 400; },
   .fills_chip = [](const Engine * e) { return e->nblk >= 6u * e->cu_count && e->nblk < 24u * e->cu_count; },
   .units = [](const Engine * e) { return (e->nblk + 7u) / 8u; }, .batch_wgs = 1,
@@ -1241,6 +1247,14 @@ static const ChainFamily * chain_family(const Engine * e)
 // attribute a tip is a vector -- and, when it came through pll_set_tip_states, a class node as well (upload_tip_classes)
 static bool coded_tip(const Engine * e, unsigned idx) { return e->coded_tips && idx < e->tips; }
 
+// LDS doubles of a lone cherry folded into the chain that reads it, or 0: the family has no folds, none at this
+// shape, or PLLHIP_FOLD=0 (the schedules without folds: the reference of the A/B runs and of the bitwise tests)
+static unsigned fold_table_lds(const Engine * e, const ChainFamily & f, unsigned lut_used)
+{
+  static const int use_fold = getenv("PLLHIP_FOLD") ? atoi(getenv("PLLHIP_FOLD")) : 1;
+  return use_fold && f.fold_lds && e->coded_tips ? f.fold_lds(e, lut_used) : 0u;
+}
+
 // LDS doubles of the table of child `idx` in a chain kernel; wide: the child is read as a wide tip
 static unsigned child_table_lds(const Engine * e, const ChainFamily & f, unsigned idx, unsigned lut_used, bool wide)
 {
@@ -1257,6 +1271,9 @@ struct ChainPlan
   std::vector<int> launch;                       // per chain: launch round
   std::vector<unsigned> lds;                     // per chain: LDS doubles of its operations' tables
   std::vector<unsigned char> carried;            // per op
+  // per op: 1 / 2 = a lone cherry that the next operation of its chain builds in registers as its child 1 / 2
+  // (plan_folds; empty: no folds).  Such an operation sits in front of its consumer in `chains`
+  std::vector<unsigned char> folded;
   int rounds = 0;
 };
 
@@ -1333,6 +1350,159 @@ static bool plan_chains(const Engine * e, const ChainFamily * f, const pll_opera
     plan.rounds = std::max(plan.rounds, plan.launch[chain_of[k]] + 1);
   }
   return true;
+}
+
+// Folded cherries.  The vector that an operation reads next to the handed-over one comes back from memory -- unless it
+// is a lone cherry (a tip x tip operation that is a chain of its own): that one the consumer can build in registers
+// from the two tip tables, at the price of fold_lds doubles of the chain's LDS.  LDS is what ends chains, and a cut
+// costs a read as well (the handed-over vector comes back from memory), so cuts and folds are chosen together: per
+// heavy path (the operations linked by their larger child, which is what plan_chains' chains are pieces of) a dynamic
+// programme picks the cut points that minimise
+//     vectors read from memory = cuts + foldable cherries that are not folded
+// under the caps (max_len operations per chain, not counting the folded ones; lds_cap doubles including the folds'
+// tables); within a piece as many cherries are folded as fit.  Ties go to fewer cuts.  Without a foldable cherry, or
+// when the optimum folds nothing, `plan` stays what plan_chains made it -- whose greedy cuts are the fewest possible --,
+// so the result never reads more than the plan without folds.
+// `plan`: plan_chains' result for the same arguments (the list has the shape of a tree traversal).
+static void plan_folds(const Engine * e, const ChainFamily & f, const pll_operation_t * ops, unsigned count, unsigned max_len,
+                       unsigned lds_cap, unsigned lut_used, unsigned fold_lds, ChainPlan & plan)
+{
+  if (!fold_lds || count < 2) return;
+  std::vector<int> producer(e->nodes, -1), hprod(count, -1), up(count, -1), cherry(count, -1);
+  std::vector<unsigned> size(count, 1), cost(count, 0);
+  std::vector<unsigned char> hside(count, 0);
+  bool any = false;
+  for (unsigned k = 0; k < count; ++k)
+  {
+    const pll_operation_t & op = ops[k];
+    const int pr[2] = {producer[op.child1_clv_index], producer[op.child2_clv_index]};
+    producer[op.parent_clv_index] = (int)k;
+    size[k] = 1 + (pr[0] >= 0 ? size[pr[0]] : 0) + (pr[1] >= 0 ? size[pr[1]] : 0);
+    cost[k] = child_table_lds(e, f, op.child1_clv_index, lut_used, false) + child_table_lds(e, f, op.child2_clv_index, lut_used, false);
+    int heavy = -1;                               // (plan_chains' choice)
+    if (pr[0] >= 0 && (pr[1] < 0 || size[pr[0]] >= size[pr[1]])) heavy = 0;
+    else if (pr[1] >= 0) heavy = 1;
+    if (heavy < 0) continue;
+    hprod[k] = pr[heavy];
+    hside[k] = (unsigned char)(heavy + 1);
+    up[pr[heavy]] = (int)k;
+    const int light = pr[1 - heavy];
+    if (light < 0) continue;
+    const pll_operation_t & c = ops[light];
+    if (coded_tip(e, c.child1_clv_index) && coded_tip(e, c.child2_clv_index) &&
+        c.child1_scaler_index == PLL_SCALE_BUFFER_NONE && c.child2_scaler_index == PLL_SCALE_BUFFER_NONE)
+    {
+      cherry[k] = light;
+      any = true;
+    }
+  }
+  if (!any) return;
+
+  // per path: the pieces [a, b] and how many cherries each folds
+  struct Piece { unsigned a, b, folds; };
+  std::vector<std::vector<unsigned>> paths;
+  std::vector<std::vector<Piece>> pieces;
+  unsigned nfolds = 0;
+  for (unsigned k = 0; k < count; ++k)
+  {
+    if (hprod[k] >= 0) continue;                  // not the bottom of a path
+    std::vector<unsigned> path;
+    for (int x = (int)k; x >= 0; x = up[x]) path.push_back((unsigned)x);
+    const unsigned n = (unsigned)path.size();
+    // best[i]: the first i operations of the path; value = (pieces - folds, pieces), smallest first
+    const long INF = 1L << 40;
+    std::vector<long> best(n + 1, INF);
+    std::vector<unsigned> from(n + 1, 0), nf(n + 1, 0);
+    best[0] = 0;
+    for (unsigned b = 0; b < n; ++b)
+    {
+      unsigned lds = 0, foldable = 0;
+      for (unsigned a = b + 1; a-- > 0 && b - a < max_len; )
+      {
+        lds += cost[path[a]];
+        if (lds > lds_cap) break;
+        if (cherry[path[a]] >= 0) ++foldable;
+        if (best[a] >= INF) continue;
+        const unsigned folds = std::min(foldable, (lds_cap - lds) / fold_lds);
+        const long v = best[a] + (1L - (long)folds) * 4096L + 1L;
+        if (v < best[b + 1]) { best[b + 1] = v; from[b + 1] = a; nf[b + 1] = folds; }
+      }
+    }
+    if (best[n] >= INF) return;                   // (an operation whose own tables exceed the cap: plan_chains' plan stands)
+    std::vector<Piece> pc;
+    for (unsigned i = n; i > 0; i = from[i]) pc.push_back({from[i], i - 1, nf[i]});
+    std::reverse(pc.begin(), pc.end());
+    for (const Piece & x : pc) nfolds += x.folds;
+    paths.push_back(std::move(path));
+    pieces.push_back(std::move(pc));
+  }
+  if (!nfolds) return;
+
+  // the chains: the pieces of the paths, numbered by their first operation as plan_chains numbers them; a folded
+  // cherry (a path of one operation) goes in front of its consumer instead of forming a chain
+  std::vector<char> is_folded(count, 0);
+  std::vector<std::pair<unsigned, std::vector<unsigned>>> made;     // (first operation, chain)
+  std::vector<unsigned> made_lds;
+  ChainPlan out;
+  out.carried.assign(count, 0);
+  out.folded.assign(count, 0);
+  for (size_t p = 0; p < paths.size(); ++p)
+    for (const Piece & x : pieces[p])
+    {
+      unsigned left = x.folds;
+      for (unsigned j = x.a; j <= x.b && left; ++j)
+        if (cherry[paths[p][j]] >= 0) { is_folded[cherry[paths[p][j]]] = 1; --left; }
+    }
+  for (size_t p = 0; p < paths.size(); ++p)
+  {
+    if (paths[p].size() == 1 && is_folded[paths[p][0]]) continue;
+    for (const Piece & x : pieces[p])
+    {
+      std::vector<unsigned> ch;
+      unsigned lds = 0;
+      for (unsigned j = x.a; j <= x.b; ++j)
+      {
+        const unsigned k = paths[p][j];
+        if (cherry[k] >= 0 && is_folded[cherry[k]])
+        {
+          ch.push_back((unsigned)cherry[k]);
+          out.folded[cherry[k]] = (unsigned char)(3 - hside[k]);      // the child that is not the heavy one
+          lds += fold_lds;
+        }
+        ch.push_back(k);
+        lds += cost[k];
+        out.carried[k] = j > x.a ? hside[k] : 0;
+      }
+      made.emplace_back(paths[p][x.a], std::move(ch));
+      made_lds.push_back(lds);
+    }
+  }
+  std::vector<size_t> idx(made.size());
+  for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
+  std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return made[a].first < made[b].first; });
+  std::vector<int> chain_of(count, -1);
+  for (size_t i : idx)
+  {
+    for (unsigned k : made[i].second) chain_of[k] = (int)out.chains.size();
+    out.chains.push_back(std::move(made[i].second));
+    out.lds.push_back(made_lds[i]);
+  }
+  // rounds: a chain runs after the chains whose last vector it reads from memory (a folded cherry is no chain)
+  out.launch.assign(out.chains.size(), 0);
+  std::fill(producer.begin(), producer.end(), -1);
+  for (unsigned k = 0; k < count; ++k)
+  {
+    const unsigned child[2] = {ops[k].child1_clv_index, ops[k].child2_clv_index};
+    for (int c = 0; c < 2; ++c)
+    {
+      const int pk = producer[child[c]];
+      if (pk >= 0 && chain_of[pk] != chain_of[k])
+        out.launch[chain_of[k]] = std::max(out.launch[chain_of[k]], out.launch[chain_of[pk]] + 1);
+    }
+    producer[ops[k].parent_clv_index] = (int)k;
+    out.rounds = std::max(out.rounds, out.launch[chain_of[k]] + 1);
+  }
+  plan = std::move(out);
 }
 
 // make DevicePlan::bytes resident on the device (stream-ordered; nothing is copied when the
@@ -1757,6 +1927,7 @@ struct ScheduleRequest
   unsigned mode;
   bool transient;                                // an evaluate-only traversal (pllhip_set_transient)
   const RepeatPlan * rp;                         // site repeats: the class operations and the rest (null: none)
+  bool fold = false;                             // lone cherries may be folded into the chains that read them (plan_folds)
 };
 
 struct ScheduleBuild                             // the schedule being built (DevicePlan::bytes)
@@ -1768,6 +1939,7 @@ struct ScheduleBuild                             // the schedule being built (De
   std::vector<PairLutJob> level_pairs;           // row tables of class children, by level of their parent
   size_t pairlut_used = 0;                       // doubles of e->d_pairlut handed out
   unsigned nops = 0, lds_max = 0;
+  unsigned nfolds = 0, inner_reads = 0;          // folded cherries; inner vectors that the chains read from memory
 };
 
 // site repeats: children that are cherries kept per class are read as wide tips (kernels_repeats.hpp);
@@ -1804,13 +1976,14 @@ static bool mark_wide_tips(Engine * e, const pll_operation_t * ops, unsigned cou
 // the cache key: the list as the caller passed it (the cherries taken out of it are part of the schedule), the codes
 // in use, the mode, the wide tips, and which operations are kept per class (the same list can meet other class nodes
 // of earlier calls)
-static std::vector<unsigned char> schedule_key(const ScheduleRequest & rq, unsigned lut_used, const std::vector<unsigned char> & wide)
+static std::vector<unsigned char> schedule_key(const ScheduleRequest & rq, unsigned lut_used, const std::vector<unsigned char> & wide,
+                                               bool fold)
 {
   std::vector<unsigned char> tracked(rq.rp ? rq.count : 0, 0);
   if (rq.rp) for (unsigned k : rq.rp->cherry_ops) tracked[k] = 1;
   const size_t list_bytes = (size_t)rq.count * sizeof(pll_operation_t);
   std::vector<unsigned char> key(3 * sizeof(unsigned) + list_bytes + wide.size() + tracked.size());
-  const unsigned mode_key = rq.mode | (rq.transient ? 0x100u : 0u);
+  const unsigned mode_key = rq.mode | (rq.transient ? 0x100u : 0u) | (fold ? 0x200u : 0u);
   memcpy(key.data(), &rq.count, sizeof(unsigned));
   memcpy(key.data() + sizeof(unsigned), &lut_used, sizeof(unsigned));
   memcpy(key.data() + 2 * sizeof(unsigned), &mode_key, sizeof(unsigned));
@@ -1954,16 +2127,49 @@ static void emit_chains(const Engine * e, const ChainFamily & f, const pll_opera
     }
     sb.pchains.push_back({sb.nops, (unsigned)ch.size(), f.extent(e), e->lut_codes, lut_used, chain_flags});
     unsigned off = 0;
+    unsigned fold_side = 0;                       // the operation in front is a cherry folded into this one (as child 1 / 2)
+    bool first = true;                            // the first operation of the chain that is not folded
     for (size_t i = 0; i < ch.size(); ++i)
     {
-      const pll_operation_t & o = ops[ch[i]];
+      pll_operation_t o = ops[ch[i]];
       PlanOp & po = sb.pops[sb.nops++];
       memset(&po, 0, sizeof(po));
       const double before = dp.algo_bytes;
+      const unsigned folded = plan.folded.empty() ? 0u : plan.folded[ch[i]];
+      po.carried = first ? 0 : plan.carried[ch[i]];
+      if (!folded) first = false;
+      if (fold_side == 1)                         // the folded cherry is child 2 (products commute)
+      {
+        std::swap(o.child1_clv_index, o.child2_clv_index);
+        std::swap(o.child1_matrix_index, o.child2_matrix_index);
+        std::swap(o.child1_scaler_index, o.child2_scaler_index);
+        if (po.carried) po.carried = 3 - po.carried;
+        fold_side = 2;
+      }
       fill_desc(e, o, po.d, dp.algo_bytes, dp.algo_flops);
-      po.carried = i ? plan.carried[ch[i]] : 0;
       // an evaluate-only traversal: the vectors inside a chain are handed on in registers only
       po.flags = (rq.transient && i + 1 < ch.size()) ? 1u : 0u;
+      if (folded)
+      {
+        // a folded cherry: bit 3 here, bit 4 on its consumer (the next entry); its two tip tables and, behind
+        // them, its scaling decisions per pair of codes take fold_lds doubles of the chain's LDS
+        po.flags |= 8u;
+        sb.pchains.back().flags |= 2u;
+        ++sb.nfolds;
+        dp.min_bytes += dp.algo_bytes - before - ((po.flags & 1u) ? (double)e->N * e->R * 8.0 * e->S : 0.0);
+        po.slot1 = off;
+        po.slot2 = off + child_table_lds(e, f, o.child1_clv_index, lut_used, false);
+        off += f.fold_lds(e, lut_used);
+        fold_side = folded;
+        continue;
+      }
+      if (fold_side) po.flags |= 16u;
+      for (unsigned x = 1; x <= 2; ++x)
+      {
+        const unsigned idx = x == 1 ? o.child1_clv_index : o.child2_clv_index;
+        const bool w_x = !wide.empty() && wide[2 * ch[i] + x - 1];
+        if (idx >= e->tips && !w_x && po.carried != x && fold_side != x) ++sb.inner_reads;
+      }
       double wide_saved = (po.flags & 1u) ? (double)e->N * e->R * 8.0 * e->S : 0.0;
       const bool w[2] = {!wide.empty() && wide[2 * ch[i]], !wide.empty() && wide[2 * ch[i] + 1]};
       for (int x = 0; x < 2; ++x)
@@ -1986,6 +2192,10 @@ static void emit_chains(const Engine * e, const ChainFamily & f, const pll_opera
       if (po.carried)
         dp.min_bytes -= (double)e->N * e->R * 8.0 * e->S +
                         ((po.carried == 1 ? po.d.scaler1 : po.d.scaler2) ? 4.0 * (double)e->N * (e->rate_scalers ? e->R : 1) : 0.0);
+      // ... and so does a folded cherry
+      if (fold_side)
+        dp.min_bytes -= (double)e->N * e->R * 8.0 * e->S + ((fold_side == 1 ? po.d.scaler1 : po.d.scaler2) ? 4.0 * (double)e->N : 0.0);
+      fold_side = 0;
       po.slot1 = off;
       off += child_table_lds(e, f, o.child1_clv_index, lut_used, w[0]);
       po.slot2 = off;
@@ -2125,11 +2335,14 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   std::vector<unsigned char> wide;
   unsigned nwide = 0;
   if (!mark_wide_tips(e, ops, count, lut_used, wide, nwide)) return false;
-  std::vector<unsigned char> key = schedule_key(rq, lut_used, wide);
+  // (folds: not next to class nodes; PLLHIP_FOLD and the family decide the rest)
+  const unsigned fold_lds = rq.fold && !rq.rp && !nwide ? fold_table_lds(e, f, lut_used) : 0u;
+  std::vector<unsigned char> key = schedule_key(rq, lut_used, wide, fold_lds != 0);
   if (!dp.key.empty() && dp.key == key) return true;
   if ((nwide || rq.rp) && !reserve_pair_tables(e, rq, ops, count, wide)) return false;
   ChainPlan plan;
   if (!plan_chains(e, &f, ops, count, f.chain_max, f.chain_lds, lut_used, plan, &wide)) return false;
+  plan_folds(e, f, ops, count, f.chain_max, f.chain_lds, lut_used, fold_lds, plan);
   ScheduleBuild sb;
   sb.pops.resize(count);
   emit_chains(e, f, ops, plan, chain_order(e, ops, count, plan, rq.mode == 0), wide, lut_used, rq, dp, sb);
@@ -2141,6 +2354,8 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   dp.nops = sb.nops;
   dp.nchains = (unsigned)sb.pchains.size();
   dp.lds_doubles = sb.lds_max;
+  dp.nfolds = sb.nfolds;
+  dp.inner_reads = sb.inner_reads;
   dp.max_extent = f.extent(e);
   dp.generation = ++plan_generation;
   dp.key.swap(key);
@@ -2374,7 +2589,7 @@ static int launch_resident(Engine * e, const ChainFamily & f, const DevicePlan &
 {
   for (const DevicePlan::Launch & l : dp.launches)
     if (!counted_launch(e, l.bytes, l.flops, l.ops, l.min_bytes, [&]()
-        { return f.traverse(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, l.rows, wgs, wide, transient); }))
+        { return f.traverse(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, l.rows, wgs, wide, transient, dp.nfolds != 0); }))
       return PLL_FAILURE;
   return PLL_SUCCESS;
 }
@@ -2677,7 +2892,7 @@ static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops
     if (!select_class_ops(e, ops, count, lut_used, rp)) return PLL_FAILURE;
     // (evaluate-only traversals: not together with site repeats, whose class operations leave the list)
     const bool transient = e->transient_mode && !e->site_repeats;
-    if (prepare_schedule(e, p, *f, {ops, count, (unsigned)mode, transient, rp.active ? &rp : nullptr}))
+    if (prepare_schedule(e, p, *f, {ops, count, (unsigned)mode, transient, rp.active ? &rp : nullptr, true}))
       return run_resident(e, *f, ops, count, rp, transient);
     if (rp.active)
       for (unsigned k : rp.cherry_ops) e->cherries[ops[k].parent_clv_index].valid = false;     // the plain paths below compute them
@@ -4235,6 +4450,17 @@ int pllhip_discard_transient(pll_partition_t * p)
 int pllhip_transient_stats(const pll_partition_t * p, pllhip_transient_stats_t * out)
 {
   *out = exec_engine(p)->transient_stats;
+  return PLL_SUCCESS;
+}
+
+int pllhip_schedule_stats(const pll_partition_t * p, pllhip_schedule_stats_t * out)
+{
+  const DevicePlan & dp = exec_engine(p)->plan;
+  const bool resident = !dp.key.empty();
+  out->chains = resident ? dp.nchains : 0;
+  out->operations = resident ? dp.nops : 0;
+  out->inner_reads = resident ? dp.inner_reads : 0;
+  out->folded_cherries = resident ? dp.nfolds : 0;
   return PLL_SUCCESS;
 }
 

@@ -110,6 +110,10 @@ class TransientStats(C.Structure):
     _fields_ = [(n, C.c_ulonglong) for n in ("skipped", "materialized", "discarded")]
 
 
+class ScheduleStats(C.Structure):
+    _fields_ = [(n, C.c_uint) for n in ("chains", "operations", "inner_reads", "folded_cherries")]
+
+
 class Profile(C.Structure):
     _fields_ = [("launches", C.c_ulonglong), ("ops", C.c_ulonglong),
                 ("kernel_ms", C.c_double), ("algorithmic_bytes", C.c_double),
@@ -156,6 +160,7 @@ pllhip_shard_count pllhip_results_create pllhip_results_destroy
 pllhip_results_edge_loglikelihood pllhip_results_derivatives pllhip_results_fetch
 pllhip_eval_attach_comm pllhip_update_partials_batch pllhip_results_poison pllhip_newton_branch pllhip_repeat_stats
 pllhip_set_transient pllhip_discard_transient pllhip_transient_stats pllhip_newton_branch_multi
+pllhip_schedule_stats
 pllhip_parsimony_tree_score""".split()
 
 
@@ -303,6 +308,7 @@ class PllLib:
             L.pllhip_set_transient.argtypes = [pp, C.c_int]
             L.pllhip_discard_transient.argtypes = [pp]
             L.pllhip_transient_stats.argtypes = [pp, C.POINTER(TransientStats)]
+            L.pllhip_schedule_stats.argtypes = [pp, C.POINTER(ScheduleStats)]
             L.pllhip_comm_get_unique_id.argtypes = [C.c_char_p]
             L.pllhip_comm_create.restype = C.c_void_p
             L.pllhip_comm_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -594,6 +600,11 @@ class Instance:
     def transient_stats(self):
         st = TransientStats()
         self.L.pllhip_transient_stats(self.p, C.byref(st))
+        return st
+
+    def schedule_stats(self):
+        st = ScheduleStats()
+        self.L.pllhip_schedule_stats(self.p, C.byref(st))
         return st
 
 
