@@ -685,8 +685,11 @@ PLL_EXPORT int pll_utree_rollback(pll_utree_rb_t * rollback,
 
 /* ------------------------------------------------------------------ */
 /* B3: declared so that the remaining pll-modules files parse; the ones
-   without an implementation in this engine return PLL_FAILURE / NULL and
-   set pll_errno = PLL_ERROR_NOT_IMPLEMENTED.                          */
+   without an implementation in this engine (pll_rtree_*) return
+   PLL_FAILURE / NULL and set pll_errno = PLL_ERROR_NOT_IMPLEMENTED.
+   Real in the product library: the PRNG, parsimony, the FASTA / PHYLIP
+   readers and site-pattern compression ("Alignment
+   input"); the oracle keeps stubs for the last three groups.          */
 /* ------------------------------------------------------------------ */
 
 PLL_EXPORT pll_rtree_t * pll_rtree_parse_newick(const char * filename);
@@ -747,6 +750,11 @@ PLL_EXPORT unsigned int * pll_compress_site_patterns(char ** sequence,
                                                      const pll_state_t * map,
                                                      int count,
                                                      int * length);
+/* the same on msa->sequence / count / length; site_pattern_map (may be NULL)
+   receives the pattern index of each of the original msa->length sites */
+PLL_EXPORT unsigned int * pll_compress_site_patterns_msa(pll_msa_t * msa,
+                                                         const pll_state_t * map,
+                                                         unsigned int * site_pattern_map);
 
 #ifdef __cplusplus
 }

@@ -380,6 +380,16 @@ PLL_EXPORT void pllhip_results_poison(pllhip_results_t * results);
 struct pllhip_eval;
 PLL_EXPORT int pllhip_eval_attach_comm(struct pllhip_eval * ev, pllhip_comm_t * comm);
 
+/* device time of this thread's last successful pll_compress_site_patterns[_msa] call, in ms between HIP events on the
+   call's stream: rows up; the kernels (table set-up, hash, insert, numbering, then gather: two device segments, without
+   the host's read of the pattern count and its allocation of the output between them); results down.  Any pointer
+   may be NULL.  (tools/gpu_compress.py) */
+PLL_EXPORT void pllhip_compress_last_times(double * upload_ms, double * kernel_ms, double * download_ms);
+/* work of the hash table in that call: slots passed over (probe steps beyond a site's first slot) and full column
+   compares.  With all 64 hash bits the first is about 0.3 per site at most and the second the number of sites that
+   joined a group; PLLHIP_COMPRESS_HASH_BITS=0 turns every site's walk into one chain from slot 0. */
+PLL_EXPORT void pllhip_compress_last_counts(unsigned long long * probe_steps, unsigned long long * compares);
+
 #ifdef __cplusplus
 }
 #endif

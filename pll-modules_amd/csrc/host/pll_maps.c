@@ -39,8 +39,8 @@ const pll_state_t pll_map_aa[256] = {
 
 /* Validity classes of the FASTA reader (test/src/tree/treemove-spr.c:178 and the other tree / binary test
  * programs pass it to pll_fasta_open; [libpll-2 knowledge]: 0 = illegal, reported with its line number;
- * 1 = legal sequence symbol; 2 = fatal; 3 = silently stripped white space).  The reader itself is
- * tier B3 (PLL_ERROR_NOT_IMPLEMENTED); the table exists so that those programs compile and link. */
+ * 1 = legal sequence symbol; 2 = fatal; 3 = silently stripped white space).  The readers that use it are
+ * pll_fasta_getnext and pll_phylip_load (pll_msa_io.c); the oracle keeps stubs of them and only links the table. */
 #define FA_RANGE_26(first) [first] = 1, [first + 1] = 1, [first + 2] = 1, [first + 3] = 1, [first + 4] = 1, \
   [first + 5] = 1, [first + 6] = 1, [first + 7] = 1, [first + 8] = 1, [first + 9] = 1, [first + 10] = 1,   \
   [first + 11] = 1, [first + 12] = 1, [first + 13] = 1, [first + 14] = 1, [first + 15] = 1, [first + 16] = 1, \

@@ -1,13 +1,15 @@
 /*
  * pll_notimpl.c -- tier B3 of include/pll.h: libpll-2 entry points that
  * pll-modules' NON-hot-path files (rooted trees, parsimony, sequence file
- * readers, PRNG) reference.  They are outside the scope of this engine
- * ("B3 out of scope") and exist only so that a program
- * that also links those files resolves its symbols.  Every one of them fails
+ * readers, PRNG) reference.  The rooted-tree ones are outside the scope of this
+ * engine ("B3 out of scope") and exist only so that a
+ * program that also links those files resolves its symbols.  Every stub fails
  * loudly: it sets pll_errno = PLL_ERROR_NOT_IMPLEMENTED and returns
  * NULL / PLL_FAILURE.  Nothing on the likelihood path calls them.
  * (pll_fastparsimony_init / _stepwise / _stepwise_extend / _stepwise_spr_round and pll_parsimony_destroy are
  * real in the product library: pll_parsimony.c; the stubs below are weak and stay for the oracle.)
+ * (pll_fasta_*, pll_phylip_load, pll_msa_destroy and pll_compress_site_patterns[_msa] are real in the product library as
+ * well: pll_msa_io.c and pll_compress_dev.hip; their stubs below are weak and stay for the oracle.)
  * (The SPR / NNI topology primitives that pllmod_algo_spr_round needs are real:
  * pll_utree_moves.c.)
  */
@@ -38,11 +40,12 @@ __attribute__((weak)) NI_PTR(pll_utree_t *, pll_fastparsimony_stepwise, (pll_par
 __attribute__((weak)) NI_INT(pll_fastparsimony_stepwise_extend, (pll_utree_t * t, pll_parsimony_t ** l, unsigned int c, char * const * lab, unsigned int * m, unsigned int seed, unsigned int * s))
 __attribute__((weak)) NI_INT(pll_fastparsimony_stepwise_spr_round, (pll_utree_t * t, pll_parsimony_t ** l, unsigned int c, const unsigned int * m, unsigned int seed, const int * v, unsigned int * cost))
 
-NI_PTR(pll_fasta_t *, pll_fasta_open, (const char * f, const unsigned int * m))
-NI_INT(pll_fasta_getnext, (pll_fasta_t * fd, char ** h, long * hl, char ** s, long * sl, long * no))
-NI_VOID(pll_fasta_close, (pll_fasta_t * fd))
-NI_INT(pll_fasta_rewind, (pll_fasta_t * fd))
-NI_PTR(pll_msa_t *, pll_phylip_load, (const char * f, pll_bool_t i))
-NI_VOID(pll_msa_destroy, (pll_msa_t * m))
-NI_PTR(unsigned int *, pll_compress_site_patterns, (char ** s, const pll_state_t * m, int c, int * l))
-
+/* weak: the product library links the real ones (pll_msa_io.c, pll_compress_dev.hip); the oracle keeps these */
+__attribute__((weak)) NI_PTR(pll_fasta_t *, pll_fasta_open, (const char * f, const unsigned int * m))
+__attribute__((weak)) NI_INT(pll_fasta_getnext, (pll_fasta_t * fd, char ** h, long * hl, char ** s, long * sl, long * no))
+__attribute__((weak)) NI_VOID(pll_fasta_close, (pll_fasta_t * fd))
+__attribute__((weak)) NI_INT(pll_fasta_rewind, (pll_fasta_t * fd))
+__attribute__((weak)) NI_PTR(pll_msa_t *, pll_phylip_load, (const char * f, pll_bool_t i))
+__attribute__((weak)) NI_VOID(pll_msa_destroy, (pll_msa_t * m))
+__attribute__((weak)) NI_PTR(unsigned int *, pll_compress_site_patterns, (char ** s, const pll_state_t * m, int c, int * l))
+__attribute__((weak)) NI_PTR(unsigned int *, pll_compress_site_patterns_msa, (pll_msa_t * m, const pll_state_t * map, unsigned int * spm))

@@ -120,6 +120,12 @@ class Profile(C.Structure):
                 ("algorithmic_flops", C.c_double), ("minimum_bytes", C.c_double)]
 
 
+class Msa(C.Structure):
+    """pll_msa_t"""
+    _fields_ = [("count", C.c_int), ("length", C.c_int), ("sequence", C.POINTER(C.c_void_p)),
+                ("label", C.POINTER(C.c_char_p))]
+
+
 TRAVERSE_CB = C.CFUNCTYPE(C.c_int, C.POINTER(UNode))
 REDUCE_CB = C.CFUNCTYPE(None, C.c_void_p, c_double_p, C.c_size_t, C.c_int)
 
@@ -138,7 +144,9 @@ pll_utree_graph_destroy pll_utree_clone pll_utree_reset_template_indices
 pll_utree_check_integrity pll_utree_every pll_utree_parse_newick
 pll_utree_parse_newick_unroot pll_utree_parse_newick_string
 pll_utree_parse_newick_string_unroot pll_utree_export_newick pll_utree_show_ascii
-pll_random_create pll_random_getint pll_random_destroy""".split()
+pll_random_create pll_random_getint pll_random_destroy
+pll_fasta_open pll_fasta_getnext pll_fasta_close pll_fasta_rewind pll_phylip_load pll_msa_destroy
+pll_compress_site_patterns pll_compress_site_patterns_msa""".split()
 
 PLLHIP_EVAL_H_FUNCTIONS = """pllhip_eval_create pllhip_eval_destroy pllhip_eval_set_partition
 pllhip_eval_set_parallel_context pllhip_eval_set_root pllhip_eval_root pllhip_eval_invalidate_all
@@ -161,7 +169,7 @@ pllhip_results_edge_loglikelihood pllhip_results_derivatives pllhip_results_fetc
 pllhip_eval_attach_comm pllhip_update_partials_batch pllhip_results_poison pllhip_newton_branch pllhip_repeat_stats
 pllhip_set_transient pllhip_discard_transient pllhip_transient_stats pllhip_newton_branch_multi
 pllhip_schedule_stats
-pllhip_parsimony_tree_score""".split()
+pllhip_parsimony_tree_score pllhip_compress_last_times pllhip_compress_last_counts""".split()
 
 
 def _u32(a):
@@ -170,6 +178,23 @@ def _u32(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+_libc = C.CDLL(None)
+_libc.free.argtypes = [C.c_void_p]
+_libc.free.restype = None
+
+
+def _libc_free(ptr):
+    """free() of memory the library malloc()ed for its caller"""
+    _libc.free(C.cast(ptr, C.c_void_p))
+
+
+class CompressResult:
+    """outcome of PllLib.compress_site_patterns: ok, errno, errmsg, length, rows (bytes per taxon), weights (uint32),
+    site_pattern_map (uint32 per original site; the _msa form only), probe_steps / compares (pllhip_compress_last_counts)"""
+    ok, errno, errmsg, length, rows, weights, site_pattern_map = False, 0, "", 0, None, None, None
+    probe_steps, compares = 0, 0
 
 
 class PllLib:
@@ -248,6 +273,23 @@ class PllLib:
                                                         c_uint_p, C.c_uint, c_uint_p]
         L.pll_fastparsimony_stepwise_spr_round.argtypes = [tp, C.POINTER(C.c_void_p), C.c_uint, c_uint_p, C.c_uint,
                                                            C.POINTER(C.c_int), c_uint_p]
+        mp = C.POINTER(Msa)
+        L.pll_fasta_open.restype = C.c_void_p
+        L.pll_fasta_open.argtypes = [C.c_char_p, c_uint_p]
+        L.pll_fasta_getnext.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_long), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        L.pll_fasta_close.restype = None
+        L.pll_fasta_close.argtypes = [C.c_void_p]
+        L.pll_fasta_rewind.argtypes = [C.c_void_p]
+        L.pll_phylip_load.restype = mp
+        L.pll_phylip_load.argtypes = [C.c_char_p, C.c_int]
+        L.pll_msa_destroy.restype = None
+        L.pll_msa_destroy.argtypes = [mp]
+        L.pll_compress_site_patterns.restype = c_uint_p
+        L.pll_compress_site_patterns.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.c_int,
+                                                 C.POINTER(C.c_int)]
+        L.pll_compress_site_patterns_msa.restype = c_uint_p
+        L.pll_compress_site_patterns_msa.argtypes = [mp, C.POINTER(C.c_ulonglong), c_uint_p]
         if hasattr(L, "pllhip_eval_create"):
             L.pllhip_eval_create.restype = C.c_void_p
             L.pllhip_eval_create.argtypes = [tp, C.c_uint, C.c_uint]
@@ -319,6 +361,10 @@ class PllLib:
             L.pllhip_shard_count.argtypes = [pp]
             L.pllhip_shard_count.restype = C.c_uint
             L.pllhip_parsimony_tree_score.argtypes = [C.POINTER(C.c_void_p), C.c_uint, tp, c_uint_p]
+            L.pllhip_compress_last_times.restype = None
+            L.pllhip_compress_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
+            L.pllhip_compress_last_counts.restype = None
+            L.pllhip_compress_last_counts.argtypes = [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
             L.pllhip_comm_rank.argtypes = [C.c_void_p]
             L.pllhip_comm_size.argtypes = [C.c_void_p]
             L.pllhip_eval_attach_comm.argtypes = [C.c_void_p, C.c_void_p]
@@ -359,6 +405,85 @@ class PllLib:
     @property
     def errmsg(self):
         return (C.c_char * 200).in_dll(self.lib, "pll_errmsg").value.decode(errors="replace")
+
+    # --- alignment input ----------------------------------------------------
+    def char_map(self, name):
+        """pll_map_nt / pll_map_aa / pll_map_bin (256 pll_state_t) or pll_map_fasta (256 unsigned) of the library"""
+        ctype = C.c_uint if name == "pll_map_fasta" else C.c_ulonglong
+        return (ctype * 256).in_dll(self.lib, name)
+
+    def fasta_open(self, path, status=None):
+        """pll_fasta_t * (or None, see errno); status: 256 unsigned, default pll_map_fasta"""
+        status = self.char_map("pll_map_fasta") if status is None else (C.c_uint * 256)(*[int(x) for x in status])
+        self._fasta_status = status                                   # the handle keeps the pointer
+        return self.lib.pll_fasta_open(os.fsencode(str(path)), status)
+
+    def fasta_getnext(self, fd):
+        """(head, head_len, seq, seq_len, seqno) with head / seq as bytes, or None (see errno)"""
+        head, seq = C.c_void_p(), C.c_void_p()
+        hl, sl, no = C.c_long(-1), C.c_long(-1), C.c_long(-1)
+        if not self.lib.pll_fasta_getnext(fd, C.byref(head), C.byref(hl), C.byref(seq), C.byref(sl), C.byref(no)):
+            return None
+        out = (C.string_at(head.value), hl.value, C.string_at(seq.value), sl.value, no.value)
+        _libc_free(head)
+        _libc_free(seq)
+        return out
+
+    def phylip_load(self, path, interleaved=False):
+        """pll_msa_t * (a ctypes pointer; falsy on failure, see errno); free it with lib.pll_msa_destroy"""
+        return self.lib.pll_phylip_load(os.fsencode(str(path)), 1 if interleaved else 0)
+
+    @staticmethod
+    def msa_contents(msa):
+        """(count, length, labels, sequences) of a pll_msa_t *, strings as bytes up to their NUL"""
+        m = msa.contents
+        return (m.count, m.length, [m.label[i] for i in range(m.count)],
+                [C.string_at(m.sequence[i]) for i in range(m.count)])
+
+    def compress_site_patterns(self, rows, charmap, count=None, length=None, msa_form=False, want_map=True):
+        """pll_compress_site_patterns (msa_form: pll_compress_site_patterns_msa) on a copy of `rows` ([T][L] bytes).
+        Returns a CompressResult; .ok is False when the call returned NULL."""
+        rows = [bytes(r) for r in rows]
+        T = len(rows) if count is None else count
+        L = (len(rows[0]) if rows else 0) if length is None else length
+        bufs = [C.create_string_buffer(r, len(r) + 1) for r in rows]
+        seqs = (C.c_void_p * max(1, len(bufs)))(*[C.addressof(b) for b in bufs])
+        cmap = (C.c_ulonglong * 256)(*[int(x) for x in charmap])
+        res = CompressResult()
+        self.errno = 0
+        if msa_form:
+            msa = Msa(T, L, seqs, None)
+            spm = np.full(max(L, 1), 0xffffffff, dtype=np.uint32)
+            w = self.lib.pll_compress_site_patterns_msa(C.byref(msa), cmap, spm.ctypes.data_as(c_uint_p) if want_map else None)
+            res.length = msa.length
+            res.site_pattern_map = spm[:L] if want_map else None
+        else:
+            n = C.c_int(L)
+            w = self.lib.pll_compress_site_patterns(seqs, cmap, T, C.byref(n))
+            res.length = n.value
+        res.ok = bool(w)
+        res.errno, res.errmsg = self.errno, self.errmsg
+        if res.ok:
+            res.weights = np.ctypeslib.as_array(w, shape=(res.length,)).copy()
+            _libc_free(w)
+            res.rows = [C.string_at(C.addressof(b)) for b in bufs]     # up to the NUL the call wrote
+            if self.is_product:
+                res.probe_steps, res.compares = self.compress_last_counts()
+        else:
+            res.rows = [b.raw[:-1] for b in bufs]                      # the whole buffers: must be untouched
+        return res
+
+    def compress_last_counts(self):
+        """(probe steps, full column compares) of the hash table in the last compression call"""
+        probes, compares = C.c_ulonglong(), C.c_ulonglong()
+        self.lib.pllhip_compress_last_counts(C.byref(probes), C.byref(compares))
+        return probes.value, compares.value
+
+    def compress_last_times(self):
+        """(upload, kernels, download) ms of the last compression call"""
+        up, kern, down = C.c_double(), C.c_double(), C.c_double()
+        self.lib.pllhip_compress_last_times(C.byref(up), C.byref(kern), C.byref(down))
+        return up.value, kern.value, down.value
 
     def gamma_cats(self, alpha, k, mode=PLL_GAMMA_RATES_MEAN):
         out = np.zeros(k)
