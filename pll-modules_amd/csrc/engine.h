@@ -327,12 +327,14 @@ struct Engine
   unsigned long long newton_seq = 0;
   int newton_capacity = -1;           // co-resident workgroups of the loop kernel (-1: not asked yet)
   int newton_resident = 0;            // blocks per wave that k_newton_mfma_resident keeps in registers (0: the streaming loop)
-  const void * newton_fn = nullptr;
+  const void * newton_fn = nullptr;   // the loop kernel of a partition on its own: the resident form where it fits, else the streaming one
   size_t newton_lds = 0;
   // ... and the streaming form of the same loop (several partitions under one branch length share the chip)
   const void * newton_stream_fn = nullptr;
   size_t newton_stream_lds = 0;
   int newton_stream_capacity = 0;
+  // workgroups per CU of k_newton_multi (without / with the 2 .. 32-state family; dynamic LDS up to / beyond 16 KiB)
+  int newton_multi_per_cu[2][2] = {{-1, -1}, {-1, -1}};
   hipEvent_t newton_ready = nullptr;  // the control block of a multi-partition loop is initialised
   hipEvent_t newton_done = nullptr;   // this partition's instance of the last multi-partition loop has left the device
 

@@ -449,6 +449,44 @@ static bool sum_prep_needed(Engine * e, const ParamIdx & params, bool want_lut)
   return true;
 }
 
+// The sumtable of a matrix-core family is one partials operation on eigen-basis operands: the family's k_sumtable_prep_*
+// fills the scratch area Lm | Rm | lutL | lutR (`mats` doubles per matrix block, `luts` per table) when
+// sum_prep_needed says so, and the family's partials launcher writes the table
+typedef void (*SumtablePrep)(ModelView, ParamIdx, const unsigned long long *, unsigned, bool, double *, double *, double *, double *);
+
+static int launch_sumtable_by_partials(Engine * e, const ModelView & mv, const ParamIdx & params,
+                                       const NodeRef & parent, const NodeRef & child, double * d_sum,
+                                       SumtablePrep prep, size_t mats, size_t luts,
+                                       int (*partials)(Engine * e, const OpBatch & batch, unsigned nops))
+{
+  if (!e->d_sum_scratch)
+  {
+    hipError_t err = hipMalloc(reinterpret_cast<void **>(&e->d_sum_scratch),
+                               sizeof(double) * 2 * (mats + (size_t)e->R * PLL_ASCII_SIZE * e->S));
+    if (err != hipSuccess)
+    {
+      set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc for sumtable scratch failed");
+      return PLL_FAILURE;
+    }
+  }
+  double * Lm = e->d_sum_scratch, * Rm = Lm + mats, * lutL = Rm + mats, * lutR = lutL + luts;
+  const bool want_lut = parent.codes || child.codes;
+  if (sum_prep_needed(e, params, want_lut))
+  {
+    hipLaunchKernelGGL(prep, dim3(e->R), dim3(256), 0, e->stream,
+                       mv, params, e->d_tipmap, e->lut_codes, want_lut, Lm, Rm, lutL, lutR);
+    PLLHIP_TRY(hipGetLastError());
+  }
+  OpBatch batch;
+  OpDesc & d = batch.op[0];
+  d.clv1 = parent.clv; d.codes1 = parent.codes; d.pmat1 = Lm; d.lut1 = lutL;
+  d.clv2 = child.clv;  d.codes2 = child.codes;  d.pmat2 = Rm; d.lut2 = lutR;
+  d.scaler1 = d.scaler2 = nullptr;
+  d.parent = d_sum;
+  d.parent_scaler = nullptr;
+  return partials(e, batch, 1);
+}
+
 // keep: workgroups a row keeps whatever the other rows take (the ones it needs to share a LARGE partition out
 // finely enough -- few long-lived workgroups per row leave a tail at the end of every round)
 static unsigned round_grid(const Engine * e, unsigned gx, unsigned rows, unsigned per_cu_default = 4u, unsigned keep = 0u)

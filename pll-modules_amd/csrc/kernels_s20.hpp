@@ -1860,34 +1860,8 @@ static int launch_edge_lnl_s20(Engine * e, const ModelView & mv, const ParamIdx 
 static int launch_sumtable_s20(Engine * e, const ModelView & mv, const ParamIdx & params,
                                const NodeRef & parent, const NodeRef & child, double * d_sum)
 {
-  // scratch: Lm | Rm | lutL | lutR
-  const size_t mats = (size_t)e->R * 400, luts = (size_t)e->R * std::max(1u, e->lut_codes) * 20;
-  if (!e->d_sum_scratch)
-  {
-    hipError_t err = hipMalloc(reinterpret_cast<void **>(&e->d_sum_scratch),
-                               sizeof(double) * 2 * (mats + (size_t)e->R * PLL_ASCII_SIZE * 20));
-    if (err != hipSuccess)
-    {
-      set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc for sumtable scratch failed");
-      return PLL_FAILURE;
-    }
-  }
-  double * Lm = e->d_sum_scratch, * Rm = Lm + mats, * lutL = Rm + mats, * lutR = lutL + luts;
-  const bool want_lut = parent.codes || child.codes;
-  if (sum_prep_needed(e, params, want_lut))
-  {
-    hipLaunchKernelGGL(k_sumtable_prep_s20, dim3(e->R), dim3(256), 0, e->stream,
-                       mv, params, e->d_tipmap, e->lut_codes, want_lut, Lm, Rm, lutL, lutR);
-    PLLHIP_TRY(hipGetLastError());
-  }
-  OpBatch batch;
-  OpDesc & d = batch.op[0];
-  d.clv1 = parent.clv; d.codes1 = parent.codes; d.pmat1 = Lm; d.lut1 = lutL;
-  d.clv2 = child.clv;  d.codes2 = child.codes;  d.pmat2 = Rm; d.lut2 = lutR;
-  d.scaler1 = d.scaler2 = nullptr;
-  d.parent = d_sum;
-  d.parent_scaler = nullptr;
-  return launch_partials_s20(e, batch, 1);
+  return launch_sumtable_by_partials(e, mv, params, parent, child, d_sum, k_sumtable_prep_s20, (size_t)e->R * 400,
+                                     (size_t)e->R * std::max(1u, e->lut_codes) * 20, launch_partials_s20);
 }
 
 // up to 4 trial lengths per launch (spare rows repeat the last length)

@@ -880,21 +880,6 @@ static const unsigned * scaler_ptr(const Engine * e, int idx)
   return (idx == PLL_SCALE_BUFFER_NONE) ? nullptr : e->d_scalers + (size_t)idx * e->sc_len;
 }
 
-static unsigned reduce_grid(const Engine * e)
-{
-  // generic: one thread per site; S4: one lane per (site, rate), 4 per trip;
-  // S20: one wave per 32-site block
-  unsigned long long need = ((unsigned long long)e->N + 255ULL) / 256ULL;
-  if (e->blocked) need = ((unsigned long long)e->nblk + 3ULL) / 4ULL;
-  else if (e->family == KernelFamily::S4) need = ((unsigned long long)e->N * e->R + 1023ULL) / 1024ULL;
-  // fewer, longer-lived workgroups than one per trip: their prologue (matrix / fragment loads)
-  // and the block reduction are paid less often (measured at 1 M sites: 4-state lnL 82 -> 62 us
-  // with 1024 blocks, 20-state lnL 254 -> 245 us with 2048)
-  static const unsigned env_cap = getenv("PLLHIP_REDUCE_BLOCKS") ? (unsigned)atoi(getenv("PLLHIP_REDUCE_BLOCKS")) : 0u;
-  const unsigned cap = env_cap ? env_cap : (e->family == KernelFamily::S4 ? 1024u : 2048u);
-  return (unsigned)std::max<unsigned long long>(1ULL, std::min<unsigned long long>(need, std::min(cap, (unsigned)REDUCE_BLOCKS)));
-}
-
 // --- ascertainment-bias correction on the host (same formulas as oracle/orc_kernels.c) ---------
 // from the log-likelihoods l[k] of the S constant patterns:
 //   Lewis  - W log(1 - sum_k L_k);  Felsenstein  + w log(sum_k L_k);  Stamatakis  + sum_k w_k log(L_k)
@@ -1078,27 +1063,6 @@ static int check_scaler_index(const Engine * e, int idx)
 }
 
 // ---------------------------------------------------------------------------
-// partials: level scheduling + launch
-// ---------------------------------------------------------------------------
-static int launch_partials(Engine * e, const OpBatch & batch, unsigned nops)
-{
-  switch (e->family)
-  {
-    case KernelFamily::S4:
-      return launch_partials_s4(e, batch, nops);
-    case KernelFamily::S20:
-      return launch_partials_s20(e, batch, nops);
-    case KernelFamily::S61:
-      return launch_partials_s61(e, batch, nops);
-    case KernelFamily::S16:
-      return launch_partials_s16(e, batch, nops);
-    default:
-      break;
-  }
-  return launch_partials_generic(e, batch, nops);
-}
-
-// ---------------------------------------------------------------------------
 // The families with operation chains (4 states, 2 .. 32 states, 20 states): what the schedules of
 // pll_update_partials and pllhip_update_partials_batch and the class nodes of site repeats need of one.
 // chain_family() is the one place of that path that tells the families apart.
@@ -1241,6 +1205,130 @@ static const ChainFamily * chain_family(const Engine * e)
   static const int use_chains = getenv("PLLHIP_CHAINS") ? atoi(getenv("PLLHIP_CHAINS")) : 1;
   const ChainFamily * f = family_entry(e->family);
   return use_chains && f && f->supported(e) ? f : nullptr;
+}
+
+// ---------------------------------------------------------------------------
+// The edge path (edge and root lnL, sumtable, derivatives, the device Newton-Raphson loop): what it needs of a kernel
+// family.  Every partition has an entry, the generic family included; edge_family() is the one place of this path that
+// tells the families apart.
+// ---------------------------------------------------------------------------
+static bool newton_probe_s4(Engine * e), newton_probe_s16(Engine * e), newton_probe_s20(Engine * e), newton_probe_s61(Engine * e);
+
+struct EdgeFamily
+{
+  const char * name;                                    // pllhip_partials_kernel_name
+  int (*partials)(Engine * e, const OpBatch & batch, unsigned nops);     // one level of the plain schedule
+  // lnL at an edge, and at a root vector (pm, lut null; k_edge_lnl_s4 has no root form: 4 states take the generic kernel)
+  int (*lnl)(Engine * e, const ModelView & mv, const ParamIdx & fidx, const NodeRef & parent, const NodeRef & child,
+             const double * pm, const double * lut, const unsigned * ps, const unsigned * cs, double * persite, unsigned nblocks);
+  decltype(lnl) root_lnl;
+  bool root_child_scaler;                               // the root form is handed the caller's child scaler (else none)
+  int (*sumtable)(Engine * e, const ModelView & mv, const ParamIdx & params, const NodeRef & parent, const NodeRef & child,
+                  double * d_sum);
+  int (*derivatives)(Engine * e, const ModelView & mv, const ParamIdx & params, const TrialLengths & tl, unsigned count,
+                     const double * d_sum, const unsigned * ps, const unsigned * cs, unsigned nblocks);
+  // reduce_grid(): the workgroups that have work -- one thread per site (generic), one lane per (site, rate) and 4 per
+  // trip (4 states), one wave per site block (blocked families) -- and the most that are launched
+  unsigned long long (*reduce_need)(const Engine * e);
+  unsigned reduce_cap;
+  bool scan_on_newton_grid;                             // derivative scans run on scan_grid(), not on reduce_grid()
+  // trial lengths per derivatives launch: four on the matrix cores; the others are bounded by their coefficient tables
+  // (3 x R x S doubles per length, below 48 KiB of LDS).  0: no launch carries this shape (error set)
+  unsigned (*trial_lengths)(const Engine * e);
+  // the device Newton-Raphson loop.  newton_probe fills the engine's newton_* cache once (false: HIP error; nothing is
+  // cached, unless it was the resident candidate's query that failed: the streaming loop stays); null: no loop kernel
+  // (the three newton_* entries below are null with it: newton_prepare and the newton_kind test at the top of
+  // newton_multi_one_launch turn such a partition away before anything reads them)
+  bool (*newton_probe)(Engine * e);
+  bool newton_rate_scalers;                             // ... that handles per-rate scalers
+  unsigned (*newton_ks)(const Engine * e);              // k-steps of the matrix-core loop (0: none, the 4-state loop)
+  unsigned (*newton_kind)(const Engine * e);            // NewtonMultiPart::kind
+};
+
+// LDS of the streaming matrix-core loop, and of a partition's part in k_newton_multi
+static size_t newton_table_lds(const Engine * e, unsigned ks) { return sizeof(double) * e->R * ks * 64; }
+
+static unsigned long long reduce_need_blocked(const Engine * e) { return ((unsigned long long)e->nblk + 3ULL) / 4ULL; }
+static unsigned trial_lengths_blocked(const Engine *) { return 4u; }
+
+static const EdgeFamily EDGE_GENERIC = {
+  .name = "generic", .partials = launch_partials_generic,
+  .lnl = launch_edge_lnl_generic, .root_lnl = launch_edge_lnl_generic, .root_child_scaler = false,
+  .sumtable = launch_sumtable_generic, .derivatives = launch_derivatives_generic,
+  .reduce_need = [](const Engine * e) { return ((unsigned long long)e->N + 255ULL) / 256ULL; }, .reduce_cap = 2048,
+  .scan_on_newton_grid = false,
+  .trial_lengths = [](const Engine * e)
+  {
+    unsigned kmax = MAX_TRIAL_LENGTHS;
+    while (kmax > 1 && (size_t)3 * kmax * e->R * e->S * sizeof(double) > 48 * 1024) kmax >>= 1;
+    if ((size_t)3 * e->R * e->S * sizeof(double) <= 64 * 1024) return kmax;
+    set_error(PLL_ERROR_PARAM_INVALID, "derivatives: %u rates x %u states exceed the LDS tables", e->R, e->S);
+    return 0u;
+  },
+  .newton_probe = nullptr, .newton_rate_scalers = false, .newton_ks = nullptr, .newton_kind = nullptr,
+};
+
+static const EdgeFamily EDGE_S4 = {
+  .name = "s4-valu", .partials = launch_partials_s4,
+  .lnl = launch_edge_lnl_s4, .root_lnl = launch_edge_lnl_generic, .root_child_scaler = false,
+  .sumtable = launch_sumtable_s4, .derivatives = launch_derivatives_s4,
+  .reduce_need = [](const Engine * e) { return ((unsigned long long)e->N * e->R + 1023ULL) / 1024ULL; }, .reduce_cap = 1024,
+  .scan_on_newton_grid = true, .trial_lengths = [](const Engine *) { return MAX_TRIAL_LENGTHS; },
+  .newton_probe = newton_probe_s4, .newton_rate_scalers = false, .newton_ks = [](const Engine *) { return 0u; },
+  .newton_kind = [](const Engine *) { return NEWTON_KIND_S4; },
+};
+
+static const EdgeFamily EDGE_S16 = {
+  .name = "s16-mfma",
+  .partials = [](Engine * e, const OpBatch & batch, unsigned nops) { return launch_partials_s16(e, batch, nops); },
+  .lnl = launch_edge_lnl_s16, .root_lnl = launch_edge_lnl_s16, .root_child_scaler = false,
+  .sumtable = launch_sumtable_s16, .derivatives = launch_derivatives_s16,
+  .reduce_need = reduce_need_blocked, .reduce_cap = 2048, .scan_on_newton_grid = true, .trial_lengths = trial_lengths_blocked,
+  .newton_probe = newton_probe_s16, .newton_rate_scalers = true, .newton_ks = s16_ks,
+  .newton_kind = [](const Engine * e) { return NEWTON_KIND_S16 + s16_ks(e) - 1; },
+};
+
+static const EdgeFamily EDGE_S20 = {
+  .name = "s20-mfma", .partials = launch_partials_s20,
+  .lnl = launch_edge_lnl_s20, .root_lnl = launch_edge_lnl_s20, .root_child_scaler = true,
+  .sumtable = launch_sumtable_s20, .derivatives = launch_derivatives_s20,
+  .reduce_need = reduce_need_blocked, .reduce_cap = 2048, .scan_on_newton_grid = true, .trial_lengths = trial_lengths_blocked,
+  .newton_probe = newton_probe_s20, .newton_rate_scalers = true, .newton_ks = [](const Engine *) { return 5u; },
+  .newton_kind = [](const Engine *) { return NEWTON_KIND_S20; },
+};
+
+static const EdgeFamily EDGE_S61 = {
+  .name = "s61-mfma", .partials = launch_partials_s61,
+  .lnl = launch_edge_lnl_s61, .root_lnl = launch_edge_lnl_s61, .root_child_scaler = true,
+  .sumtable = launch_sumtable_s61, .derivatives = launch_derivatives_s61,
+  .reduce_need = reduce_need_blocked, .reduce_cap = 2048, .scan_on_newton_grid = true, .trial_lengths = trial_lengths_blocked,
+  .newton_probe = newton_probe_s61, .newton_rate_scalers = true, .newton_ks = [](const Engine *) { return S61_KS; },
+  .newton_kind = [](const Engine * e) { return e->S == S61_S ? NEWTON_KIND_S61 : NEWTON_KIND_S61_RT; },
+};
+
+static const EdgeFamily * edge_family(const Engine * e)
+{
+  switch (e->family)
+  {
+    case KernelFamily::S4: return &EDGE_S4;
+    case KernelFamily::S16: return &EDGE_S16;
+    case KernelFamily::S20: return &EDGE_S20;
+    case KernelFamily::S61: return &EDGE_S61;
+    default: return &EDGE_GENERIC;
+  }
+}
+
+static int launch_partials(Engine * e, const OpBatch & batch, unsigned nops) { return edge_family(e)->partials(e, batch, nops); }
+
+static unsigned reduce_grid(const Engine * e)
+{
+  const EdgeFamily * f = edge_family(e);
+  // fewer, longer-lived workgroups than one per trip: their prologue (matrix / fragment loads)
+  // and the block reduction are paid less often (measured at 1 M sites: 4-state lnL 82 -> 62 us
+  // with 1024 blocks, 20-state lnL 254 -> 245 us with 2048)
+  static const unsigned env_cap = getenv("PLLHIP_REDUCE_BLOCKS") ? (unsigned)atoi(getenv("PLLHIP_REDUCE_BLOCKS")) : 0u;
+  const unsigned cap = env_cap ? env_cap : f->reduce_cap;
+  return (unsigned)std::max<unsigned long long>(1ULL, std::min<unsigned long long>(f->reduce_need(e), std::min(cap, (unsigned)REDUCE_BLOCKS)));
 }
 
 // a tip that is read through byte codes and the partition's lookup tables (PLL_ATTRIB_PATTERN_TIP); without the
@@ -3362,25 +3450,11 @@ double loglikelihood_impl(pll_partition_t * p, unsigned pc, int psc, unsigned cc
     pm = e->d_pmat + (size_t)matrix_index * e->R * e->S * e->Sp;
     if (child.codes) lut = e->d_lut + (size_t)matrix_index * e->R * e->lut_codes * e->S;
   }
-  int rc;
-  if (e->family == KernelFamily::S4 && matrix_index >= 0)
-    rc = launch_edge_lnl_s4(e, mv, fidx, parent, child, pm, lut, scaler_ptr(e, psc), scaler_ptr(e, csc),
-                            persite_lnl ? e->d_persite : nullptr, nblocks);
-  else if (e->family == KernelFamily::S20)
-    rc = launch_edge_lnl_s20(e, mv, fidx, parent, child, pm, lut, scaler_ptr(e, psc), scaler_ptr(e, csc),
-                             persite_lnl ? e->d_persite : nullptr, nblocks);
-  else if (e->family == KernelFamily::S61)
-    rc = launch_edge_lnl_s61(e, mv, fidx, parent, child, pm, lut, scaler_ptr(e, psc), scaler_ptr(e, csc),
-                             persite_lnl ? e->d_persite : nullptr, nblocks);
-  else if (e->family == KernelFamily::S16)
-    rc = launch_edge_lnl_s16(e, mv, fidx, parent, child, pm, lut, scaler_ptr(e, psc),
-                             (matrix_index >= 0) ? scaler_ptr(e, csc) : nullptr,
-                             persite_lnl ? e->d_persite : nullptr, nblocks);
-  else
-    rc = launch_edge_lnl_generic(e, mv, fidx, parent, child, pm, lut, scaler_ptr(e, psc),
-                                 (matrix_index >= 0) ? scaler_ptr(e, csc) : nullptr,
-                                 persite_lnl ? e->d_persite : nullptr, nblocks);
-  if (!rc) return fail;
+  const EdgeFamily * f = edge_family(e);
+  const bool edge = matrix_index >= 0;
+  if (!(edge ? f->lnl : f->root_lnl)(e, mv, fidx, parent, child, pm, lut, scaler_ptr(e, psc),
+                                      (edge || f->root_child_scaler) ? scaler_ptr(e, csc) : nullptr,
+                                      persite_lnl ? e->d_persite : nullptr, nblocks)) return fail;
   double total = 0.0;
   e->counters.lnl_calls++;
   if (deferred)
@@ -3414,127 +3488,118 @@ double loglikelihood_impl(pll_partition_t * p, unsigned pc, int psc, unsigned cc
   return total;
 }
 
-// the loop kernel of pllhip_newton_branch for this partition's family, its LDS, and how many of its workgroups
-// the chip holds at once (-1: HIP error).  derivatives_impl sizes its scan grid with the same number, so that the
-// device loop and the host loop add the same block totals in the same order.
-static int newton_capacity(Engine * e, const void ** fn_out, size_t * lds_out)
+// PLLHIP_NEWTON_RESIDENT=0: no loop keeps the sumtable in registers
+static bool newton_resident_enabled()
 {
-  if (e->family == KernelFamily::S4)
+  static const int env_res = getenv("PLLHIP_NEWTON_RESIDENT") ? atoi(getenv("PLLHIP_NEWTON_RESIDENT")) : 1;
+  return env_res != 0;
+}
+
+// 4 states (kernels_newton_s4.hpp): the loop with the table in registers when a thread has at most two trips on the grid
+// that variant can hold at once; otherwise the host loop (capacity 0: a streaming loop in one launch measured no faster
+// than one blocking call per iterate -- 59.3 against 57.7 us all-in at 1 M sites)
+static bool newton_probe_s4(Engine * e)
+{
+  const void * fn2 = reinterpret_cast<const void *>(k_newton_s4<2>);
+  int cu2 = 0;
+  if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cu2, fn2, 256, 0), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
+    return false;
+  const unsigned cap2 = (unsigned)std::max(0, cu2) * e->cu_count;
+  const unsigned long long limit = ((unsigned long long)e->N * e->R + 63ULL) & ~63ULL;
+  // (the grid the loop is launched on: scan_grid() = the reduction grid, at most four workgroups per CU and at
+  // most what the chip holds at once)
+  const unsigned g2 = std::min({reduce_grid(e), 4u * e->cu_count, cap2});
+  const bool resident = newton_resident_enabled() && g2 && (limit + 1024ULL * g2 - 1) / (1024ULL * g2) <= 2;
+  e->newton_resident = resident ? 2 : 0;
+  // (newton_prepare takes the stream fields for a loop over several partitions: at 4 states that form is this one)
+  e->newton_fn = e->newton_stream_fn = fn2;
+  e->newton_lds = e->newton_stream_lds = 0;
+  e->newton_capacity = e->newton_stream_capacity = resident ? (int)cap2 : 0;
+  return true;
+}
+
+// the register-resident form of a matrix-core loop: `nb` site blocks per wave, its LDS beyond the streaming loop's
+struct NewtonResident { const void * fn; unsigned nb; size_t extra_lds; };
+
+// the matrix cores: the streaming loop `fn` at `ks` k-steps, and the family's register-resident candidate
+static bool newton_probe_mfma(Engine * e, unsigned ks, const void * fn, const NewtonResident & res)
+{
+  const size_t lds = newton_table_lds(e, ks);
+  e->newton_resident = 0;
+  e->newton_fn = fn;
+  e->newton_lds = lds;
+  if (lds > 160 * 1024 - 512) { e->newton_capacity = 0; return true; }
+  if (lds > 64 * 1024 && !hip_ok(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512), "hipFuncSetAttribute"))
+    return false;
+  int per_cu = 0;
+  if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
+    return false;
+  e->newton_capacity = std::max(0, per_cu) * (int)e->cu_count;
+  e->newton_stream_fn = fn;
+  e->newton_stream_lds = lds;
+  e->newton_stream_capacity = e->newton_capacity;
+  // Does the sumtable fit the registers of the waves of ONE co-resident grid (k_newton_mfma_resident)?  Then that
+  // grid is the scan grid of this partition -- for the single scans of derivatives_impl as well, so that both
+  // add the same block totals in the same order.
+  if (!newton_resident_enabled() || !res.fn || e->R != 4 || e->rate_scalers || lds > 64 * 1024) return true;
+  const size_t res_lds = lds + res.extra_lds;
+  int res_cu = 0;
+  if (res_lds > 64 * 1024 && !hip_ok(hipFuncSetAttribute(res.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)res_lds), "hipFuncSetAttribute"))
+    return false;
+  if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&res_cu, res.fn, 256, res_lds), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
+    return false;
+  const unsigned cap_res = (unsigned)std::max(0, res_cu) * e->cu_count;
+  const unsigned g = std::min({reduce_grid(e), 4u * e->cu_count, cap_res});
+  if (g && (unsigned long long)e->nblk <= (unsigned long long)res.nb * 4u * g)
   {
-    // 4 states (kernels_newton_s4.hpp): the loop with the table in registers when a thread has at most two trips
-    // on the grid that variant can hold at once; otherwise the host loop (capacity 0: a streaming loop in one
-    // launch measured no faster than one blocking call per iterate -- 59.3 against 57.7 us all-in at 1 M sites)
-    if (e->newton_capacity < 0)
-    {
-      static const int env_res = getenv("PLLHIP_NEWTON_RESIDENT") ? atoi(getenv("PLLHIP_NEWTON_RESIDENT")) : 1;
-      const void * fn2 = reinterpret_cast<const void *>(k_newton_s4<2>);
-      int cu2 = 0;
-      if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&cu2, fn2, 256, 0), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
-        return -1;
-      const unsigned cap2 = (unsigned)std::max(0, cu2) * e->cu_count;
-      const unsigned long long limit = ((unsigned long long)e->N * e->R + 63ULL) & ~63ULL;
-      // (the grid the loop is launched on: scan_grid() = the reduction grid, at most four workgroups per CU and at
-      // most what the chip holds at once)
-      const unsigned g2 = std::min({reduce_grid(e), 4u * e->cu_count, cap2});
-      const bool resident = env_res && g2 && (limit + 1024ULL * g2 - 1) / (1024ULL * g2) <= 2;
-      e->newton_resident = resident ? 2 : 0;
-      e->newton_fn = fn2;
-      e->newton_lds = 0;
-      e->newton_capacity = resident ? (int)cap2 : 0;
-    }
-    if (fn_out) *fn_out = e->newton_fn;
-    if (lds_out) *lds_out = 0;
-    return e->newton_capacity;
+    e->newton_resident = (int)res.nb;
+    e->newton_fn = res.fn;
+    e->newton_lds = res_lds;
+    e->newton_capacity = (int)cap_res;
   }
-  const unsigned ks = e->family == KernelFamily::S20 ? 5u : e->family == KernelFamily::S61 ? S61_KS : s16_ks(e);
-  const size_t lds = sizeof(double) * e->R * ks * 64;
+  return true;
+}
+
+static bool newton_probe_s20(Engine * e)
+{
+  return newton_probe_mfma(e, 5, reinterpret_cast<const void *>(k_newton_mfma<5, 20>),
+                           {reinterpret_cast<const void *>(k_newton_mfma_resident<5, 20, 4, 3>), 4, sizeof(double2) * 4 * 4 * 5 * 64});
+}
+
+static bool newton_probe_s61(Engine * e)
+{
+  if (e->S == S61_S)
+    return newton_probe_mfma(e, S61_KS, reinterpret_cast<const void *>(k_newton_mfma<S61_KS, S61_S>),
+                             {reinterpret_cast<const void *>(k_newton_mfma_resident<S61_KS, S61_S, 1, 1>), 1, 0});
+  return newton_probe_mfma(e, S61_KS, reinterpret_cast<const void *>(k_newton_mfma<S61_KS, 0>),
+                           {reinterpret_cast<const void *>(k_newton_mfma_resident<S61_KS, 0, 1, 1>), 1, 0});
+}
+
+// 2 .. 32 states: site blocks that k_newton_mfma_resident keeps in registers at KS k-steps -- as many as ~240 registers
+// hold (16 KS per block) --, one more in LDS
+constexpr unsigned S16_RESIDENT_BLOCKS[9] = {0, 7, 7, 5, 3, 3, 2, 2, 1};
+
+static bool newton_probe_s16(Engine * e)
+{
   const void * fn = nullptr;
-#define PLLHIP_PICK(KK, SS) fn = reinterpret_cast<const void *>(k_newton_mfma<KK, SS>)
-  if (e->family == KernelFamily::S20) PLLHIP_PICK(5, 20);
-  else if (e->family == KernelFamily::S61) { if (e->S == S61_S) PLLHIP_PICK(S61_KS, S61_S); else PLLHIP_PICK(S61_KS, 0); }
-  else
-    switch (ks)
-    {
-      case 1: PLLHIP_PICK(1, 0); break;
-      case 2: PLLHIP_PICK(2, 0); break;
-      case 3: PLLHIP_PICK(3, 0); break;
-      case 4: PLLHIP_PICK(4, 0); break;
-      case 5: PLLHIP_PICK(5, 0); break;
-      case 6: PLLHIP_PICK(6, 0); break;
-      case 7: PLLHIP_PICK(7, 0); break;
-      default: PLLHIP_PICK(8, 0); break;
-    }
-#undef PLLHIP_PICK
-  if (lds_out) *lds_out = lds;
-  if (e->newton_capacity < 0)
-  {
-    if (lds > 160 * 1024 - 512) { e->newton_capacity = 0; return 0; }
-    if (lds > 64 * 1024 && !hip_ok(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512), "hipFuncSetAttribute"))
-      return -1;
-    int per_cu = 0;
-    if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
-      return -1;
-    e->newton_capacity = std::max(0, per_cu) * (int)e->cu_count;
-    e->newton_stream_fn = fn;
-    e->newton_stream_lds = lds;
-    e->newton_stream_capacity = e->newton_capacity;
-    // Does the sumtable fit the registers of the waves of ONE co-resident grid (k_newton_mfma_resident)?  Then that
-    // grid is the scan grid of this partition -- for the single scans of derivatives_impl as well, so that both
-    // add the same block totals in the same order.
-    static const int env_res = getenv("PLLHIP_NEWTON_RESIDENT") ? atoi(getenv("PLLHIP_NEWTON_RESIDENT")) : 1;
-    e->newton_resident = 0;
-    e->newton_fn = nullptr;
-    const void * rfn = nullptr;
-    unsigned nb = 0;
-    size_t res_lds = lds;
-    if (env_res && e->R == 4 && !e->rate_scalers && lds <= 64 * 1024)
-    {
-      if (e->family == KernelFamily::S20) { rfn = reinterpret_cast<const void *>(k_newton_mfma_resident<5, 20, 4, 3>); nb = 4; res_lds = lds + sizeof(double2) * 4 * 4 * 5 * 64; }
-      else if (e->family == KernelFamily::S61)
-      {
-        rfn = e->S == S61_S ? reinterpret_cast<const void *>(k_newton_mfma_resident<S61_KS, S61_S, 1, 1>)
-                            : reinterpret_cast<const void *>(k_newton_mfma_resident<S61_KS, 0, 1, 1>);
-        nb = 1;
-      }
-      else if (e->family == KernelFamily::S16)
-      {
-        // 2 .. 32 states: as many blocks in registers as ~240 of them hold (16 KS per block), one more in LDS
-#define PLLHIP_RES(KK, NBR) do { rfn = reinterpret_cast<const void *>(k_newton_mfma_resident<KK, 0, NBR + 1, NBR>); nb = NBR + 1; \
-                                 res_lds = lds + sizeof(double2) * 4 * 4 * KK * 64; } while (0)
-        switch (ks)
-        {
-          case 1: PLLHIP_RES(1, 7); break;
-          case 2: PLLHIP_RES(2, 7); break;
-          case 3: PLLHIP_RES(3, 5); break;
-          case 4: PLLHIP_RES(4, 3); break;
-          case 5: PLLHIP_RES(5, 3); break;
-          case 6: PLLHIP_RES(6, 2); break;
-          case 7: PLLHIP_RES(7, 2); break;
-          default: PLLHIP_RES(8, 1); break;
-        }
-#undef PLLHIP_RES
-      }
-    }
-    if (rfn)
-    {
-      int res_cu = 0;
-      if (res_lds > 64 * 1024 && !hip_ok(hipFuncSetAttribute(rfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)res_lds), "hipFuncSetAttribute"))
-        return -1;
-      if (!hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&res_cu, rfn, 256, res_lds), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
-        return -1;
-      const unsigned cap_res = (unsigned)std::max(0, res_cu) * e->cu_count;
-      const unsigned g = std::min({reduce_grid(e), 4u * e->cu_count, cap_res});
-      if (g && (unsigned long long)e->nblk <= (unsigned long long)nb * 4u * g)
-      {
-        e->newton_resident = (int)nb;
-        e->newton_fn = rfn;
-        e->newton_lds = res_lds;
-        e->newton_capacity = (int)cap_res;
-      }
-    }
-  }
-  if (fn_out) *fn_out = e->newton_resident ? e->newton_fn : fn;
-  if (lds_out && e->newton_resident) *lds_out = e->newton_lds;
+  NewtonResident res = {nullptr, 0, 0};
+#define PLLHIP_STREAMING(KK) fn = reinterpret_cast<const void *>(k_newton_mfma<KK, 0>)
+#define PLLHIP_RESIDENT(KK) \
+  res = {reinterpret_cast<const void *>(k_newton_mfma_resident<KK, 0, S16_RESIDENT_BLOCKS[KK] + 1, S16_RESIDENT_BLOCKS[KK]>), \
+         S16_RESIDENT_BLOCKS[KK] + 1, sizeof(double2) * 4 * 4 * KK * 64}
+  PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_STREAMING);
+  PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_RESIDENT);
+#undef PLLHIP_STREAMING
+#undef PLLHIP_RESIDENT
+  return newton_probe_mfma(e, s16_ks(e), fn, res);
+}
+
+// how many workgroups of the family's loop kernel (Engine::newton_fn, newton_lds) the chip holds at once (-1: HIP error).
+// derivatives_impl sizes its scan grid with the same number, so that the device loop and the host loop add the same
+// block totals in the same order.
+static int newton_capacity(Engine * e)
+{
+  if (e->newton_capacity < 0 && !edge_family(e)->newton_probe(e)) return -1;
   return e->newton_capacity;
 }
 
@@ -3544,7 +3609,7 @@ static int newton_capacity(Engine * e, const void ** fn_out, size_t * lds_out)
 static unsigned scan_grid(Engine * e)
 {
   unsigned nblocks = std::min(reduce_grid(e), 4u * e->cu_count);
-  const int cap = newton_capacity(e, nullptr, nullptr);
+  const int cap = newton_capacity(e);
   if (cap > 0) nblocks = std::min(nblocks, (unsigned)cap);
   return nblocks;
 }
@@ -3574,22 +3639,12 @@ int derivatives_impl(pll_partition_t * p, int parent_scaler_index, int child_sca
   }
   if (!sync_model(p) || !ensure_invariant(p)) return PLL_FAILURE;
   if (!need_scaler(e, parent_scaler_index) || !need_scaler(e, child_scaler_index)) return PLL_FAILURE;
-  const unsigned nblocks = (e->blocked || e->family == KernelFamily::S4) ? scan_grid(e) : reduce_grid(e);
+  const EdgeFamily * f = edge_family(e);
+  const unsigned nblocks = f->scan_on_newton_grid ? scan_grid(e) : reduce_grid(e);
   const ModelView mv = model_view(e);
   const ParamIdx params = make_params(p, params_indices);
-  // lengths per launch: the matrix-core kernel (20 / 61 states) takes four; the others are
-  // bounded by their coefficient tables (3 x R x S doubles per length, below 48 KiB of LDS)
-  unsigned kmax = MAX_TRIAL_LENGTHS;
-  if (e->blocked) kmax = 4;
-  else if (e->family != KernelFamily::S4)
-  {
-    while (kmax > 1 && (size_t)3 * kmax * e->R * e->S * sizeof(double) > 48 * 1024) kmax >>= 1;
-    if ((size_t)3 * e->R * e->S * sizeof(double) > 64 * 1024)
-    {
-      set_error(PLL_ERROR_PARAM_INVALID, "derivatives: %u rates x %u states exceed the LDS tables", e->R, e->S);
-      return PLL_FAILURE;
-    }
-  }
+  const unsigned kmax = f->trial_lengths(e);
+  if (!kmax) return PLL_FAILURE;
   const bool asc = e->N > e->Nreal;
   if (asc && deferred)
   {
@@ -3619,18 +3674,8 @@ int derivatives_impl(pll_partition_t * p, int parent_scaler_index, int child_sca
     e->sink.nq = 2 * nb;
     if (first + nb < count) e->sink.flag = nullptr;     // the last launch tells the host
     const unsigned * ps = scaler_ptr(e, parent_scaler_index), * cs = scaler_ptr(e, child_scaler_index);
-    int rc;
-    if (e->family == KernelFamily::S4)
-      rc = launch_derivatives_s4(e, mv, params, tl, nb, d_sum, ps, cs, nblocks);
-    else if (e->family == KernelFamily::S20)
-      rc = launch_derivatives_s20(e, mv, params, tl, nb, d_sum, ps, cs, nblocks);
-    else if (e->family == KernelFamily::S61)
-      rc = launch_derivatives_s61(e, mv, params, tl, nb, d_sum, ps, cs, nblocks);
-    else if (e->family == KernelFamily::S16)
-      rc = launch_derivatives_s16(e, mv, params, tl, nb, d_sum, ps, cs, nblocks);
-    else
-      rc = launch_derivatives_generic(e, mv, params, tl, nb, d_sum, ps, cs, nblocks);
-    if (!rc || !finish_launch(e, nblocks, e->blocked ? 8 : 2 * trial_instance(nb))) return PLL_FAILURE;
+    if (!f->derivatives(e, mv, params, tl, nb, d_sum, ps, cs, nblocks) ||
+        !finish_launch(e, nblocks, e->blocked ? 8 : 2 * trial_instance(nb))) return PLL_FAILURE;
   }
   e->counters.derivative_calls++;
   e->counters.derivative_points += count;
@@ -3714,17 +3759,7 @@ int pll_update_sumtable(pll_partition_t * p,
   const ModelView mv = model_view(e);
   const ParamIdx params = make_params(p, params_indices);
   const NodeRef parent = node_ref(e, parent_clv_index), child = node_ref(e, child_clv_index);
-  int rc;
-  if (e->family == KernelFamily::S4)
-    rc = launch_sumtable_s4(e, mv, params, parent, child, d_sum);
-  else if (e->family == KernelFamily::S20)
-    rc = launch_sumtable_s20(e, mv, params, parent, child, d_sum);
-  else if (e->family == KernelFamily::S61)
-    rc = launch_sumtable_s61(e, mv, params, parent, child, d_sum);
-  else if (e->family == KernelFamily::S16)
-    rc = launch_sumtable_s16(e, mv, params, parent, child, d_sum);
-  else
-    rc = launch_sumtable_generic(e, mv, params, parent, child, d_sum);
+  const int rc = edge_family(e)->sumtable(e, mv, params, parent, child, d_sum);
   e->counters.sumtable_calls++;
   return rc;
 }
@@ -3768,8 +3803,8 @@ static int newton_prepare(pll_partition_t * p, int parent_scaler_index, int chil
 {
   Engine * e = engine_of(p);
   static const int enabled = getenv("PLLHIP_DEVICE_NEWTON") ? atoi(getenv("PLLHIP_DEVICE_NEWTON")) : 1;
-  const bool family_ok = e->family == KernelFamily::S20 || e->family == KernelFamily::S16 || e->family == KernelFamily::S61 ||
-                         (e->family == KernelFamily::S4 && !e->rate_scalers);
+  const EdgeFamily * f = edge_family(e);
+  const bool family_ok = f->newton_probe && (f->newton_rate_scalers || !e->rate_scalers);
   if (!enabled || !e->shards.empty() || !family_ok || e->N > e->Nreal || !e->fused_finish)
   {
     set_error(PLLHIP_ERROR_NEWTON_UNSUPPORTED, "this partition does not run the Newton-Raphson loop on the device");
@@ -3788,9 +3823,11 @@ static int newton_prepare(pll_partition_t * p, int parent_scaler_index, int chil
   if (!need_scaler(e, parent_scaler_index) || !need_scaler(e, child_scaler_index)) return PLL_FAILURE;
   // the scan's own grid (derivatives_impl): the block totals, and with them every bit of the sums, are the same
   L.nblocks = scan_grid(e);
-  int capacity = newton_capacity(e, &L.fn, &L.lds);
+  int capacity = newton_capacity(e);
   if (capacity < 0) return PLL_FAILURE;
-  if (!resident && e->newton_resident && e->family != KernelFamily::S4)
+  L.fn = e->newton_fn;
+  L.lds = e->newton_lds;
+  if (!resident && e->newton_resident)
   {
     L.fn = e->newton_stream_fn;
     L.lds = e->newton_stream_lds;
@@ -3835,7 +3872,7 @@ static int newton_launch(const NewtonLaunch & L, const NewtonParams & np_, Newto
   ro.fused = 1;
   ro.nq = 2;
   unsigned rs = e->rate_scalers ? 1u : 0u;
-  if (e->family == KernelFamily::S4)
+  if (!e->blocked)        // the 4-state loop: no site blocks and no per-rate scalers in its argument list
   {
     void * args4[] = {(void *)&L.mv, (void *)&L.params, (void *)&np, (void *)&L.d_sum, (void *)&L.ps, (void *)&L.cs,
                       (void *)&e->d_weights, (void *)&e->d_invariant, (void *)&e->N, (void *)&e->R,
@@ -3875,6 +3912,31 @@ static NewtonParams newton_params(double start, double bl_min, double bl_max, do
   np.debug = getenv("PLLHIP_NEWTON_DEBUG") ? 1u : 0u;
   np.iter_base = 0;
   return np;
+}
+
+// what the launches of one loop share: the control block in the lead partition's device memory, where the results go
+struct NewtonRun { NewtonControl * ctl; double * host_out; unsigned long long * host_flag; unsigned long long seq; };
+
+// Starts a loop on `lead`, on whose stream the caller has ordered everything that used the control block before.  The
+// block is initialised from the kernel arguments -- NewtonParams::iter_base, this loop's own range of `iter` values --;
+// with PLLHIP_NEWTON_DEBUG the counters of the dump are reset by a copy (pageable source, staged by the runtime before
+// the call returns).  nscales partitions with length_scalers (null: 1.0); 0: a loop of one partition, its scale in np.
+static int newton_begin(Engine * lead, NewtonParams & np, const double * length_scalers, unsigned nscales, NewtonRun & run)
+{
+  run.ctl = static_cast<NewtonControl *>(lead->d_newton);
+  run.seq = ++lead->newton_seq;
+  np.iter_base = (unsigned)(run.seq << 8);
+  if (np.debug)
+  {
+    NewtonControl init;
+    memset(&init, 0, sizeof(init));
+    init.x = np.x0; init.xl = np.bl_min; init.xh = np.bl_max; init.iter = 0; init.status = NEWTON_RUNNING;
+    for (unsigned k = 0; k < nscales; ++k) init.pscale[k] = length_scalers ? length_scalers[k] : 1.0;
+    PLLHIP_TRY(hipMemcpyAsync(run.ctl, &init, sizeof(init), hipMemcpyHostToDevice, lead->stream));
+  }
+  run.host_out = lead->hd_newton;
+  run.host_flag = reinterpret_cast<unsigned long long *>(lead->hd_newton + 112);
+  return PLL_SUCCESS;
 }
 
 // wait for the loop that `lead` hosts and translate how it ended; `all`: every engine that took part
@@ -3949,19 +4011,11 @@ int pllhip_newton_branch(pll_partition_t * p, int parent_scaler_index, int child
   NewtonLaunch L;
   if (!newton_prepare(p, parent_scaler_index, child_scaler_index, params_indices, sumtable, true, L)) return PLL_FAILURE;
   Engine * e = L.e;
-  const NewtonParams np = newton_params(start, bl_min, bl_max, tolerance, max_newton, L.nblocks);
-  NewtonControl init;
-  memset(&init, 0, sizeof(init));
-  init.x = np.x0; init.xl = bl_min; init.xh = bl_max; init.iter = 0; init.status = NEWTON_RUNNING;
-  NewtonControl * ctl = static_cast<NewtonControl *>(e->d_newton);
-  // (the control block is initialised from the kernel arguments -- NewtonParams::iter_base --; with PLLHIP_NEWTON_DEBUG
-  // the counters of the dump are reset by a copy: pageable source, staged by the runtime before the call returns)
-  const unsigned long long seq = ++e->newton_seq;
-  NewtonParams np1 = np;
-  np1.iter_base = (unsigned)(seq << 8);
-  if (np1.debug) PLLHIP_TRY(hipMemcpyAsync(ctl, &init, sizeof(init), hipMemcpyHostToDevice, e->stream));
-  if (!newton_launch(L, np1, ctl, e->hd_newton, reinterpret_cast<unsigned long long *>(e->hd_newton + 112), seq)) return PLL_FAILURE;
-  return newton_finish(e, std::vector<Engine *>(1, e), seq, length, iterations, trail);
+  NewtonParams np = newton_params(start, bl_min, bl_max, tolerance, max_newton, L.nblocks);
+  NewtonRun run;
+  if (!newton_begin(e, np, nullptr, 0, run)) return PLL_FAILURE;
+  if (!newton_launch(L, np, run.ctl, run.host_out, run.host_flag, run.seq)) return PLL_FAILURE;
+  return newton_finish(e, std::vector<Engine *>(1, e), run.seq, length, iterations, trail);
 }
 
 // The loop over several partitions runs one launch per partition, each on its partition's stream, and the launches wait
@@ -3989,11 +4043,7 @@ static int newton_multi_one_launch(pll_partition_t * const * partitions, unsigne
   static const int enabled = getenv("PLLHIP_NEWTON_ONE_LAUNCH") ? atoi(getenv("PLLHIP_NEWTON_ONE_LAUNCH")) : 1;
   if (!enabled) return -1;
   for (unsigned k = 0; k < count; ++k)
-  {
-    const Engine * e = engine_of(partitions[k]);
-    if (e->family != KernelFamily::S4 && e->family != KernelFamily::S20 && e->family != KernelFamily::S61 &&
-        e->family != KernelFamily::S16) return -1;
-  }
+    if (!edge_family(engine_of(partitions[k]))->newton_kind) return -1;
   std::vector<NewtonLaunch> L(count);
   NewtonMultiArgs args;
   memset(&args, 0, sizeof(args));
@@ -4018,23 +4068,19 @@ static int newton_multi_one_launch(pll_partition_t * const * partitions, unsigne
     P.ro.flag = nullptr; P.ro.seq = 0; P.ro.fused = 1; P.ro.nq = 2;
     P.xscale = length_scalers ? length_scalers[k] : 1.0;
     P.N = e->N; P.nblk = e->nblk; P.R = e->R; P.rate_scalers = e->rate_scalers ? 1u : 0u;
-    P.kind = e->family == KernelFamily::S4 ? NEWTON_KIND_S4 : e->family == KernelFamily::S20 ? NEWTON_KIND_S20
-           : e->family == KernelFamily::S16 ? NEWTON_KIND_S16 + s16_ks(e) - 1
-           : e->S == S61_S ? NEWTON_KIND_S61 : NEWTON_KIND_S61_RT;
+    P.kind = edge_family(e)->newton_kind(e);
     P.first_block = total; P.nblocks = L[k].nblocks;
     total += L[k].nblocks;
-    if (e->family != KernelFamily::S4)
-      lds = std::max(lds, sizeof(double) * e->R * (e->family == KernelFamily::S20 ? 5u : e->family == KernelFamily::S16 ? s16_ks(e) : S61_KS) * 64);
+    lds = std::max(lds, newton_table_lds(e, edge_family(e)->newton_ks(e)));
   }
   Engine * lead = L[0].e;
   PLLHIP_TRY(hipSetDevice(lead->device));
   if (lds > 64 * 1024) return -1;
   // every workgroup waits for the others inside the launch: all of them on the chip at once
   bool any16 = false;
-  for (unsigned k = 0; k < count; ++k) any16 = any16 || L[k].e->family == KernelFamily::S16;
+  for (unsigned k = 0; k < count; ++k) any16 = any16 || args.part[k].kind >= NEWTON_KIND_S16;
   const void * fn = any16 ? reinterpret_cast<const void *>(k_newton_multi<true>) : reinterpret_cast<const void *>(k_newton_multi<false>);
-  static int per_cu_cache[2][2] = {{-1, -1}, {-1, -1}};    // (kernel; without / with dynamic LDS beyond 16 KiB)
-  int & per_cu = per_cu_cache[any16 ? 1 : 0][lds > 16 * 1024 ? 1 : 0];
+  int & per_cu = lead->newton_multi_per_cu[any16 ? 1 : 0][lds > 16 * 1024 ? 1 : 0];
   if (per_cu < 0 &&
       !hip_ok(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256,
                                                           lds > 16 * 1024 ? 64 * 1024 : 16 * 1024), "hipOccupancyMaxActiveBlocksPerMultiprocessor"))
@@ -4045,11 +4091,6 @@ static int newton_multi_one_launch(pll_partition_t * const * partitions, unsigne
   args.np = newton_params(start, bl_min, bl_max, tolerance, max_newton, L[0].nblocks);
   args.np.nparts = count;
   args.nparts = count;
-  NewtonControl init;
-  memset(&init, 0, sizeof(init));
-  init.x = args.np.x0; init.xl = bl_min; init.xh = bl_max; init.iter = 0; init.status = NEWTON_RUNNING;
-  for (unsigned k = 0; k < count; ++k) init.pscale[k] = args.part[k].xscale;
-  NewtonControl * ctl = static_cast<NewtonControl *>(lead->d_newton);
   // the launch runs on the first partition's stream: after what the others have issued (their sumtables) ...
   for (unsigned k = 1; k < count; ++k)
   {
@@ -4061,12 +4102,9 @@ static int newton_multi_one_launch(pll_partition_t * const * partitions, unsigne
     // (... and after the instance of an earlier loop of the other form, should there have been one)
     if (e->newton_done) PLLHIP_TRY(hipStreamWaitEvent(lead->stream, e->newton_done, 0));
   }
-  const unsigned long long seq = ++lead->newton_seq;
-  args.np.iter_base = (unsigned)(seq << 8);
-  if (args.np.debug) PLLHIP_TRY(hipMemcpyAsync(ctl, &init, sizeof(init), hipMemcpyHostToDevice, lead->stream));
-  double * host_out = lead->hd_newton;
-  unsigned long long * host_flag = reinterpret_cast<unsigned long long *>(lead->hd_newton + 112);
-  void * kargs[] = {(void *)&args, (void *)&ctl, (void *)&host_out, (void *)&host_flag, (void *)&seq};
+  NewtonRun run;
+  if (!newton_begin(lead, args.np, length_scalers, count, run)) return PLL_FAILURE;
+  void * kargs[] = {(void *)&args, (void *)&run.ctl, (void *)&run.host_out, (void *)&run.host_flag, (void *)&run.seq};
   PLLHIP_TRY(hipLaunchKernel(fn, dim3(total), dim3(256), kargs, lds, lead->stream));
   std::vector<Engine *> all;
   for (unsigned k = 0; k < count; ++k) { all.push_back(L[k].e); L[k].e->counters.derivative_calls++; }
@@ -4075,7 +4113,7 @@ static int newton_multi_one_launch(pll_partition_t * const * partitions, unsigne
   PLLHIP_TRY(hipEventRecord(lead->newton_done, lead->stream));
   for (unsigned k = 1; k < count; ++k)
     if (L[k].e->stream != lead->stream) PLLHIP_TRY(hipStreamWaitEvent(L[k].e->stream, lead->newton_done, 0));
-  return newton_finish(lead, all, seq, length, iterations, trail);
+  return newton_finish(lead, all, run.seq, length, iterations, trail);
 }
 
 // Several partitions under ONE branch length (linked lengths, or scaled ones: partition p sees s_p x): the loop of
@@ -4145,24 +4183,17 @@ int pllhip_newton_branch_multi(pll_partition_t * const * partitions, unsigned in
   }
   Engine * lead = L[0].e;
   NewtonParams np = newton_params(start, bl_min, bl_max, tolerance, max_newton, L[0].nblocks);
-  NewtonControl init;
-  memset(&init, 0, sizeof(init));
-  init.x = np.x0; init.xl = bl_min; init.xh = bl_max; init.iter = 0; init.status = NEWTON_RUNNING;
-  for (unsigned k = 0; k < count; ++k) init.pscale[k] = length_scalers ? length_scalers[k] : 1.0;
   PLLHIP_TRY(hipSetDevice(lead->device));
   // (the instances are different kernels on different hardware queues -- pllhip_runtime_defaults asks the runtime for
-  // enough of them; they meet in the first partition's control block)
-  NewtonControl * ctl = static_cast<NewtonControl *>(lead->d_newton);
-  // (the instances of the previous loop of these partitions have left the device: they read the block to the end)
+  // enough of them; they meet in the first partition's control block, after the instances of the previous loop of
+  // these partitions have left the device: they read the block to the end)
   for (unsigned k = 1; k < count; ++k)
     if (L[k].e->newton_done) PLLHIP_TRY(hipStreamWaitEvent(lead->stream, L[k].e->newton_done, 0));
-  const unsigned long long seq = ++lead->newton_seq;
-  np.iter_base = (unsigned)(seq << 8);
-  if (np.debug) PLLHIP_TRY(hipMemcpyAsync(ctl, &init, sizeof(init), hipMemcpyHostToDevice, lead->stream));
+  NewtonRun run;
+  if (!newton_begin(lead, np, length_scalers, count, run)) return PLL_FAILURE;
   // the other partitions' launches use the control block: after the instances of the previous loop have left it
   if (!lead->newton_ready) PLLHIP_TRY(hipEventCreateWithFlags(&lead->newton_ready, hipEventDisableTiming));
   PLLHIP_TRY(hipEventRecord(lead->newton_ready, lead->stream));
-  unsigned long long * host_flag = reinterpret_cast<unsigned long long *>(lead->hd_newton + 112);
   std::vector<Engine *> all;
   np.nparts = count;
   // (an instance that shares a hardware queue with another one never meets it: a shorter bound than the single loop's)
@@ -4171,13 +4202,13 @@ int pllhip_newton_branch_multi(pll_partition_t * const * partitions, unsigned in
   for (unsigned k = 0; k < count; ++k)
   {
     np.part = k;
-    np.xscale = init.pscale[k];
+    np.xscale = length_scalers ? length_scalers[k] : 1.0;
     if (k) { np.stall_block = ~0u; PLLHIP_TRY(hipStreamWaitEvent(L[k].e->stream, lead->newton_ready, 0)); }
     all.push_back(L[k].e);
-    if (!newton_launch(L[k], np, ctl, lead->hd_newton, host_flag, seq))
+    if (!newton_launch(L[k], np, run.ctl, run.host_out, run.host_flag, run.seq))
     {
       // (the instances already launched give up after their bounded wait)
-      (void)newton_finish(lead, all, seq, nullptr, nullptr, nullptr);
+      (void)newton_finish(lead, all, run.seq, nullptr, nullptr, nullptr);
       return PLL_FAILURE;
     }
     if (k)
@@ -4186,7 +4217,7 @@ int pllhip_newton_branch_multi(pll_partition_t * const * partitions, unsigned in
       PLLHIP_TRY(hipEventRecord(L[k].e->newton_done, L[k].e->stream));
     }
   }
-  return newton_finish(lead, all, seq, length, iterations, trail);
+  return newton_finish(lead, all, run.seq, length, iterations, trail);
 }
 
 unsigned int pllhip_free_trial_lengths(const pll_partition_t * p)
@@ -4707,14 +4738,7 @@ int pllhip_profile_read(pll_partition_t * p, pllhip_profile_t * out)
 
 const char * pllhip_partials_kernel_name(const pll_partition_t * p)
 {
-  switch (exec_engine(p)->family)
-  {
-    case KernelFamily::S4: return "s4-valu";
-    case KernelFamily::S20: return "s20-mfma";
-    case KernelFamily::S61: return "s61-mfma";
-    case KernelFamily::S16: return "s16-mfma";
-    default: return "generic";
-  }
+  return edge_family(exec_engine(p))->name;
 }
 
 } // extern "C"
