@@ -390,6 +390,76 @@ PLL_EXPORT void pllhip_compress_last_times(double * upload_ms, double * kernel_m
    joined a group; PLLHIP_COMPRESS_HASH_BITS=0 turns every site's walk into one chain from slot 0. */
 PLL_EXPORT void pllhip_compress_last_counts(unsigned long long * probe_steps, unsigned long long * compares);
 
+/* ---- empirical parameters and alignment statistics ("Empirical parameters and alignment
+ * statistics") ----
+ * What pll-modules' src/msa/pll_msa.c computes on the host, from tips that live on the device: one pass over the
+ * tips fills 64-bit integer tables, the host makes the few divisions, so results do not depend on summation order
+ * and are the same from run to run.  Arrays are malloc()ed; the caller frees them.
+ *
+ * Partition forms (any partition of 2 .. 64 states, sharded ones included; only partition->sites patterns count):
+ *   frequencies [states]: every character adds w / popcount(mask) to each state of its mask, gaps included; over
+ *     sum(w) * tips (pllmod_msa_empirical_frequencies).  Tips set through pll_set_tip_clv with entries other than
+ *     0 and 1 add w * v[k] / sum(v) instead: the one floating-point sum, made in a fixed order.
+ *   subst_rates [states * (states - 1) / 2]: per column cnt[k] = characters that are no gap and contain k,
+ *     pair[i][j] += cnt[i] * cnt[j] * w; over pair[S-2][S-1] (1 if 0), clamped to [0.01, 50], last entry 1
+ *     (pllmod_msa_empirical_subst_rates, with the counts reset for every column -- the reference resets half).
+ *   invariant_sites: weighted share of invariant[n] > -1 (pll_update_invariant_sites runs if it has not: a column
+ *     whose characters share any state, so an all-gap column counts); -INFINITY on failure. */
+PLL_EXPORT double * pllhip_empirical_frequencies(pll_partition_t * partition);
+PLL_EXPORT double * pllhip_empirical_subst_rates(pll_partition_t * partition);
+PLL_EXPORT double pllhip_empirical_invariant_sites(pll_partition_t * partition);
+
+/* Alignment form (pllmod_msa_compute_stats): raw characters and a character -> state map.  Bit values and the
+ * result's fields are those of PLLMOD_MSA_STATS_* / pllmod_msa_stats_t (src/msa/pll_msa.h:29-66).  The gap state is
+ * the full mask of `states` bits; frequencies ignore gaps; an invariant column is one whose masks' AND has exactly one
+ * bit (an all-gap column is not); weights == NULL means 1.  A character that maps to 0 fails the call with
+ * PLL_ERROR_MSA_MAP_INVALID, the message naming the first such character in sequence-major order.  A mask that
+ * asks only for duplicates is host work and touches no device. */
+#define PLLHIP_MSA_STATS_NONE        (0ul)
+#define PLLHIP_MSA_STATS_DUP_TAXA    (1ul<<0)
+#define PLLHIP_MSA_STATS_DUP_SEQS    (1ul<<1)
+#define PLLHIP_MSA_STATS_GAP_PROP    (1ul<<2)
+#define PLLHIP_MSA_STATS_GAP_SEQS    (1ul<<3)
+#define PLLHIP_MSA_STATS_GAP_COLS    (1ul<<4)
+#define PLLHIP_MSA_STATS_INV_PROP    (1ul<<5)
+#define PLLHIP_MSA_STATS_INV_COLS    (1ul<<6)
+#define PLLHIP_MSA_STATS_FREQS       (1ul<<7)
+#define PLLHIP_MSA_STATS_SUBST_RATES (1ul<<8)
+#define PLLHIP_MSA_STATS_ALL         (~0ul)
+
+typedef struct pllhip_msa_stats
+{
+  unsigned int states;
+
+  unsigned long dup_taxa_pairs_count;
+  unsigned long * dup_taxa_pairs;      /* (first occurrence, later copy), by first occurrence, then by copy */
+
+  unsigned long dup_seqs_pairs_count;
+  unsigned long * dup_seqs_pairs;
+
+  double gap_prop;
+  unsigned long gap_seqs_count;
+  unsigned long * gap_seqs;
+  unsigned long gap_cols_count;
+  unsigned long * gap_cols;
+
+  double inv_prop;
+  unsigned long inv_cols_count;
+  unsigned long * inv_cols;
+
+  double * freqs;
+  double * subst_rates;
+} pllhip_msa_stats_t;
+
+PLL_EXPORT pllhip_msa_stats_t * pllhip_msa_compute_stats(const pll_msa_t * msa, unsigned int states,
+                                                         const pll_state_t * tipmap, const unsigned int * weights,
+                                                         unsigned long stats_mask);
+PLL_EXPORT void pllhip_msa_destroy_stats(pllhip_msa_stats_t * stats);
+
+/* device time of this thread's last successful statistics call, in ms between HIP events: rows up (alignment form;
+   0 for a partition), the kernels (summed over shards).  Any pointer may be NULL.  (tools/gpu_msa_stats.py) */
+PLL_EXPORT void pllhip_msa_stats_last_times(double * upload_ms, double * kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

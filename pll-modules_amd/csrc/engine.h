@@ -392,6 +392,7 @@ int upload_tip_clv(pll_partition_t * p, unsigned tip, const double * host_clv);
 int upload_tip_classes(pll_partition_t * p, unsigned tip, const unsigned * site_class, const unsigned long long * masks,
                        unsigned nclasses);
 int upload_weights(pll_partition_t * p);
+int upload_tipmap(pll_partition_t * p);                                 // tip code table -> HBM if it grew
 void invalidate_luts(pll_partition_t * p);
 
 } // namespace pllhip

@@ -6,6 +6,7 @@
 // caller's rows and *length are written only after the last device operation has succeeded.
 #include "engine.h"
 #include "kernels_compress.hpp"
+#include "msa_upload.hpp"
 #include "pllhip.h"
 
 #include <algorithm>
@@ -72,45 +73,6 @@ bool job_alloc(T ** ptr, size_t count, const char * what)
 unsigned grid_for(size_t items, unsigned per_block)
 {
   return (unsigned)std::max<size_t>(1, std::min<size_t>((items + per_block - 1) / per_block, 4096));
-}
-
-// the caller's rows -> d_in [T][Lp], through the two halves of the staging buffer
-bool upload_rows(CompressJob & j, char ** sequence, unsigned T, unsigned L, size_t Lp, size_t half)
-{
-  unsigned turn = 0;
-  bool used[2] = {false, false};
-  auto send = [&](size_t dst_off, size_t bytes, unsigned h) {
-    return hip_ok(hipMemcpyAsync(j.d_in + dst_off, j.h_stage + h * half, bytes, hipMemcpyHostToDevice, j.stream),
-                  "upload alignment") &&
-           hip_ok(hipEventRecord(j.half_free[h], j.stream), "hipEventRecord");
-  };
-  auto claim = [&](unsigned h) {
-    if (used[h] && !hip_ok(hipEventSynchronize(j.half_free[h]), "hipEventSynchronize")) return false;
-    used[h] = true;
-    return true;
-  };
-  if (Lp <= half)
-  {
-    const unsigned per = (unsigned)std::min<size_t>(T, half / Lp);       // whole rows per half, at the device's stride
-    for (unsigned t0 = 0; t0 < T; t0 += per, ++turn)
-    {
-      const unsigned h = turn & 1u, n = std::min(per, T - t0);
-      if (!claim(h)) return false;
-      for (unsigned r = 0; r < n; ++r) memcpy(j.h_stage + h * half + (size_t)r * Lp, sequence[t0 + r], L);
-      if (!send((size_t)t0 * Lp, (size_t)(n - 1u) * Lp + L, h)) return false;
-    }
-  }
-  else
-    for (unsigned t = 0; t < T; ++t)
-      for (size_t off = 0; off < L; off += half, ++turn)
-      {
-        const unsigned h = turn & 1u;
-        const size_t n = std::min(half, (size_t)L - off);
-        if (!claim(h)) return false;
-        memcpy(j.h_stage + h * half, sequence[t] + off, n);
-        if (!send((size_t)t * Lp + off, n, h)) return false;
-      }
-  return true;
 }
 
 // PLLHIP_COMPRESS_HASH_BITS=<0..64>: only that many bits of both hashes are used (a test knob: with few bits the

@@ -478,7 +478,7 @@ int upload_weights(pll_partition_t * p)
   return PLL_SUCCESS;
 }
 
-static int upload_tipmap(pll_partition_t * p)
+int upload_tipmap(pll_partition_t * p)
 {
   Engine * e = engine_of(p);
   if (!lut_active(e) || e->tipmap_codes_uploaded == codes_in_use(e, p)) return PLL_SUCCESS;

@@ -126,6 +126,23 @@ class Msa(C.Structure):
                 ("label", C.POINTER(C.c_char_p))]
 
 
+class MsaStats(C.Structure):
+    """pllhip_msa_stats_t (the fields of pllmod_msa_stats_t)"""
+    _fields_ = [("states", C.c_uint),
+                ("dup_taxa_pairs_count", C.c_ulong), ("dup_taxa_pairs", C.POINTER(C.c_ulong)),
+                ("dup_seqs_pairs_count", C.c_ulong), ("dup_seqs_pairs", C.POINTER(C.c_ulong)),
+                ("gap_prop", C.c_double),
+                ("gap_seqs_count", C.c_ulong), ("gap_seqs", C.POINTER(C.c_ulong)),
+                ("gap_cols_count", C.c_ulong), ("gap_cols", C.POINTER(C.c_ulong)),
+                ("inv_prop", C.c_double),
+                ("inv_cols_count", C.c_ulong), ("inv_cols", C.POINTER(C.c_ulong)),
+                ("freqs", c_double_p), ("subst_rates", c_double_p)]
+
+
+MSA_STATS_DUP_TAXA, MSA_STATS_DUP_SEQS, MSA_STATS_GAP_PROP, MSA_STATS_GAP_SEQS, MSA_STATS_GAP_COLS = 1, 2, 4, 8, 16
+MSA_STATS_INV_PROP, MSA_STATS_INV_COLS, MSA_STATS_FREQS, MSA_STATS_SUBST_RATES = 32, 64, 128, 256
+MSA_STATS_ALL = (1 << (8 * C.sizeof(C.c_ulong))) - 1
+
 TRAVERSE_CB = C.CFUNCTYPE(C.c_int, C.POINTER(UNode))
 REDUCE_CB = C.CFUNCTYPE(None, C.c_void_p, c_double_p, C.c_size_t, C.c_int)
 
@@ -169,7 +186,9 @@ pllhip_results_edge_loglikelihood pllhip_results_derivatives pllhip_results_fetc
 pllhip_eval_attach_comm pllhip_update_partials_batch pllhip_results_poison pllhip_newton_branch pllhip_repeat_stats
 pllhip_set_transient pllhip_discard_transient pllhip_transient_stats pllhip_newton_branch_multi
 pllhip_schedule_stats
-pllhip_parsimony_tree_score pllhip_compress_last_times pllhip_compress_last_counts""".split()
+pllhip_parsimony_tree_score pllhip_compress_last_times pllhip_compress_last_counts
+pllhip_empirical_frequencies pllhip_empirical_subst_rates pllhip_empirical_invariant_sites
+pllhip_msa_compute_stats pllhip_msa_destroy_stats pllhip_msa_stats_last_times""".split()
 
 
 def _u32(a):
@@ -380,6 +399,19 @@ class PllLib:
             L.pllhip_results_fetch.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_int, c_double_p]
             L.pllhip_results_poison.argtypes = [C.c_void_p]
             L.pllhip_results_poison.restype = None
+        if hasattr(L, "pllhip_msa_compute_stats"):
+            L.pllhip_empirical_frequencies.restype = c_double_p
+            L.pllhip_empirical_frequencies.argtypes = [pp]
+            L.pllhip_empirical_subst_rates.restype = c_double_p
+            L.pllhip_empirical_subst_rates.argtypes = [pp]
+            L.pllhip_empirical_invariant_sites.restype = C.c_double
+            L.pllhip_empirical_invariant_sites.argtypes = [pp]
+            L.pllhip_msa_compute_stats.restype = C.POINTER(MsaStats)
+            L.pllhip_msa_compute_stats.argtypes = [mp, C.c_uint, C.POINTER(C.c_ulonglong), c_uint_p, C.c_ulong]
+            L.pllhip_msa_destroy_stats.restype = None
+            L.pllhip_msa_destroy_stats.argtypes = [C.POINTER(MsaStats)]
+            L.pllhip_msa_stats_last_times.restype = None
+            L.pllhip_msa_stats_last_times.argtypes = [c_double_p, c_double_p]
         if hasattr(L, "pllhip_newton_branch"):
             L.pllhip_newton_branch.argtypes = [pp, C.c_int, C.c_int, c_uint_p, c_double_p, C.c_double, C.c_double,
                                                C.c_double, C.c_double, C.c_uint, c_double_p, c_uint_p, c_double_p]
@@ -484,6 +516,73 @@ class PllLib:
         up, kern, down = C.c_double(), C.c_double(), C.c_double()
         self.lib.pllhip_compress_last_times(C.byref(up), C.byref(kern), C.byref(down))
         return up.value, kern.value, down.value
+
+    # --- empirical parameters and alignment statistics ----------------------
+    def _take_doubles(self, ptr, n):
+        """copy of n doubles the library malloc()ed (freed here), or None when the call returned NULL"""
+        if not ptr:
+            return None
+        out = np.ctypeslib.as_array(ptr, shape=(n,)).copy()
+        _libc_free(ptr)
+        return out
+
+    def empirical_frequencies(self, partition):
+        """pllhip_empirical_frequencies: [states] float64, or None (see errno)"""
+        self.errno = 0
+        return self._take_doubles(self.lib.pllhip_empirical_frequencies(partition), partition.contents.states)
+
+    def empirical_subst_rates(self, partition):
+        """pllhip_empirical_subst_rates: [states * (states - 1) / 2] float64, or None (see errno)"""
+        self.errno = 0
+        S = partition.contents.states
+        return self._take_doubles(self.lib.pllhip_empirical_subst_rates(partition), S * (S - 1) // 2)
+
+    def empirical_invariant_sites(self, partition):
+        self.errno = 0
+        return self.lib.pllhip_empirical_invariant_sites(partition)
+
+    def msa_compute_stats(self, rows, states, charmap, weights=None, mask=MSA_STATS_ALL, labels=None):
+        """pllhip_msa_compute_stats on rows ([T][L] bytes); labels default to t0, t1, ...  Returns a dict of the
+        result's fields (lists and float64 arrays; pairs as lists of tuples), or None when the call returned NULL
+        (see errno / errmsg)."""
+        rows = [bytes(r) for r in rows]
+        T, L = len(rows), len(rows[0])
+        bufs = [C.create_string_buffer(r, len(r) + 1) for r in rows]
+        seqs = (C.c_void_p * T)(*[C.addressof(b) for b in bufs])
+        names = [b"t%d" % t for t in range(T)] if labels is None else [bytes(x) for x in labels]
+        lab = (C.c_char_p * T)(*names)
+        msa = Msa(T, L, seqs, lab)
+        cmap = (C.c_ulonglong * 256)(*[int(x) for x in charmap])
+        w = None if weights is None else _u32(weights)
+        self.errno = 0
+        st = self.lib.pllhip_msa_compute_stats(C.byref(msa), states, cmap,
+                                               None if w is None else w.ctypes.data_as(c_uint_p), mask)
+        if not st:
+            return None
+        c = st.contents
+        npairs = states * (states - 1) // 2
+        out = {
+            "states": c.states,
+            "dup_taxa_pairs": [(c.dup_taxa_pairs[2 * i], c.dup_taxa_pairs[2 * i + 1])
+                               for i in range(c.dup_taxa_pairs_count)],
+            "dup_seqs_pairs": [(c.dup_seqs_pairs[2 * i], c.dup_seqs_pairs[2 * i + 1])
+                               for i in range(c.dup_seqs_pairs_count)],
+            "gap_prop": c.gap_prop,
+            "gap_seqs": [c.gap_seqs[i] for i in range(c.gap_seqs_count)],
+            "gap_cols": [c.gap_cols[i] for i in range(c.gap_cols_count)],
+            "inv_prop": c.inv_prop,
+            "inv_cols": [c.inv_cols[i] for i in range(c.inv_cols_count)],
+            "freqs": np.ctypeslib.as_array(c.freqs, shape=(states,)).copy() if c.freqs else None,
+            "subst_rates": np.ctypeslib.as_array(c.subst_rates, shape=(npairs,)).copy() if c.subst_rates else None,
+        }
+        self.lib.pllhip_msa_destroy_stats(st)
+        return out
+
+    def msa_stats_last_times(self):
+        """(upload, kernels) ms of the last statistics call"""
+        up, kern = C.c_double(), C.c_double()
+        self.lib.pllhip_msa_stats_last_times(C.byref(up), C.byref(kern))
+        return up.value, kern.value
 
     def gamma_cats(self, alpha, k, mode=PLL_GAMMA_RATES_MEAN):
         out = np.zeros(k)
