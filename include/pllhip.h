@@ -460,6 +460,66 @@ PLL_EXPORT void pllhip_msa_destroy_stats(pllhip_msa_stats_t * stats);
    0 for a partition), the kernels (summed over shards).  Any pointer may be NULL.  (tools/gpu_msa_stats.py) */
 PLL_EXPORT void pllhip_msa_stats_last_times(double * upload_ms, double * kernel_ms);
 
+/* ---- tree sets: splits, RF distances, bootstrap support ("Split support and tree distances") ----
+ * A set of B binary unrooted trees over the same T tips (4 .. 65535), and what pll-modules' src/tree computes from
+ * such trees on one host thread: pllmod_utree_split_create, pllmod_utree_split_rf_distance, Felsenstein support and
+ * pllmod_utree_tbe_naive.  Integer work on the device; every result is exact and the same from run to run.
+ *
+ * Tip ids: with labels, the index of a tip's label in `labels` (copied); without, the tip's node_index, which must be
+ *   a permutation of 0 .. T-1 (what pllmod_utree_consistency_set arranges).  Trees are only read, and nothing of them
+ *   is kept.
+ * Split: ceil(T/32) words per inner edge, bit id%32 of word id/32 set for the tips on one side, normalised so that
+ *   bit 0 of word 0 is set, unused high bits clear; a tree's T-3 splits ascending by words compared as unsigned, word
+ *   0 first (content and order of pllmod_utree_split_create).
+ * RF(a, b) = 2 * (T - 3 - common splits).  FBP support of a reference split = trees that hold it / B.
+ * TBE support: with p the size of the split's lighter side and delta = min(p - 1, min over the nodes v of a tree of
+ *   min(d, T - d)), d = |split xor tips below v|, the support is 1 - sum(delta) / (B * (p - 1)); the sum is a 64-bit
+ *   integer and the quotient (B * (p - 1) - sum) / (B * (p - 1)) is rounded once.
+ *
+ * pllhip_treeset_create and _add touch no device.  The other calls run on the device pllhip_get_device() names, on a
+ * stream of their own, and return when done.  PLL_FAILURE / NULL with pll_errno PLL_ERROR_PARAM_INVALID (NULL
+ * arguments, T outside 4 .. 65535, a bad index, an empty set, tip ids or labels that are unknown, duplicate or
+ * missing), PLL_ERROR_TREE_INVALID (not binary, not T tips), PLL_ERROR_MEM_ALLOC, PLL_ERROR_HIP_NODEVICE,
+ * PLL_ERROR_HIP_RUNTIME; a failed call leaves the set as it was.
+ * PLLHIP_TREESET_BATCH=<trees> fixes how many trees' splits are built at a time (default: from free device memory);
+ * PLLHIP_SPLIT_HASH_BITS=<0..64> keeps that many bits of the split hash.  Neither changes a result. */
+typedef struct pllhip_treeset pllhip_treeset_t;
+
+#define PLLHIP_SUPPORT_FBP 0
+#define PLLHIP_SUPPORT_TBE 1
+
+PLL_EXPORT pllhip_treeset_t * pllhip_treeset_create(unsigned int tip_count, const char * const * labels);
+PLL_EXPORT void pllhip_treeset_destroy(pllhip_treeset_t * ts);
+PLL_EXPORT unsigned int pllhip_treeset_count(const pllhip_treeset_t * ts);
+PLL_EXPORT int pllhip_treeset_add(pllhip_treeset_t * ts, const pll_utree_t * tree);
+/* the (T-3) * ceil(T/32) words of tree `index` */
+PLL_EXPORT int pllhip_treeset_splits(pllhip_treeset_t * ts, unsigned int index, unsigned int * out);
+/* out [B * B]: symmetric, zero diagonal */
+PLL_EXPORT int pllhip_treeset_rf_matrix(pllhip_treeset_t * ts, unsigned int * out);
+/* out [B]: RF distance of every tree to `ref` */
+PLL_EXPORT int pllhip_treeset_rf_to(pllhip_treeset_t * ts, const pll_utree_t * ref, unsigned int * out);
+/* support [T-3]: entry i belongs to the i-th split of `ref` in the order above (the index pllmod_utree_split_create
+   gives on the same tree); split_to_node_map [T-3] or NULL: a record of that edge in the caller's tree, so that
+   pllmod_utree_draw_support(ref, support, map, NULL) works unchanged */
+PLL_EXPORT int pllhip_treeset_support(pllhip_treeset_t * ts, const pll_utree_t * ref, int kind, double * support,
+                                      pll_unode_t ** split_to_node_map);
+/* the integers behind this thread's last support call: trees that hold split i (FBP) or sum(delta) (TBE).  Copies
+   min(count, T-3) of them and returns T-3. */
+PLL_EXPORT unsigned int pllhip_treeset_last_sums(unsigned long long * out, unsigned int count);
+/* what the host made of tree `index` (host only; csrc/treeset_plan.h): order [T-1] tip ids depth first from tip 0's
+   neighbour, lo/hi [T-3] the inner edges as intervals of it, program [2 * (2T-3)] (kind, argument) pairs with kind 0 =
+   push tip, 1 = combine the two top entries into a node of `argument` tips, and the deepest stack the program reaches
+   (never more than 1 + floor(log2(T))).  Any pointer may be NULL. */
+PLL_EXPORT int pllhip_treeset_plan(const pllhip_treeset_t * ts, unsigned int index, unsigned int * order,
+                                   unsigned int * lo, unsigned int * hi, unsigned int * program,
+                                   unsigned int * max_stack);
+/* device time of this thread's last successful tree-set query, in ms between HIP events: plans, programs and the
+   reference up; kernels; results down.  Trees added since the last query are brought to the device by the next one
+   and count towards it.  pllhip_treeset_last_counts: slots passed over and full bit-vector compares of the split
+   table while the last such trees were inserted. */
+PLL_EXPORT void pllhip_treeset_last_times(double * upload_ms, double * kernel_ms, double * download_ms);
+PLL_EXPORT void pllhip_treeset_last_counts(unsigned long long * probe_steps, unsigned long long * compares);
+
 #ifdef __cplusplus
 }
 #endif

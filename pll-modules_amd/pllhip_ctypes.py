@@ -188,7 +188,10 @@ pllhip_set_transient pllhip_discard_transient pllhip_transient_stats pllhip_newt
 pllhip_schedule_stats
 pllhip_parsimony_tree_score pllhip_compress_last_times pllhip_compress_last_counts
 pllhip_empirical_frequencies pllhip_empirical_subst_rates pllhip_empirical_invariant_sites
-pllhip_msa_compute_stats pllhip_msa_destroy_stats pllhip_msa_stats_last_times""".split()
+pllhip_msa_compute_stats pllhip_msa_destroy_stats pllhip_msa_stats_last_times
+pllhip_treeset_create pllhip_treeset_destroy pllhip_treeset_count pllhip_treeset_add pllhip_treeset_splits
+pllhip_treeset_rf_matrix pllhip_treeset_rf_to pllhip_treeset_support pllhip_treeset_last_sums pllhip_treeset_plan
+pllhip_treeset_last_times pllhip_treeset_last_counts""".split()
 
 
 def _u32(a):
@@ -412,6 +415,26 @@ class PllLib:
             L.pllhip_msa_destroy_stats.argtypes = [C.POINTER(MsaStats)]
             L.pllhip_msa_stats_last_times.restype = None
             L.pllhip_msa_stats_last_times.argtypes = [c_double_p, c_double_p]
+        if hasattr(L, "pllhip_treeset_create"):
+            ull_p = C.POINTER(C.c_ulonglong)
+            L.pllhip_treeset_create.restype = C.c_void_p
+            L.pllhip_treeset_create.argtypes = [C.c_uint, C.POINTER(C.c_char_p)]
+            L.pllhip_treeset_destroy.restype = None
+            L.pllhip_treeset_destroy.argtypes = [C.c_void_p]
+            L.pllhip_treeset_count.restype = C.c_uint
+            L.pllhip_treeset_count.argtypes = [C.c_void_p]
+            L.pllhip_treeset_add.argtypes = [C.c_void_p, tp]
+            L.pllhip_treeset_splits.argtypes = [C.c_void_p, C.c_uint, c_uint_p]
+            L.pllhip_treeset_rf_matrix.argtypes = [C.c_void_p, c_uint_p]
+            L.pllhip_treeset_rf_to.argtypes = [C.c_void_p, tp, c_uint_p]
+            L.pllhip_treeset_support.argtypes = [C.c_void_p, tp, C.c_int, c_double_p, C.POINTER(up)]
+            L.pllhip_treeset_last_sums.restype = C.c_uint
+            L.pllhip_treeset_last_sums.argtypes = [ull_p, C.c_uint]
+            L.pllhip_treeset_plan.argtypes = [C.c_void_p, C.c_uint, c_uint_p, c_uint_p, c_uint_p, c_uint_p, c_uint_p]
+            L.pllhip_treeset_last_times.restype = None
+            L.pllhip_treeset_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
+            L.pllhip_treeset_last_counts.restype = None
+            L.pllhip_treeset_last_counts.argtypes = [ull_p, ull_p]
         if hasattr(L, "pllhip_newton_branch"):
             L.pllhip_newton_branch.argtypes = [pp, C.c_int, C.c_int, c_uint_p, c_double_p, C.c_double, C.c_double,
                                                C.c_double, C.c_double, C.c_uint, c_double_p, c_uint_p, c_double_p]
@@ -1074,6 +1097,117 @@ def utree_splits(tree):
             s = side(rec)
             splits.add(s if low not in s else frozenset(tips) - s)
     return splits
+
+
+SUPPORT_FBP, SUPPORT_TBE = 0, 1
+PLL_ERROR_MEM_ALLOC, PLL_ERROR_PARAM_INVALID, PLL_ERROR_TREE_INVALID = 112, 113, 133
+PLL_ERROR_HIP_RUNTIME, PLL_ERROR_HIP_NODEVICE = 900, 901
+
+
+class TreeSet:
+    """pllhip_treeset_* (include/pllhip.h): a set of binary trees over the same tips.  Trees go in as Newick strings
+    (parsed by the library) or as POINTER(UTree); a failed call returns None / False with lib.errno set."""
+
+    def __init__(self, lib, tip_count, labels=None):
+        self.lib, self.L, self.T = lib, lib.lib, tip_count
+        arr = None
+        if labels is not None:
+            arr = (C.c_char_p * len(labels))(*[None if l is None else l.encode() for l in labels])
+        self.h = self.L.pllhip_treeset_create(tip_count, arr)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.h:
+            self.L.pllhip_treeset_destroy(self.h)
+            self.h = None
+
+    @property
+    def count(self):
+        return self.L.pllhip_treeset_count(self.h)
+
+    @property
+    def words(self):
+        return (self.T + 31) // 32
+
+    def _with_tree(self, tree, call):
+        """call(POINTER(UTree)) on a Newick string or a tree"""
+        if not isinstance(tree, str):
+            return call(tree)
+        t = self.L.pll_utree_parse_newick_string(tree.encode())
+        if not t:
+            raise ValueError(f"cannot parse {tree[:60]!r}: {self.lib.errmsg}")
+        try:
+            return call(t)
+        finally:
+            self.L.pll_utree_destroy(t, None)
+
+    def add(self, tree):
+        return bool(self._with_tree(tree, lambda t: self.L.pllhip_treeset_add(self.h, t)))
+
+    def plan(self, index):
+        """(order, lo, hi, program [2T-3, 2], deepest stack) of tree `index`, or None"""
+        T = self.T
+        order, lo, hi = np.zeros(T - 1, np.uint32), np.zeros(T - 3, np.uint32), np.zeros(T - 3, np.uint32)
+        prog, deepest = np.zeros((2 * T - 3, 2), np.uint32), C.c_uint(0)
+        ok = self.L.pllhip_treeset_plan(self.h, index, order.ctypes.data_as(c_uint_p), lo.ctypes.data_as(c_uint_p),
+                                        hi.ctypes.data_as(c_uint_p), prog.ctypes.data_as(c_uint_p), C.byref(deepest))
+        return (order, lo, hi, prog, deepest.value) if ok else None
+
+    def splits(self, index):
+        out = np.zeros((self.T - 3, self.words), np.uint32)
+        return out if self.L.pllhip_treeset_splits(self.h, index, out.ctypes.data_as(c_uint_p)) else None
+
+    def rf_matrix(self):
+        B = self.count
+        out = np.zeros((B, B), np.uint32)
+        return out if self.L.pllhip_treeset_rf_matrix(self.h, out.ctypes.data_as(c_uint_p)) else None
+
+    def rf_to(self, ref):
+        out = np.zeros(self.count, np.uint32)
+        ok = self._with_tree(ref, lambda t: self.L.pllhip_treeset_rf_to(self.h, t, out.ctypes.data_as(c_uint_p)))
+        return out if ok else None
+
+    def support(self, ref, kind, with_map=False):
+        """(support [T-3], the integers behind it [T-3]) or None; with_map: also, per split, the clv indices of the
+        tips behind the mapped record's back pointer (the side of the edge away from the record)"""
+        R = self.T - 3
+        out, nodes = np.zeros(R, np.float64), (C.POINTER(UNode) * R)()
+        sides = []
+
+        def call(t):
+            ok = self.L.pllhip_treeset_support(self.h, t, kind, out.ctypes.data_as(c_double_p), nodes if with_map else None)
+            if ok and with_map:
+                for rec in nodes:
+                    tips, stack = set(), [rec.contents.back]
+                    while stack:
+                        r = stack.pop()
+                        if not r.contents.next:
+                            tips.add(r.contents.label.decode() if r.contents.label else r.contents.node_index)
+                        else:
+                            stack += [r.contents.next.contents.back, r.contents.next.contents.next.contents.back]
+                    sides.append(frozenset(tips))
+            return ok
+
+        if not self._with_tree(ref, call):
+            return None
+        sums = np.zeros(R, np.uint64)
+        self.L.pllhip_treeset_last_sums(sums.ctypes.data_as(C.POINTER(C.c_ulonglong)), R)
+        return (out, sums, sides) if with_map else (out, sums)
+
+    def last_times(self):
+        up, kern, down = C.c_double(0), C.c_double(0), C.c_double(0)
+        self.L.pllhip_treeset_last_times(C.byref(up), C.byref(kern), C.byref(down))
+        return up.value, kern.value, down.value
+
+    def last_counts(self):
+        probes, compares = C.c_ulonglong(0), C.c_ulonglong(0)
+        self.L.pllhip_treeset_last_counts(C.byref(probes), C.byref(compares))
+        return probes.value, compares.value
 
 
 def state_charmap(nstates):
