@@ -520,6 +520,42 @@ PLL_EXPORT int pllhip_treeset_plan(const pllhip_treeset_t * ts, unsigned int ind
 PLL_EXPORT void pllhip_treeset_last_times(double * upload_ms, double * kernel_ms, double * download_ms);
 PLL_EXPORT void pllhip_treeset_last_counts(unsigned long long * probe_steps, unsigned long long * compares);
 
+/* ---- consensus of a tree set ("Split support and tree distances") ----
+ * What pllmod_utree_weight_consensus with equal weights computes: threshold 1.0 is the strict consensus, 0.5 majority
+ * rule, 0.0 extended majority rule; a value outside [0, 1] fails with PLL_ERROR_PARAM_INVALID, an empty set as every
+ * other query does.  With B trees and c the number of trees that hold a split:
+ *   need_major  c = B for threshold 1.0; 2c > B for max(threshold, 0.5) = 0.5; otherwise the smallest c for which the
+ *               one correctly rounded quotient (double)c / (double)B is greater than the threshold.  Every split with
+ *               c >= need_major is in.
+ *   need_minor  for a threshold below 0.5 the splits with c / B > threshold (every split for 0.0; the same rounded
+ *               comparison) are candidates of the greedy extension: in rank order, each one that is compatible with
+ *               everything taken so far is taken, until T-3 splits are held.
+ *   rank        c descending, then the bit vector ascending (words as unsigned, word 0 first).  The output is in this
+ *               order, in the normal form of pllhip_treeset_splits.  The result is that of the sequential definition,
+ *               whatever PLLHIP_CONSENSUS_BLOCK=<1..2048> (candidates per round on the device, default 1024) says.
+ * out_words [(T-3) * ceil(T/32)], out_trees [T-3] (c), out_support [T-3] ((double)c / (double)B, rounded once); any may
+ * be NULL.  *out_count = K, the number of splits (0 .. T-3).  The arrays are what a pll_split_system_t holds (splits
+ * row by row, support, split_count, max_support = 1.0).  pllhip_treeset_last_times covers both calls. */
+PLL_EXPORT int pllhip_treeset_consensus(pllhip_treeset_t * ts, double threshold, unsigned int * out_count,
+                                        unsigned int * out_words, unsigned int * out_trees, double * out_support);
+/* The unrooted, possibly multifurcating tree of that split system, built on the host; destroy it with
+   pll_utree_destroy(tree, NULL).  Tips carry the set's labels (none for an unlabelled set) and node_index = clv_index =
+   tip id; vroot is tip 0's neighbour; K = 0 gives the star.  The support of a split is the label of the inner node on
+   the side of its edge away from tip 0, as the shortest decimal that reads back as the same double (all records of
+   the node share the string, as in a cloned tree): pll_utree_export_newick(tree->vroot, NULL) prints it in the place
+   of a bootstrap value, and a callback finds it in node->label of every record with node->next != NULL. */
+PLL_EXPORT pll_utree_t * pllhip_treeset_consensus_tree(pllhip_treeset_t * ts, double threshold);
+/* The same builder for any `count` pairwise compatible, distinct, non-trivial splits in normal form (host only; support
+   may be NULL: no inner labels).  NULL with PLL_ERROR_PARAM_INVALID when the splits are not such a system. */
+PLL_EXPORT pll_utree_t * pllhip_treeset_tree_from_splits(const pllhip_treeset_t * ts, unsigned int count,
+                                                         const unsigned int * words, const double * support);
+/* need_major and need_minor of `tree_count` trees (host only) */
+PLL_EXPORT int pllhip_consensus_needs(unsigned int tree_count, double threshold, unsigned int * need_major,
+                                      unsigned int * need_minor);
+/* this thread's last consensus call: splits of the accepted set that candidates were tested against, and pairs of
+   candidates of one round tested against each other */
+PLL_EXPORT void pllhip_treeset_last_consensus_counts(unsigned long long * accepted_tests, unsigned long long * pair_tests);
+
 #ifdef __cplusplus
 }
 #endif

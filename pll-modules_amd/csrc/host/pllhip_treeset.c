@@ -23,6 +23,7 @@ struct pllhip_ts_labels
   unsigned int count;
   ts_label_t * entry;
   char * text;
+  const char ** by_id;
 };
 
 static int label_cmp(const void * a, const void * b)
@@ -42,8 +43,13 @@ pllhip_ts_labels_t * pllhip_ts_labels_create(unsigned int tip_count, const char 
     bytes += strlen(labels[i]) + 1;
   }
   t = (pllhip_ts_labels_t *)calloc(1, sizeof(*t));
-  if (t) { t->entry = (ts_label_t *)malloc(tip_count * sizeof(ts_label_t)); t->text = (char *)malloc(bytes); }
-  if (!t || !t->entry || !t->text)
+  if (t)
+  {
+    t->entry = (ts_label_t *)malloc(tip_count * sizeof(ts_label_t));
+    t->text = (char *)malloc(bytes);
+    t->by_id = (const char **)malloc(tip_count * sizeof(char *));
+  }
+  if (!t || !t->entry || !t->text || !t->by_id)
   {
     pllhip_ts_labels_destroy(t);
     fail(PLL_ERROR_MEM_ALLOC, "tree set: cannot allocate the label table");
@@ -56,6 +62,7 @@ pllhip_ts_labels_t * pllhip_ts_labels_create(unsigned int tip_count, const char 
     memcpy(t->text + at, labels[i], n);
     t->entry[i].label = t->text + at;
     t->entry[i].id = i;
+    t->by_id[i] = t->text + at;
     at += n;
   }
   qsort(t->entry, tip_count, sizeof(ts_label_t), label_cmp);
@@ -76,7 +83,13 @@ void pllhip_ts_labels_destroy(pllhip_ts_labels_t * t)
   if (!t) return;
   free(t->entry);
   free(t->text);
+  free((void *)t->by_id);
   free(t);
+}
+
+const char * pllhip_ts_labels_get(const pllhip_ts_labels_t * t, unsigned int id)
+{
+  return t && id < t->count ? t->by_id[id] : NULL;
 }
 
 long pllhip_ts_labels_find(const pllhip_ts_labels_t * t, const char * label)

@@ -11,6 +11,8 @@
 //   k_ts_lookup   ids of the reference tree's splits (TS_NONE: in no tree)
 //   k_ts_rf_*     common splits of two id lists: a wave per pair, a binary search per id
 //   k_ts_tbe      transfer distances: a lane per reference split, a workgroup walks transfer programs
+//   k_cs_*        consensus: candidates ranked by (trees that hold them, content), then a greedy selection in blocks
+//                 (described where the kernels are, at the end of this file)
 //
 // Which split of a group of equal ones owns a slot, and which id it gets, is a race.  Nothing that leaves the device
 // depends on either: splits leave as bit vectors and are ordered by content, RF and FBP count equal ids, and TBE does
@@ -338,6 +340,279 @@ __global__ __launch_bounds__(TS_WG) void k_ts_tbe(const uint2 * __restrict__ pro
     acc += delta;
   }
   if (i < R) atomicAdd(sums + i, acc);
+}
+
+// ---- consensus --------------------------------------------------------------------------
+// Candidates are the distinct splits held by at least need_minor trees.  Their rank is (trees descending, bit vector
+// ascending, word 0 first): content, never an id.  A rank entry is {key, id} with key = ~trees << 32 | word 0, so the
+// key alone decides all but ties in trees and word 0; those are settled by comparing the two rows of the store.
+// Splits held by need_major trees or more are pairwise compatible and are accepted as they stand; the others go
+// through the greedy selection in blocks of n <= CS_MAX_BLOCK candidates:
+//   k_cs_filter   a wave per candidate: against every accepted split, stopping at the first incompatible one
+//   k_cs_pairs    a wave per survivor i: against the survivors j < i of the block; conflict[i] is a row of bits
+//   k_cs_resolve  one workgroup: wave 0 walks the block in rank order and takes survivor i when conflict[i] has no bit
+//                 in common with the survivors taken so far; then all four waves append the taken vectors
+// Two normalised splits (both hold tip 0) are compatible exactly when one holds the other or their union is every tip.
+// A wave tests 64 / G splits at a time, G = the power of two >= len (at most 64) lanes per split, lanes striding over
+// words; three ballots carry the three properties and a fold per group decides.
+// state: {held, candidates, majority, unused}; tests: {candidate-accepted tests, pairwise tests}.
+
+constexpr unsigned CS_MAX_BLOCK = 2048;                        // 64 lanes x 32 bits: a conflict row fits a wave
+constexpr unsigned CS_HELD = 0, CS_NCAND = 1, CS_NMAJOR = 2;
+
+struct CsEntry { unsigned long long key; unsigned id; unsigned pad; };
+
+__global__ __launch_bounds__(TS_WG) void k_cs_candidates(const unsigned * __restrict__ trees_with, const uint32_t * __restrict__ store,
+                                                         unsigned len, unsigned D, unsigned need_major, unsigned need_minor,
+                                                         CsEntry * __restrict__ rank, unsigned * state)
+{
+  for (size_t at = (size_t)blockIdx.x * TS_WG + threadIdx.x; at < D; at += (size_t)gridDim.x * TS_WG)
+  {
+    const unsigned c = trees_with[at];
+    if (c < need_minor) continue;
+    const unsigned slot = atomicAdd(state + CS_NCAND, 1u);
+    if (c >= need_major) atomicAdd(state + CS_NMAJOR, 1u);
+    CsEntry e;
+    e.key = ((unsigned long long)(~c) << 32) | store[at * len];
+    e.id = (unsigned)at;
+    e.pad = 0u;
+    rank[slot] = e;
+  }
+}
+
+// rank[from .. n) = padding that sorts last
+__global__ __launch_bounds__(TS_WG) void k_cs_pad(CsEntry * __restrict__ rank, const unsigned * __restrict__ state, unsigned n)
+{
+  const unsigned from = state[CS_NCAND];
+  for (size_t at = (size_t)blockIdx.x * TS_WG + threadIdx.x + from; at < n; at += (size_t)gridDim.x * TS_WG)
+  {
+    CsEntry e;
+    e.key = ~0ULL; e.id = TS_NONE; e.pad = 0u;
+    rank[at] = e;
+  }
+}
+
+__device__ inline bool cs_after(const CsEntry & a, const CsEntry & b, const uint32_t * __restrict__ store, unsigned len)
+{
+  if (a.key != b.key) return a.key > b.key;
+  if (a.id == b.id || a.id == TS_NONE || b.id == TS_NONE) return false;
+  const uint32_t * x = store + (size_t)a.id * len, * y = store + (size_t)b.id * len;
+  for (unsigned w = 1; w < len; ++w)
+    if (x[w] != y[w]) return x[w] > y[w];
+  return false;
+}
+
+// one step (k, j) of a bitonic sort of n = 2^m entries in global memory
+__global__ __launch_bounds__(TS_WG) void k_cs_sort_step(CsEntry * rank, unsigned n, unsigned k, unsigned j,
+                                                        const uint32_t * __restrict__ store, unsigned len)
+{
+  for (size_t at = (size_t)blockIdx.x * TS_WG + threadIdx.x; at < n; at += (size_t)gridDim.x * TS_WG)
+  {
+    const unsigned i = (unsigned)at, l = i ^ j;
+    if (l <= i) continue;
+    const CsEntry a = rank[i], b = rank[l];
+    if (((i & k) == 0u) ? cs_after(a, b, store, len) : cs_after(b, a, store, len)) { rank[i] = b; rank[l] = a; }
+  }
+}
+
+// all the steps j <= TS_WG of one k, or (k == 0) the whole sort of every 2 * TS_WG entries, in LDS
+__global__ __launch_bounds__(TS_WG) void k_cs_sort_local(CsEntry * rank, unsigned n, unsigned k_from, unsigned k_to,
+                                                         const uint32_t * __restrict__ store, unsigned len)
+{
+  __shared__ CsEntry tile[2u * TS_WG];
+  for (size_t base = (size_t)blockIdx.x * 2u * TS_WG; base < n; base += (size_t)gridDim.x * 2u * TS_WG)
+  {
+    for (unsigned i = threadIdx.x; i < 2u * TS_WG; i += TS_WG)
+    {
+      if (base + i < n) tile[i] = rank[base + i];
+      else { tile[i].key = ~0ULL; tile[i].id = TS_NONE; tile[i].pad = 0u; }
+    }
+    __syncthreads();
+    for (unsigned k = k_from; k <= k_to; k <<= 1)
+      for (unsigned j = min(k >> 1, TS_WG); j; j >>= 1)
+      {
+        const unsigned i = 2u * threadIdx.x - (threadIdx.x & (j - 1u)), l = i + j;      // the pair's lower index
+        const bool up = (((unsigned)base + i) & k) == 0u;
+        const CsEntry a = tile[i], b = tile[l];
+        if (up ? cs_after(a, b, store, len) : cs_after(b, a, store, len)) { tile[i] = b; tile[l] = a; }
+        __syncthreads();
+      }
+    for (unsigned i = threadIdx.x; i < 2u * TS_WG; i += TS_WG)
+      if (base + i < n) rank[base + i] = tile[i];
+    __syncthreads();
+  }
+}
+
+// accepted[i] = the vector of rank[i], i < min(majority, R); held = that many
+__global__ __launch_bounds__(TS_WG) void k_cs_take_majority(const CsEntry * __restrict__ rank, const uint32_t * __restrict__ store,
+                                                            const unsigned * __restrict__ trees_with, unsigned len, unsigned R,
+                                                            uint32_t * __restrict__ accepted, unsigned * __restrict__ acc_trees,
+                                                            unsigned * state)
+{
+  const unsigned m = min(state[CS_NMAJOR], R);
+  const size_t n = (size_t)m * len;
+  for (size_t at = (size_t)blockIdx.x * TS_WG + threadIdx.x; at < n; at += (size_t)gridDim.x * TS_WG)
+  {
+    const unsigned id = rank[at / len].id;
+    accepted[at] = store[(size_t)id * len + at % len];
+    if (at % len == 0u) acc_trees[at / len] = trees_with[id];
+  }
+  if (blockIdx.x == 0u && threadIdx.x == 0u) state[CS_HELD] = m;     // read by later kernels only
+}
+
+// the groups (of G lanes, bit g * G) whose split is incompatible with the wave's own: every property has a lane
+__device__ inline unsigned long long cs_bad_groups(bool a_outside_b, bool b_outside_a, bool missing, unsigned G)
+{
+  unsigned long long x = __ballot(a_outside_b), y = __ballot(b_outside_a), z = __ballot(missing);
+  for (unsigned s = 1; s < G; s <<= 1) { x |= x >> s; y |= y >> s; z |= z >> s; }
+  return x & y & z;
+}
+
+__device__ inline unsigned long long cs_group_heads(unsigned G)
+{
+  unsigned long long m = 0;
+  for (unsigned b = 0; b < 64u; b += G) m |= 1ULL << b;
+  return m;
+}
+
+// `mine` against rows[0 .. count), 64 / G of them at a time: true when compatible with all; it stops after the first
+// group that holds an incompatible row.  tests += rows looked at.
+__device__ inline bool cs_against(const uint32_t * __restrict__ mine, const uint32_t * __restrict__ rows, unsigned count,
+                                  unsigned len, uint32_t last, unsigned G, unsigned lane, unsigned long long & tests)
+{
+  const unsigned per = 64u / G, sub = lane / G, w0 = lane % G;
+  const unsigned long long heads = cs_group_heads(G);
+  for (unsigned base = 0; base < count; base += per)
+  {
+    const unsigned s = base + sub;
+    bool f1 = false, f2 = false, f3 = false;
+    if (s < count)
+      for (unsigned w = w0; w < len; w += G)
+      {
+        const uint32_t a = mine[w], b = rows[(size_t)s * len + w];
+        f1 |= (a & ~b) != 0u;
+        f2 |= (b & ~a) != 0u;
+        f3 |= (~(a | b) & (w + 1u == len ? last : 0xffffffffu)) != 0u;
+      }
+    tests += min(per, count - base);
+    if (cs_bad_groups(f1, f2, f3, G) & heads) return false;
+  }
+  return true;
+}
+
+// a wave per candidate rank[first + i], i < n: survives[i] = compatible with accepted[0 .. held)
+__global__ __launch_bounds__(TS_WG) void k_cs_filter(const CsEntry * __restrict__ rank, unsigned first, unsigned n,
+                                                     const uint32_t * __restrict__ store, const uint32_t * __restrict__ accepted,
+                                                     unsigned len, unsigned T, unsigned R, unsigned G,
+                                                     const unsigned * __restrict__ state, unsigned * __restrict__ survives,
+                                                     unsigned long long * tests)
+{
+  const unsigned held = state[CS_HELD], lane = threadIdx.x & 63u;
+  if (held >= R) return;
+  const uint32_t last = (T & 31u) ? ((1u << (T & 31u)) - 1u) : 0xffffffffu;
+  unsigned long long done = 0;
+  for (unsigned i = blockIdx.x * 4u + (threadIdx.x >> 6); i < n; i += gridDim.x * 4u)
+  {
+    const uint32_t * mine = store + (size_t)rank[first + i].id * len;
+    const bool ok = cs_against(mine, accepted, held, len, last, G, lane, done);
+    if (lane == 0u) survives[i] = ok ? 1u : 0u;
+  }
+  if (lane == 0u && done) atomicAdd(tests, done);
+}
+
+// a wave per candidate i of the block: conflict[i][w], bit j % 32 of word j / 32 = survivors i and j < i are
+// incompatible.  rowwords = ceil(n / 32) <= 64
+__global__ __launch_bounds__(TS_WG) void k_cs_pairs(const CsEntry * __restrict__ rank, unsigned first, unsigned n,
+                                                    const uint32_t * __restrict__ store, unsigned len, unsigned T, unsigned R,
+                                                    unsigned G, const unsigned * __restrict__ state,
+                                                    const unsigned * __restrict__ survives, uint32_t * __restrict__ conflict,
+                                                    unsigned rowwords, unsigned long long * tests)
+{
+  const unsigned lane = threadIdx.x & 63u;
+  if (state[CS_HELD] >= R) return;
+  const uint32_t last = (T & 31u) ? ((1u << (T & 31u)) - 1u) : 0xffffffffu;
+  const unsigned per = 64u / G, sub = lane / G, w0 = lane % G;
+  const unsigned long long heads = cs_group_heads(G);
+  unsigned long long done = 0;
+  for (unsigned i = blockIdx.x * 4u + (threadIdx.x >> 6); i < n; i += gridDim.x * 4u)
+  {
+    uint32_t row = 0;                                          // lane w holds word w of the row
+    if (survives[i])
+    {
+      const uint32_t * mine = store + (size_t)rank[first + i].id * len;
+      for (unsigned base = 0; base < i; base += per)
+      {
+        const unsigned j = base + sub;
+        const bool live = j < i && survives[j] != 0u;
+        bool f1 = false, f2 = false, f3 = false;
+        if (live)
+        {
+          const uint32_t * other = store + (size_t)rank[first + j].id * len;
+          for (unsigned w = w0; w < len; w += G)
+          {
+            const uint32_t a = mine[w], b = other[w];
+            f1 |= (a & ~b) != 0u;
+            f2 |= (b & ~a) != 0u;
+            f3 |= (~(a | b) & (w + 1u == len ? last : 0xffffffffu)) != 0u;
+          }
+        }
+        done += (unsigned long long)__popcll(__ballot(live) & heads);
+        unsigned long long bad = cs_bad_groups(f1, f2, f3, G) & heads;
+        for (; bad; bad &= bad - 1ULL)
+        {
+          const unsigned j_bad = base + ((unsigned)__ffsll((long long)bad) - 1u) / G;
+          if (lane == j_bad / 32u) row |= 1u << (j_bad % 32u);
+        }
+      }
+    }
+    if (lane < rowwords) conflict[(size_t)i * rowwords + lane] = row;
+  }
+  if (lane == 0u && done) atomicAdd(tests, done);
+}
+
+// one workgroup.  Wave 0 walks the block in rank order; then every thread appends the taken vectors.
+__global__ __launch_bounds__(TS_WG) void k_cs_resolve(const CsEntry * __restrict__ rank, unsigned first, unsigned n,
+                                                      const uint32_t * __restrict__ store, const unsigned * __restrict__ trees_with,
+                                                      unsigned len, unsigned R, const unsigned * __restrict__ survives,
+                                                      const uint32_t * __restrict__ conflict, unsigned rowwords,
+                                                      uint32_t * __restrict__ accepted, unsigned * __restrict__ acc_trees,
+                                                      unsigned * state)
+{
+  __shared__ unsigned short taken_at[CS_MAX_BLOCK];            // the block index of the k-th split taken
+  __shared__ unsigned ntaken;
+  const unsigned held = state[CS_HELD];
+  if (held >= R) return;
+  if (threadIdx.x < 64u)
+  {
+    const unsigned lane = threadIdx.x;
+    uint32_t taken = 0;                                        // lane w: word w of the set of survivors taken
+    unsigned count = 0;
+    for (unsigned base = 0; base < n && held + count < R; base += 64u)
+    {
+      // the survivors among 64 candidates at once: most rounds have few
+      unsigned long long live = __ballot(base + lane < n && survives[base + lane] != 0u);
+      for (; live && held + count < R; live &= live - 1ULL)
+      {
+        const unsigned i = base + (unsigned)__ffsll((long long)live) - 1u;
+        const uint32_t row = lane < rowwords ? conflict[(size_t)i * rowwords + lane] : 0u;
+        if (__ballot((row & taken) != 0u)) continue;
+        if (lane == i / 32u) taken |= 1u << (i % 32u);
+        if (lane == 0u) taken_at[count] = (unsigned short)i;
+        ++count;
+      }
+    }
+    if (lane == 0u) ntaken = count;
+  }
+  __syncthreads();
+  const unsigned count = ntaken;
+  for (unsigned at = threadIdx.x; at < count * len; at += TS_WG)
+  {
+    const unsigned k = at / len, w = at % len, id = rank[first + taken_at[k]].id;
+    accepted[(size_t)(held + k) * len + w] = store[(size_t)id * len + w];
+    if (w == 0u) acc_trees[held + k] = trees_with[id];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0u) state[CS_HELD] = held + count;
 }
 
 } // namespace pllhip

@@ -1,6 +1,7 @@
 // pll_treeset_dev.hip -- pllhip_treeset_*: a set of trees on the device and what is computed from it: normalised
-// splits, Robinson-Foulds distances, Felsenstein and transfer bootstrap support (kernels_treeset.hpp; host side:
-// host/pllhip_treeset.c; contract: INTEGRATION.md, "Split support and tree distances"; design: DESIGN.md section 16).
+// splits, Robinson-Foulds distances, Felsenstein and transfer bootstrap support, and the consensus of the set
+// (kernels_treeset.hpp; host side: host/pllhip_treeset.c, host/pllhip_consensus.c; contract: INTEGRATION.md, "Split
+// support and tree distances"; design: DESIGN.md sections 16 and 17).
 //
 // The host keeps every tree's split plan and transfer program (O(T) each); pllhip_treeset_add touches no device.  The
 // device holds a cache of them: the programs, the distinct splits' bit vectors, the hash table over those and every
@@ -46,6 +47,7 @@ namespace {
 thread_local double g_last_ms[3] = {0.0, 0.0, 0.0};
 thread_local unsigned long long g_last_counts[2] = {0, 0};
 thread_local std::vector<unsigned long long> g_last_sums;
+thread_local unsigned long long g_last_consensus[2] = {0, 0};
 
 void drop_cache(pllhip_treeset * ts)
 {
@@ -359,6 +361,141 @@ bool check_set(const pllhip_treeset * ts, const void * a, const void * b, const 
   return true;
 }
 
+// PLLHIP_CONSENSUS_BLOCK=<1..2048>: candidates per round of the greedy selection (a test knob; no result changes)
+unsigned consensus_block()
+{
+  const char * env = getenv("PLLHIP_CONSENSUS_BLOCK");
+  const long k = env && *env ? atol(env) : 1024L;
+  return (unsigned)std::max(1L, std::min(k, (long)CS_MAX_BLOCK));
+}
+
+struct Consensus
+{
+  unsigned count = 0;
+  std::vector<uint32_t> words;                                 // [count][len], in rank order
+  std::vector<unsigned> trees;                                 // [count]
+  unsigned long long tests[2] = {0, 0};
+};
+
+// the consensus split system of the set: ranking and selection on the device (kernels_treeset.hpp, k_cs_*)
+bool run_consensus(pllhip_treeset * ts, double threshold, const char * who, Consensus & out)
+{
+  if (!ts)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "%s: NULL argument", who);
+    return false;
+  }
+  if (!(threshold >= 0.0 && threshold <= 1.0))
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "%s: threshold %g is outside [0, 1]", who, threshold);
+    return false;
+  }
+  if (!ts->count)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "%s: the tree set is empty", who);
+    return false;
+  }
+  unsigned need_major = 0, need_minor = 0;
+  if (!pllhip_ts_consensus_needs(ts->count, threshold, &need_major, &need_minor)) return false;
+  const unsigned T = ts->T, R = ts->R, len = ts->len;
+  unsigned G = 1;
+  while (G < len && G < 64u) G <<= 1;
+  const unsigned block = consensus_block(), rowwords_max = (block + 31u) / 32u;
+
+  Job j;
+  if (!j.open(ts)) return false;
+  if (!sync_cache(ts, j)) { drop_cache(ts); return false; }
+  const unsigned D = ts->ndistinct;
+  size_t cap = 1;
+  while (cap < D) cap <<= 1;
+  CsEntry * d_rank = nullptr;
+  unsigned * d_state = nullptr, * d_acc_trees = nullptr, * d_survives = nullptr;
+  unsigned long long * d_tests = nullptr;
+  uint32_t * d_accepted = nullptr, * d_conflict = nullptr;
+  unsigned state[4] = {0, 0, 0, 0};
+  bool ok = j.temp(&d_rank, cap, "the ranked candidates") && j.temp(&d_state, 4, "consensus state") &&
+            j.temp(&d_tests, 2, "consensus counters") && j.temp(&d_accepted, (size_t)R * len, "accepted splits") &&
+            j.temp(&d_acc_trees, R, "accepted counts") && j.temp(&d_survives, block, "survivors") &&
+            j.temp(&d_conflict, (size_t)block * rowwords_max, "the conflict matrix");
+  ok = ok && j.start() && hip_ok(hipMemsetAsync(d_state, 0, 4 * sizeof(unsigned), j.stream), "memset") &&
+       hip_ok(hipMemsetAsync(d_tests, 0, 2 * sizeof(unsigned long long), j.stream), "memset");
+  if (!ok) { drop_cache(ts); return false; }
+  hipLaunchKernelGGL(k_cs_candidates, dim3(grid_for(D, TS_WG)), dim3(TS_WG), 0, j.stream, (const unsigned *)ts->d_trees_with,
+                     (const uint32_t *)ts->d_store, len, D, need_major, need_minor, d_rank, d_state);
+  if (!j.down(state, d_state, sizeof(state)) || !j.stop(1, "consensus candidates")) { drop_cache(ts); return false; }
+  const unsigned ncand = state[CS_NCAND], nmajor = state[CS_NMAJOR];
+  if (ncand > D || nmajor > R || nmajor > ncand)
+  {
+    set_error(PLL_ERROR_HIP_RUNTIME, "%s: %u candidates of %u splits, %u of them in a majority of trees; a tree has %u",
+              who, ncand, D, nmajor, R);
+    drop_cache(ts);
+    return false;
+  }
+  unsigned n = 1;
+  while (n < ncand) n <<= 1;
+
+  if (!j.start()) { drop_cache(ts); return false; }
+  hipLaunchKernelGGL(k_cs_pad, dim3(grid_for(n - ncand, TS_WG)), dim3(TS_WG), 0, j.stream, d_rank, (const unsigned *)d_state, n);
+  {
+    const unsigned tiles = grid_for(n, 2u * TS_WG);
+    const uint32_t * store = ts->d_store;
+    hipLaunchKernelGGL(k_cs_sort_local, dim3(tiles), dim3(TS_WG), 0, j.stream, d_rank, n, 2u, std::min(n, 2u * TS_WG), store, len);
+    for (unsigned k = 4u * TS_WG; k <= n && k; k <<= 1)
+    {
+      for (unsigned step = k >> 1; step > TS_WG; step >>= 1)
+        hipLaunchKernelGGL(k_cs_sort_step, dim3(grid_for(n, TS_WG)), dim3(TS_WG), 0, j.stream, d_rank, n, k, step, store, len);
+      hipLaunchKernelGGL(k_cs_sort_local, dim3(tiles), dim3(TS_WG), 0, j.stream, d_rank, n, k, k, store, len);
+    }
+  }
+  hipLaunchKernelGGL(k_cs_take_majority, dim3(grid_for((size_t)nmajor * len, TS_WG)), dim3(TS_WG), 0, j.stream,
+                     (const CsEntry *)d_rank, (const uint32_t *)ts->d_store, (const unsigned *)ts->d_trees_with, len, R,
+                     d_accepted, d_acc_trees, d_state);
+  unsigned held = nmajor;
+  if (threshold < 0.5)
+  {
+    // the selection stops by itself once R splits are held (the kernels return at once); the host looks now and then
+    unsigned rounds = 0;
+    for (unsigned first = nmajor; first < ncand && held < R; first += block)
+    {
+      const unsigned nb = std::min(block, ncand - first), rowwords = (nb + 31u) / 32u;
+      hipLaunchKernelGGL(k_cs_filter, dim3(grid_for(nb, 4)), dim3(TS_WG), 0, j.stream, (const CsEntry *)d_rank, first, nb,
+                         (const uint32_t *)ts->d_store, (const uint32_t *)d_accepted, len, T, R, G, (const unsigned *)d_state,
+                         d_survives, d_tests);
+      hipLaunchKernelGGL(k_cs_pairs, dim3(grid_for(nb, 4)), dim3(TS_WG), 0, j.stream, (const CsEntry *)d_rank, first, nb,
+                         (const uint32_t *)ts->d_store, len, T, R, G, (const unsigned *)d_state, (const unsigned *)d_survives,
+                         d_conflict, rowwords, d_tests + 1);
+      hipLaunchKernelGGL(k_cs_resolve, dim3(1), dim3(TS_WG), 0, j.stream, (const CsEntry *)d_rank, first, nb,
+                         (const uint32_t *)ts->d_store, (const unsigned *)ts->d_trees_with, len, R, (const unsigned *)d_survives,
+                         (const uint32_t *)d_conflict, rowwords, d_accepted, d_acc_trees, d_state);
+      if (++rounds % 8u == 0u)
+      {
+        if (!j.down(state, d_state, sizeof(state)) || !hip_ok(hipStreamSynchronize(j.stream), "consensus selection"))
+        { drop_cache(ts); return false; }
+        held = state[CS_HELD];
+      }
+    }
+  }
+  if (!j.down(state, d_state, sizeof(state)) || !j.stop(1, "consensus kernels")) { drop_cache(ts); return false; }
+  held = state[CS_HELD];
+  if (held > R)
+  {
+    set_error(PLL_ERROR_HIP_RUNTIME, "%s: %u splits held, a tree has %u", who, held, R);
+    drop_cache(ts);
+    return false;
+  }
+  out.count = held;
+  out.words.assign((size_t)held * len, 0u);
+  out.trees.assign(held, 0u);
+  if (!j.start() || (held && (!j.down(out.words.data(), d_accepted, (size_t)held * len * 4u) ||
+                              !j.down(out.trees.data(), d_acc_trees, (size_t)held * sizeof(unsigned)))) ||
+      !j.down(out.tests, d_tests, sizeof(out.tests)) || !j.stop(2, "download"))
+  { drop_cache(ts); return false; }
+  j.commit();
+  g_last_consensus[0] = out.tests[0];
+  g_last_consensus[1] = out.tests[1];
+  return true;
+}
+
 } // namespace
 
 extern "C" {
@@ -604,6 +741,69 @@ PLL_EXPORT int pllhip_treeset_support(pllhip_treeset_t * ts, const pll_utree_t *
   }
   g_last_sums = sums;
   return PLL_SUCCESS;
+}
+
+PLL_EXPORT int pllhip_treeset_consensus(pllhip_treeset_t * ts, double threshold, unsigned int * out_count,
+                                        unsigned int * out_words, unsigned int * out_trees, double * out_support)
+{
+  try
+  {
+    Consensus c;
+    if (!run_consensus(ts, threshold, "pllhip_treeset_consensus", c)) return PLL_FAILURE;
+    if (out_count) *out_count = c.count;
+    if (out_words && c.count) memcpy(out_words, c.words.data(), c.words.size() * 4u);
+    for (unsigned i = 0; i < c.count; ++i)
+    {
+      if (out_trees) out_trees[i] = c.trees[i];
+      if (out_support) out_support[i] = (double)c.trees[i] / (double)ts->count;      // the one division per split
+    }
+    return PLL_SUCCESS;
+  }
+  catch (const std::bad_alloc &)
+  {
+    set_error(PLL_ERROR_MEM_ALLOC, "pllhip_treeset_consensus: out of memory");
+    return PLL_FAILURE;
+  }
+}
+
+PLL_EXPORT pll_utree_t * pllhip_treeset_tree_from_splits(const pllhip_treeset_t * ts, unsigned int count,
+                                                         const unsigned int * words, const double * support)
+{
+  if (!ts)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "pllhip_treeset_tree_from_splits: NULL argument");
+    return nullptr;
+  }
+  return pllhip_ts_tree_from_splits(ts->T, ts->labels, count, words, support);
+}
+
+PLL_EXPORT pll_utree_t * pllhip_treeset_consensus_tree(pllhip_treeset_t * ts, double threshold)
+{
+  try
+  {
+    Consensus c;
+    if (!run_consensus(ts, threshold, "pllhip_treeset_consensus_tree", c)) return nullptr;
+    std::vector<double> support(c.count);
+    for (unsigned i = 0; i < c.count; ++i) support[i] = (double)c.trees[i] / (double)ts->count;
+    return pllhip_ts_tree_from_splits(ts->T, ts->labels, c.count, c.words.data(), support.data());
+  }
+  catch (const std::bad_alloc &)
+  {
+    set_error(PLL_ERROR_MEM_ALLOC, "pllhip_treeset_consensus_tree: out of memory");
+    return nullptr;
+  }
+}
+
+PLL_EXPORT int pllhip_consensus_needs(unsigned int tree_count, double threshold, unsigned int * need_major,
+                                      unsigned int * need_minor)
+{
+  return pllhip_ts_consensus_needs(tree_count, threshold, need_major, need_minor);
+}
+
+PLL_EXPORT void pllhip_treeset_last_consensus_counts(unsigned long long * accepted_tests, unsigned long long * pair_tests)
+{
+  if (accepted_tests) *accepted_tests = g_last_consensus[0];
+  if (pair_tests) *pair_tests = g_last_consensus[1];
 }
 
 PLL_EXPORT unsigned int pllhip_treeset_last_sums(unsigned long long * out, unsigned int count)

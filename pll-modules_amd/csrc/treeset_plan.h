@@ -56,6 +56,8 @@ pllhip_ts_labels_t * pllhip_ts_labels_create(unsigned int tip_count, const char 
 void pllhip_ts_labels_destroy(pllhip_ts_labels_t * table);
 /* -1: unknown */
 long pllhip_ts_labels_find(const pllhip_ts_labels_t * table, const char * label);
+/* the label of tip `id`; NULL: no such tip */
+const char * pllhip_ts_labels_get(const pllhip_ts_labels_t * table, unsigned int id);
 
 /* order [T - 1], lo, hi, edge [T - 3] (edge may be NULL: the record of every inner edge in the caller's tree, on the
  * side away from tip 0), program [2T - 3].  *max_stack: the deepest stack the program reaches.  The tree is only read.
@@ -70,6 +72,28 @@ void pllhip_ts_plan_splits(unsigned int tip_count, const uint32_t * order, const
                            uint32_t * words, uint64_t * hash);
 /* perm [count]: the indices of the splits ascending by words compared as unsigned, word 0 first */
 void pllhip_ts_sort_splits(unsigned int tip_count, unsigned int count, const uint32_t * words, uint32_t * perm);
+
+/* ---- consensus (host/pllhip_consensus.c; device: kernels_treeset.hpp, k_cs_*) ---- */
+
+/* The integer thresholds of a consensus over B trees.  A split held by c trees is in outright when c >= *need_major
+ * and is a candidate at all when c >= *need_minor (<= *need_major).  threshold 1.0: need_major = B.  A cut
+ * max(threshold, 0.5) of exactly 0.5: the smallest c with 2c > B.  Any other cut: the smallest c for which the one
+ * correctly rounded quotient (double)c / (double)B is greater than the cut.  need_minor = need_major for a threshold
+ * >= 0.5, 1 for 0.0, and else the smallest c with (double)c / (double)B > threshold.
+ * PLL_FAILURE with PLL_ERROR_PARAM_INVALID for B = 0 or a threshold outside [0, 1] (NaN included). */
+int pllhip_ts_consensus_needs(unsigned int tree_count, double threshold, unsigned int * need_major,
+                              unsigned int * need_minor);
+
+/* The unrooted, possibly multifurcating tree of `count` (0 .. T - 3) pairwise compatible, distinct, non-trivial splits
+ * in normal form (bit 0 of word 0 set, unused high bits clear): words [count][ceil(T / 32)], support [count] or NULL.
+ * Tips carry node_index = clv_index = tip id and the table's label (labels may be NULL: no labels).  The inner node on
+ * the side of a split's edge away from tip 0 carries the split's support as its label, in the shortest decimal form
+ * that reads back as the same double; every record of that node points to the one string, as pll_utree_clone
+ * leaves it, so pll_utree_destroy(tree, NULL) frees everything.  vroot is tip 0's neighbour; count = 0 gives the star.
+ * NULL with PLL_ERROR_PARAM_INVALID (a split that is not in normal form, trivial, given twice, or incompatible with
+ * another) or PLL_ERROR_MEM_ALLOC. */
+pll_utree_t * pllhip_ts_tree_from_splits(unsigned int tip_count, const pllhip_ts_labels_t * labels, unsigned int count,
+                                         const uint32_t * words, const double * support);
 
 #ifdef __cplusplus
 }

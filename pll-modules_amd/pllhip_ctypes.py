@@ -191,7 +191,9 @@ pllhip_empirical_frequencies pllhip_empirical_subst_rates pllhip_empirical_invar
 pllhip_msa_compute_stats pllhip_msa_destroy_stats pllhip_msa_stats_last_times
 pllhip_treeset_create pllhip_treeset_destroy pllhip_treeset_count pllhip_treeset_add pllhip_treeset_splits
 pllhip_treeset_rf_matrix pllhip_treeset_rf_to pllhip_treeset_support pllhip_treeset_last_sums pllhip_treeset_plan
-pllhip_treeset_last_times pllhip_treeset_last_counts""".split()
+pllhip_treeset_last_times pllhip_treeset_last_counts
+pllhip_treeset_consensus pllhip_treeset_consensus_tree pllhip_treeset_tree_from_splits pllhip_consensus_needs
+pllhip_treeset_last_consensus_counts""".split()
 
 
 def _u32(a):
@@ -435,6 +437,16 @@ class PllLib:
             L.pllhip_treeset_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
             L.pllhip_treeset_last_counts.restype = None
             L.pllhip_treeset_last_counts.argtypes = [ull_p, ull_p]
+        if hasattr(L, "pllhip_treeset_consensus"):
+            ull_p = C.POINTER(C.c_ulonglong)
+            L.pllhip_treeset_consensus.argtypes = [C.c_void_p, C.c_double, c_uint_p, c_uint_p, c_uint_p, c_double_p]
+            L.pllhip_treeset_consensus_tree.restype = tp
+            L.pllhip_treeset_consensus_tree.argtypes = [C.c_void_p, C.c_double]
+            L.pllhip_treeset_tree_from_splits.restype = tp
+            L.pllhip_treeset_tree_from_splits.argtypes = [C.c_void_p, C.c_uint, c_uint_p, c_double_p]
+            L.pllhip_consensus_needs.argtypes = [C.c_uint, C.c_double, c_uint_p, c_uint_p]
+            L.pllhip_treeset_last_consensus_counts.restype = None
+            L.pllhip_treeset_last_consensus_counts.argtypes = [ull_p, ull_p]
         if hasattr(L, "pllhip_newton_branch"):
             L.pllhip_newton_branch.argtypes = [pp, C.c_int, C.c_int, c_uint_p, c_double_p, C.c_double, C.c_double,
                                                C.c_double, C.c_double, C.c_uint, c_double_p, c_uint_p, c_double_p]
@@ -1100,6 +1112,15 @@ def utree_splits(tree):
 
 
 SUPPORT_FBP, SUPPORT_TBE = 0, 1
+_libc_free = C.CDLL(None).free
+_libc_free.restype, _libc_free.argtypes = None, [C.c_void_p]
+
+
+def consensus_needs(lib, tree_count, threshold):
+    """(need_major, need_minor) of pllhip_consensus_needs, or None"""
+    a, b = C.c_uint(0), C.c_uint(0)
+    return (a.value, b.value) if lib.lib.pllhip_consensus_needs(tree_count, threshold, C.byref(a), C.byref(b)) else None
+
 PLL_ERROR_MEM_ALLOC, PLL_ERROR_PARAM_INVALID, PLL_ERROR_TREE_INVALID = 112, 113, 133
 PLL_ERROR_HIP_RUNTIME, PLL_ERROR_HIP_NODEVICE = 900, 901
 
@@ -1198,6 +1219,39 @@ class TreeSet:
         sums = np.zeros(R, np.uint64)
         self.L.pllhip_treeset_last_sums(sums.ctypes.data_as(C.POINTER(C.c_ulonglong)), R)
         return (out, sums, sides) if with_map else (out, sums)
+
+    def consensus(self, threshold):
+        """(words [K, len], trees [K], support [K]) of the consensus split system in rank order, or None"""
+        R, K = self.T - 3, C.c_uint(0)
+        words, trees, support = np.zeros((R, self.words), np.uint32), np.zeros(R, np.uint32), np.zeros(R, np.float64)
+        ok = self.L.pllhip_treeset_consensus(self.h, threshold, C.byref(K), words.ctypes.data_as(c_uint_p),
+                                             trees.ctypes.data_as(c_uint_p), support.ctypes.data_as(c_double_p))
+        return (words[:K.value].copy(), trees[:K.value].copy(), support[:K.value].copy()) if ok else None
+
+    def _newick_of(self, tree):
+        if not tree:
+            return None
+        text = self.L.pll_utree_export_newick(tree.contents.vroot, None)
+        out = C.string_at(text).decode()
+        _libc_free(text)
+        self.L.pll_utree_destroy(tree, None)
+        return out
+
+    def consensus_newick(self, threshold):
+        """the consensus tree as Newick, supports as inner labels; None on failure"""
+        return self._newick_of(self.L.pllhip_treeset_consensus_tree(self.h, threshold))
+
+    def newick_from_splits(self, words, support=None):
+        """the tree of a system of compatible splits (host only), as Newick; None on failure"""
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, self.words)
+        sup = None if support is None else np.ascontiguousarray(support, dtype=np.float64)
+        return self._newick_of(self.L.pllhip_treeset_tree_from_splits(
+            self.h, len(words), words.ctypes.data_as(c_uint_p), None if sup is None else sup.ctypes.data_as(c_double_p)))
+
+    def last_consensus_counts(self):
+        a, b = C.c_ulonglong(0), C.c_ulonglong(0)
+        self.L.pllhip_treeset_last_consensus_counts(C.byref(a), C.byref(b))
+        return a.value, b.value
 
     def last_times(self):
         up, kern, down = C.c_double(0), C.c_double(0), C.c_double(0)
