@@ -120,10 +120,17 @@ static double * tip_lookup(const pll_partition_t * p, const double * P)
  * ------------------------------------------------------------------------- */
 typedef double orc_v4 __attribute__((vector_size(32), aligned(8)));
 
+/* partitions of several host threads ask at once: read until one thread has published the value */
 static int orc_fast(void)
 {
-  static int on = -1;
-  if (on < 0) { const char * e = getenv("ORC_FAST"); on = (e && atoi(e)) ? 1 : 0; }
+  static int flag = -1;
+  int on = __atomic_load_n(&flag, __ATOMIC_RELAXED);
+  if (on < 0)
+  {
+    const char * e = getenv("ORC_FAST");
+    on = (e && atoi(e)) ? 1 : 0;
+    __atomic_store_n(&flag, on, __ATOMIC_RELAXED);
+  }
   return on;
 }
 

@@ -416,12 +416,21 @@ static double edge_loglh(pllhip_eval_t * ev, const pll_unode_t * e, int failed)
 }
 
 /* PLLHIP_EVAL_FAULT=N (+ PLLHIP_EVAL_FAULT_RANK is up to the caller: set the variable on one worker only):
-   the N-th evaluation of this process fails before its reduction -- for the tests of the path above */
+   the N-th evaluation of this process fails before its reduction -- for the tests of the path above.
+   Evaluators of several host threads come through here at once: the variable is read until one thread has
+   published its value (all of them would publish the same), the evaluations of the process are counted atomically */
 static int injected_fault(void)
 {
   static long at = -1, n = 0;
-  if (at < 0) { const char * e = getenv("PLLHIP_EVAL_FAULT"); at = e ? atol(e) : 0; }
-  if (at > 0 && ++n == at)
+  long a = __atomic_load_n(&at, __ATOMIC_RELAXED);
+  if (a < 0)
+  {
+    const char * e = getenv("PLLHIP_EVAL_FAULT");
+    a = e ? atol(e) : 0;
+    if (a < 0) a = 0;
+    __atomic_store_n(&at, a, __ATOMIC_RELAXED);
+  }
+  if (a > 0 && __atomic_add_fetch(&n, 1, __ATOMIC_RELAXED) == a)
   {
     pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "injected evaluation failure");
     return 1;

@@ -25,11 +25,18 @@
 #include "pllhip_eval_internal.h"
 #include <stdio.h>
 
-/* PLLHIP_SPR_TRACE=1: one line per scan / applied move / re-scored topology on stderr */
+/* PLLHIP_SPR_TRACE=1: one line per scan / applied move / re-scored topology on stderr
+   (read until one thread has published the value: rounds of several host threads ask at once) */
 static int trace_on(void)
 {
-  static int on = -1;
-  if (on < 0) { const char * e = getenv("PLLHIP_SPR_TRACE"); on = (e && atoi(e)) ? 1 : 0; }
+  static int flag = -1;
+  int on = __atomic_load_n(&flag, __ATOMIC_RELAXED);
+  if (on < 0)
+  {
+    const char * e = getenv("PLLHIP_SPR_TRACE");
+    on = (e && atoi(e)) ? 1 : 0;
+    __atomic_store_n(&flag, on, __ATOMIC_RELAXED);
+  }
   return on;
 }
 #define TRACE(...) do { if (trace_on()) fprintf(stderr, "[spr] " __VA_ARGS__); } while (0)

@@ -697,9 +697,9 @@ static unsigned s16_table(const Engine * e)
 // beyond 16 states with many rates the tables pass the 64 KiB a kernel gets without asking
 static int s16_allow_lds(Engine * e)
 {
-  static bool attr_set_dev[64] = {false};
-  bool & attr_set = attr_set_dev[e->device & 63];
-  if (attr_set) return PLL_SUCCESS;
+  static std::atomic<bool> attr_set_dev[64];
+  std::atomic<bool> & attr_set = attr_set_dev[e->device & 63];
+  if (attr_set.load(std::memory_order_acquire)) return PLL_SUCCESS;
 #define PLLHIP_ATTR(KK) \
   do { \
     PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_partials_s16<KK>), hipFuncAttributeMaxDynamicSharedMemorySize, S16_MAX_LDS_BYTES)); \
@@ -707,7 +707,7 @@ static int s16_allow_lds(Engine * e)
   } while (0)
   PLLHIP_ATTR(5); PLLHIP_ATTR(6); PLLHIP_ATTR(7); PLLHIP_ATTR(8);
 #undef PLLHIP_ATTR
-  attr_set = true;
+  attr_set.store(true, std::memory_order_release);
   return PLL_SUCCESS;
 }
 
@@ -762,8 +762,8 @@ static int launch_traverse_s16(Engine * e, const PlanView & plan, unsigned lds_d
                                  (extent + 16u * S16_CHAIN_WAVES - 1) / (16u * S16_CHAIN_WAVES));
   static const int env_nt = getenv("PLLHIP_S16_NT") ? atoi(getenv("PLLHIP_S16_NT")) : 2;   // stores and loads past the caches: 3 - 15 % faster
   const unsigned nt_flags = (env_nt ? 2u : 0u) | (env_nt == 2 ? 4u : 0u);
-  static bool attr_set_dev[64] = {false};
-  bool & attr_set = attr_set_dev[e->device & 63];
+  static std::atomic<bool> attr_set_dev[64];
+  std::atomic<bool> & attr_set = attr_set_dev[e->device & 63];
   const int cap = (int)(sizeof(double) * S16_CHAIN_LDS);
 #define PLLHIP_ATTR(KK) \
   do { \
@@ -771,11 +771,11 @@ static int launch_traverse_s16(Engine * e, const PlanView & plan, unsigned lds_d
     PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_traverse_s16<KK, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
     PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_traverse_s16<KK, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap)); \
   } while (0)
-  if (!attr_set)
+  if (!attr_set.load(std::memory_order_acquire))
   {
     PLLHIP_ATTR(1); PLLHIP_ATTR(2); PLLHIP_ATTR(3); PLLHIP_ATTR(4);
     PLLHIP_ATTR(5); PLLHIP_ATTR(6); PLLHIP_ATTR(7); PLLHIP_ATTR(8);
-    attr_set = true;
+    attr_set.store(true, std::memory_order_release);
   }
 #undef PLLHIP_ATTR
 #define PLLHIP_CALL(KK) \

@@ -1764,15 +1764,15 @@ static int launch_chains_s20(Engine * e, const ChainBatch & batch, unsigned ncha
   const size_t lds = sizeof(double) * lds_doubles;
   const unsigned env_flags = []() { const char * v = getenv("PLLHIP_S20_NT"); return v ? (unsigned)atoi(v) & 3u : 0u; }();
   const unsigned flags = env_flags | (s20_chain_lut_lds(e, lut_used) ? 8u : 0u);
-  static bool attr_set_dev[64] = {false};          // per device: one process may drive several GPUs
-  bool & attr_set = attr_set_dev[e->device & 63];
-  if (!attr_set)
+  static std::atomic<bool> attr_set_dev[64];          // per device: one process may drive several GPUs
+  std::atomic<bool> & attr_set = attr_set_dev[e->device & 63];
+  if (!attr_set.load(std::memory_order_acquire))
   {
     if (!s20_allow_full_lds(k_chain_s20<4, false>) || !s20_allow_full_lds(k_chain_s20<2, false>) ||
         !s20_allow_full_lds(k_chain_s20<1, false>) || !s20_allow_full_lds(k_chain_s20<4, true>) ||
         !s20_allow_full_lds(k_chain_s20<2, true>) || !s20_allow_full_lds(k_chain_s20<1, true>))
       return PLL_FAILURE;
-    attr_set = true;
+    attr_set.store(true, std::memory_order_release);
   }
   // workgroups per CU and chain (measured at 1 M sites: 1 beats 2 and 4)
   static const int env_bpc = getenv("PLLHIP_S20_CHAIN_BPC") ? atoi(getenv("PLLHIP_S20_CHAIN_BPC")) : 1;
@@ -1793,9 +1793,9 @@ static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_d
 {
   const size_t lds = sizeof(double) * lds_doubles;
   const unsigned flags = []() { const char * v = getenv("PLLHIP_S20_NT"); return v ? (unsigned)atoi(v) & 3u : 0u; }();
-  static bool attr_set_dev[64] = {false};
-  bool & attr_set = attr_set_dev[e->device & 63];
-  if (!attr_set)
+  static std::atomic<bool> attr_set_dev[64];
+  std::atomic<bool> & attr_set = attr_set_dev[e->device & 63];
+  if (!attr_set.load(std::memory_order_acquire))
   {
 #define PLLHIP_ALLOW(RS_, W_, T_, F_) (s20_allow_full_lds(k_traverse_s20<4, RS_, W_, T_, F_>) && s20_allow_full_lds(k_traverse_s20<2, RS_, W_, T_, F_>) && \
                                        s20_allow_full_lds(k_traverse_s20<1, RS_, W_, T_, F_>))
@@ -1804,7 +1804,7 @@ static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_d
         !PLLHIP_ALLOW(false, false, false, true) || !PLLHIP_ALLOW(false, false, true, true))
       return PLL_FAILURE;
 #undef PLLHIP_ALLOW
-    attr_set = true;
+    attr_set.store(true, std::memory_order_release);
   }
   const unsigned need = (extent + S20_CHAIN_WAVES - 1) / S20_CHAIN_WAVES;
   // (a row keeps at least the workgroups that leave a wave 16 site blocks: large partitions are shared out finely --

@@ -1178,9 +1178,9 @@ static int launch_partials_s61_cherries(Engine * e, const OpBatch & batch, const
 {
   if (nops > S61_V4_OPS) { set_error(PLL_ERROR_PARAM_INVALID, "cherry launch of %u operations", nops); return PLL_FAILURE; }
   const size_t lds = sizeof(double) * 4 * S61_FRAGS;
-  static bool attr_set_dev[64] = {false};
-  bool & attr_set = attr_set_dev[e->device & 63];
-  if (!attr_set)
+  static std::atomic<bool> attr_set_dev[64];
+  std::atomic<bool> & attr_set = attr_set_dev[e->device & 63];
+  if (!attr_set.load(std::memory_order_acquire))
   {
     PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_partials_s61v4<false, S61_S>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1190,7 +1190,7 @@ static int launch_partials_s61_cherries(Engine * e, const OpBatch & batch, const
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_partials_s61v4<true, 0>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
+    attr_set.store(true, std::memory_order_release);
   }
   bool scaling = false;
   for (unsigned i = 0; i < nops; ++i) scaling |= batch.op[i].parent_scaler != nullptr;
@@ -1251,13 +1251,13 @@ static int launch_edge_lnl_s61(Engine * e, const ModelView & mv, const ParamIdx 
   if (env_r4 && pm && !child.codes && e->R <= 4 && e->nblk && !e->rate_scalers)
   {
     const size_t lds = sizeof(double) * ((size_t)e->R * S61_FRAGS + (size_t)e->R * 64);
-    static bool attr_set_dev[64] = {false};        // per device: one process may drive several GPUs
-    bool & attr_set = attr_set_dev[e->device & 63];
-    if (!attr_set)
+    static std::atomic<bool> attr_set_dev[64];        // per device: one process may drive several GPUs
+    std::atomic<bool> & attr_set = attr_set_dev[e->device & 63];
+    if (!attr_set.load(std::memory_order_acquire))
     {
       PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_edge_lnl_s61_r4),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (S61_FRAGS + 64) * 8));
-      attr_set = true;
+      attr_set.store(true, std::memory_order_release);
     }
     const unsigned gx = std::max(1u, std::min({nblocks, e->cu_count, (e->nblk + 3) / 4}));
     hipLaunchKernelGGL(k_edge_lnl_s61_r4, dim3(gx), dim3(256), lds, e->stream,
@@ -1296,15 +1296,15 @@ static int launch_derivatives_s61(Engine * e, const ModelView & mv, const ParamI
   }
   if (lds > 64 * 1024)
   {
-    static bool attr_set_dev[64] = {false};        // per device: one process may drive several GPUs
-    bool & attr_set = attr_set_dev[e->device & 63];
-    if (!attr_set)
+    static std::atomic<bool> attr_set_dev[64];        // per device: one process may drive several GPUs
+    std::atomic<bool> & attr_set = attr_set_dev[e->device & 63];
+    if (!attr_set.load(std::memory_order_acquire))
     {
       PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_derivatives_mfma<S61_KS, S61_S>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
       PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_derivatives_mfma<S61_KS, 0>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-      attr_set = true;
+      attr_set.store(true, std::memory_order_release);
     }
   }
   if (e->S == S61_S)

@@ -3901,11 +3901,16 @@ static NewtonParams newton_params(double start, double bl_min, double bl_max, do
   // PLLHIP_NEWTON_SPIN_LIMIT: polls before a waiting workgroup gives up; PLLHIP_FAULT=newton_stall: workgroup 0 of
   // the next PLLHIP_FAULT_COUNT (default 1) launches never arrives (tests of the PLLHIP_ERROR_NEWTON_STUCK path)
   static const unsigned env_spin = getenv("PLLHIP_NEWTON_SPIN_LIMIT") ? (unsigned)strtoul(getenv("PLLHIP_NEWTON_SPIN_LIMIT"), nullptr, 10) : 0u;
-  static int stall_left = (getenv("PLLHIP_FAULT") && !strcmp(getenv("PLLHIP_FAULT"), "newton_stall"))
-                              ? (getenv("PLLHIP_FAULT_COUNT") ? atoi(getenv("PLLHIP_FAULT_COUNT")) : 1) : 0;
+  static std::atomic<int> stall_left{(getenv("PLLHIP_FAULT") && !strcmp(getenv("PLLHIP_FAULT"), "newton_stall"))
+                                         ? (getenv("PLLHIP_FAULT_COUNT") ? atoi(getenv("PLLHIP_FAULT_COUNT")) : 1) : 0};
   np.spin_limit = env_spin ? env_spin : NEWTON_SPIN_LIMIT;
   np.stall_block = ~0u;
-  if (stall_left > 0 && nblocks_first > 1) { --stall_left; np.stall_block = 0u; }
+  // (launches of the process, whichever thread makes them: the count goes down once per stalled launch)
+  if (nblocks_first > 1 && stall_left.load(std::memory_order_relaxed) > 0)
+  {
+    if (stall_left.fetch_sub(1, std::memory_order_relaxed) > 0) np.stall_block = 0u;
+    else stall_left.fetch_add(1, std::memory_order_relaxed);
+  }
   np.part = 0;
   np.nparts = 1;
   np.xscale = 1.0;

@@ -25,6 +25,7 @@ extern "C" {
 #include "host/pllhip_eval_internal.h"
 }
 #include <rccl/rccl.h>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -97,13 +98,13 @@ static bool fault_now(const char * kind, int rank)
 {
   static const char * spec = getenv("PLLHIP_FAULT");
   static const int only = getenv("PLLHIP_FAULT_RANK") ? atoi(getenv("PLLHIP_FAULT_RANK")) : -1;
-  static unsigned long counts[3] = {0, 0, 0};
+  static std::atomic<unsigned long> counts[3];          // events of the process, whichever thread meets them
   if (!spec || (only >= 0 && only != rank)) return false;
   const size_t kl = strlen(kind);
   if (strncmp(spec, kind, kl) != 0 || spec[kl] != '@') return false;
   const unsigned long at = strtoul(spec + kl + 1, nullptr, 10);
-  unsigned long & n = counts[kind[0] == 'd' ? 0 : kind[0] == 'c' ? 1 : 2];
-  return ++n == at;
+  std::atomic<unsigned long> & n = counts[kind[0] == 'd' ? 0 : kind[0] == 'c' ? 1 : 2];
+  return n.fetch_add(1, std::memory_order_relaxed) + 1 == at;
 }
 
 static ncclRedOp_t nccl_op(int op)
