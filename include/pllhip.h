@@ -183,6 +183,9 @@ typedef struct pllhip_schedule_stats
   unsigned int operations;             /* operations in them, folded cherries included */
   unsigned int inner_reads;            /* inner vectors that the chains read from memory */
   unsigned int folded_cherries;        /* cherries built in registers by the operation that reads them */
+  unsigned int lookup_children;        /* cherries and cherry x tip subtrees that the operation above them reads through a
+                                          table of their classes of tip codes instead of the stored vector (inner_reads
+                                          counts neither these nor the folded cherries) */
 } pllhip_schedule_stats_t;
 PLL_EXPORT int pllhip_schedule_stats(const pll_partition_t * partition, pllhip_schedule_stats_t * out);
 

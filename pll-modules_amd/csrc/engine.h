@@ -105,6 +105,9 @@ struct PlanOp
                          // bit 3: a cherry that the NEXT entry builds in registers instead of reading its vector
                          // (20 states; slot1 / slot2 = its tip tables, the scaling decisions per code pair behind them)
                          // bit 4: child 2 of this entry is the folded cherry in front of it
+                         // bit 5: child 2 is read through its class table (20 states, plan_lookups): clv2 / pmat2 /
+                         // pfrag2 = the byte codes of the two or three tips below it (pfrag2 null: two), lut2 = its rows
+                         // [rate][child2_index classes][20], scaler2 = its scaler counts per class
 };
 // operations [first, first + len) of PlanOp[], and what the kernels need to know about the partition
 // the chain belongs to (a batched schedule -- pllhip_update_partials_batch -- holds chains of several
@@ -138,6 +141,7 @@ struct DevicePlan                                 // the schedule resident on th
   unsigned nops = 0, nchains = 0, lds_doubles = 0;
   unsigned nfolds = 0;                            // lone cherries folded into the chains that read them (PlanOp::flags bit 3)
   unsigned inner_reads = 0;                       // inner vectors that the chains read from memory
+  unsigned nlookups = 0;                          // children read through their class tables (PlanOp::flags bit 5)
   double algo_bytes = 0.0, algo_flops = 0.0;      // algorithmic traffic / work of the traversal
   double min_bytes = 0.0;                         // traffic without the child vectors handed over in registers
   // launches of the schedule: one for a whole traversal, or one per round of chains (chains
@@ -232,6 +236,10 @@ struct Engine
   unsigned * h_class_total = nullptr; // pinned: the class count read back once per new map
   double * d_pairlut = nullptr;       // lookup tables of the wide tips of the resident schedule
   size_t pairlut_cap = 0;
+  // class tables, rows and scaler counts of the children that the resident schedule reads by tip codes (plan_lookups):
+  // allocated with the schedule, filled by every traversal that runs it
+  unsigned char * d_looktab = nullptr;
+  size_t looktab_cap = 0;
   pllhip_repeat_stats_t repeat_stats = {};
   // Evaluate-only traversals (pllhip_set_transient): a resident schedule may hand the vectors inside its chains on
   // in registers without storing them.  Such a vector stays recomputable -- the operation that made it is kept --

@@ -754,7 +754,7 @@ static unsigned s16_chain_slot(const Engine * e, bool tip)
 // wide: the schedule may hold wide tips (site repeats; per-site scaling only).  (An evaluate-only traversal needs no
 // instantiation of its own: the kernel reads PlanOp::flags bit 0 at run time, whatever `transient` says.)
 static int launch_traverse_s16(Engine * e, const PlanView & plan, unsigned lds_doubles, unsigned extent, unsigned chain_begin,
-                               unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu, bool wide, bool /*transient*/, bool /*fold*/)
+                               unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu, bool wide, bool /*transient*/, bool /*fold*/, bool /*look*/)
 {
   const size_t lds = sizeof(double) * lds_doubles;
   const unsigned need = (extent + S16_CHAIN_WAVES - 1) / S16_CHAIN_WAVES;

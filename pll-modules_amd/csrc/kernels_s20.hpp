@@ -471,6 +471,9 @@ __host__ __device__ inline unsigned s20_tip_slot(unsigned R, unsigned lut_used)
   return (R * lut_used * S20_LUT_RS + 7u) & ~7u;
 }
 
+// the most classes of a child read through its class table: two class codes share a register (s20_chain_op, LOOK)
+constexpr unsigned S20_LOOK_MAX = 65535;
+
 // LDS doubles of the scaling decisions of a folded cherry: one bit per pair of tip codes
 __host__ __device__ inline unsigned s20_fold_bits_lds(unsigned lut_used)
 {
@@ -545,16 +548,24 @@ __device__ inline const unsigned * s20_wide_codes(const double * clv, const uint
 // counts are what the cherry's own operation would have stored (the same product, the same factor), and they are
 // stored -- only never read back.  (Only what is needed of the entry is fetched, and only in front of a fold: both entries in scalar
 // registers at once spilled over a hundred of them.)
-template <unsigned RT, bool RS, bool WIDE, bool FOLD = false>
+// LOOK: child 2 may be a small subtree read through its class table (`look`; PlanOp::flags bit 5, plan_lookups): a
+// cherry or a cherry x tip, whose vector depends on the two or three tip codes below it alone.  The entry carries those
+// codes' arrays in clv2 / pmat2 / pfrag2 (pfrag2 null: a cherry), the rows P . vector(class) of all U^2 / U^3 classes in
+// lut2 ([rate][child2_index classes][20], k_pair_lut) and the scaler counts per class in scaler2: the wide-tip gather of
+// kernels_repeats.hpp, with the class code formed here from the tip codes.  No vector is read, no product taken for
+// that child; the child's own operation has stored vector and counts as always.  The two class codes share the
+// register that holds a folded cherry's tip codes (an operation has one or the other).
+template <unsigned RT, bool RS, bool WIDE, bool FOLD = false, bool LOOK = false>
 __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2 X[RT][5],
                                     const double * s1, const double * s2,
                                     unsigned lut_codes, unsigned lut_used, bool lut_lds,
                                     unsigned blk, unsigned lane, bool nt_ld, bool nt_st,
                                     unsigned (&xe)[RS ? RT : 1], unsigned (&xo)[RS ? RT : 1], bool store = true,
                                     unsigned wide_lds = 0, bool fold = false, const PlanOp * fentry = nullptr,
-                                    const double * lds = nullptr, bool ftrans = false)
+                                    const double * lds = nullptr, bool ftrans = false, bool look = false)
 {
   static_assert(!FOLD || (!RS && !WIDE), "cherries are folded with per-site scalers and without wide tips only");
+  static_assert(!LOOK || FOLD, "class tables are read by the fold-capable instantiation");
   // wide_lds: PlanOp::flags -- bit 1 / 2: the rows of wide tip 1 / 2 are staged in LDS (s1 / s2, rows of S20_LUT_RS)
   const unsigned q = lane >> 4, n = lane & 15;
   const size_t site0 = (size_t)blk * S20_BS + 2 * n;
@@ -587,6 +598,15 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
         fscaler[site0 + 1] = fsmall >> 1;
       }
     }
+  }
+  if (LOOK && look)
+  {
+    const uint8_t * ca = reinterpret_cast<const uint8_t *>(op.clv2), * cb = reinterpret_cast<const uint8_t *>(op.pmat2);
+    const uint8_t * cc = reinterpret_cast<const uint8_t *>(op.pfrag2);
+    unsigned ke = ca[site0] * lut_used + cb[site0], ko = ca[site0 + 1] * lut_used + cb[site0 + 1];
+    if (cc) { ke = ke * lut_used + cc[site0]; ko = ko * lut_used + cc[site0 + 1]; }
+    fcodes = ke | (ko << 16);                   // (at most S20_LOOK_MAX classes)
+    asm volatile("" : "+v"(fcodes));
   }
   unsigned c1e = 0, c1o = 0, c2e = 0, c2o = 0;
   // a "wide tip" (kernels_repeats.hpp: a cherry known per class of sites): neither vector nor byte codes; the
@@ -622,6 +642,7 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
     {
       if (carried == 2) s20_child_regs_c(X[r], s2 + r * S20_CFRAGS, lane, t2);
       else if (op.codes2) s20_child_tip(s2 + r * lut_used * S20_LUT_RS, c2e, c2o, q, t2, S20_LUT_RS);
+      else if (LOOK && look) s20_child_tip(op.lut2 + (size_t)r * op.child2_index * 20, fcodes & 0xffffu, fcodes >> 16, q, t2);
       else
       {
         // the operand block: built from the cherry's tables (and stored), or read from memory -- one product either way
@@ -732,6 +753,7 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
     {
       if (carried == 2) { ce += xe[0]; co += xo[0]; }
       else if (FOLD && fold) { ce += fsmall & 1u; co += fsmall >> 1; }
+      else if (LOOK && look) { ce += op.scaler2[fcodes & 0xffffu]; co += op.scaler2[fcodes >> 16]; }
       else if (w2) { ce += op.scaler2[c2e]; co += op.scaler2[c2o]; }
       else { ce += op.scaler2[site0]; co += op.scaler2[site0 + 1]; }
     }
@@ -829,7 +851,9 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_chain_s20(ChainBatc
 // builds in registers (bit 4 there: its child 2 is that cherry).  Its tip tables are staged like any other entry's, the
 // scaling decisions per pair of codes go behind them (PlanChain::flags bit 1: the chain has such entries), and the
 // operation loop passes it over.  Schedules without folds run the instantiation without the flag.
-template <unsigned RT, bool RS, bool WIDE, bool TRANS, bool FOLD>
+// LOOK: the schedule holds operations whose child 2 is read through its class table (PlanOp::flags bit 5; s20_chain_op):
+// nothing is staged for that child.  Schedules without such operations run the instantiations without the flag.
+template <unsigned RT, bool RS, bool WIDE, bool TRANS, bool FOLD, bool LOOK = false>
 __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_traverse_s20(PlanView plan, unsigned chain_begin,
                                                                            unsigned chain_end, unsigned nblk,
                                                                            unsigned slab, unsigned flags)
@@ -864,6 +888,7 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_traverse_s20(PlanVi
           s20_fill_slot(lds + po.slot1, po.d.pmat1, po.d.pfrag1, po.d.codes1 ? po.d.lut1 : nullptr, RT, lut_codes, lut_used, lut_lds);
         else if (po.flags & 2u)
           s20_fill_slot(lds + po.slot1, nullptr, nullptr, po.d.lut1, RT, po.d.child1_index, po.d.child1_index, true);
+        if (LOOK && (po.flags & 32u)) continue;        // (clv2 / pmat2 / pfrag2 are tip codes there)
         if (!WIDE || po.d.clv2 || po.d.codes2)
           s20_fill_slot(lds + po.slot2, po.d.pmat2, po.d.pfrag2, po.d.codes2 ? po.d.lut2 : nullptr, RT, lut_codes, lut_used, lut_lds);
         else if (po.flags & 4u)
@@ -894,9 +919,10 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_traverse_s20(PlanVi
           {
             if (po.flags & 8u) continue;                // built by the next entry
             // (tip tables are staged wherever cherries are folded: s20_fold_lds)
-            s20_chain_op<RT, RS, WIDE, FOLD>(po.d, po.carried, X, lds + po.slot1, lds + po.slot2, lut_codes, lut_used, true,
-                                             blk, lane, nt_ld, nt_st, xe, xo, TRANS ? !(po.flags & 1u) : true, 0u,
-                                             (po.flags & 16u) != 0, plan_ops_ + ch.first + i - 1, lds, TRANS);
+            s20_chain_op<RT, RS, WIDE, FOLD, LOOK>(po.d, po.carried, X, lds + po.slot1, lds + po.slot2, lut_codes, lut_used, true,
+                                                   blk, lane, nt_ld, nt_st, xe, xo, TRANS ? !(po.flags & 1u) : true, 0u,
+                                                   (po.flags & 16u) != 0, plan_ops_ + ch.first + i - 1, lds, TRANS,
+                                                   LOOK && (po.flags & 32u) != 0);
             continue;
           }
           s20_chain_op<RT, RS, WIDE>(po.d, i ? po.carried : 0u, X, lds + po.slot1, lds + po.slot2,
@@ -1789,7 +1815,7 @@ static int launch_chains_s20(Engine * e, const ChainBatch & batch, unsigned ncha
 // `extent`: site blocks of the largest partition the chains [chain_begin, chain_end) belong to
 static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_doubles, unsigned extent,
                                unsigned chain_begin, unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu,
-                               bool wide, bool transient, bool fold)
+                               bool wide, bool transient, bool fold, bool look)
 {
   const size_t lds = sizeof(double) * lds_doubles;
   const unsigned flags = []() { const char * v = getenv("PLLHIP_S20_NT"); return v ? (unsigned)atoi(v) & 3u : 0u; }();
@@ -1801,7 +1827,10 @@ static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_d
                                        s20_allow_full_lds(k_traverse_s20<1, RS_, W_, T_, F_>))
     if (!PLLHIP_ALLOW(false, false, false, false) || !PLLHIP_ALLOW(true, false, false, false) || !PLLHIP_ALLOW(false, true, false, false) ||
         !PLLHIP_ALLOW(false, false, true, false) || !PLLHIP_ALLOW(true, false, true, false) || !PLLHIP_ALLOW(false, true, true, false) ||
-        !PLLHIP_ALLOW(false, false, false, true) || !PLLHIP_ALLOW(false, false, true, true))
+        !PLLHIP_ALLOW(false, false, false, true) || !PLLHIP_ALLOW(false, false, true, true) ||
+        !s20_allow_full_lds(k_traverse_s20<4, false, false, false, true, true>) ||
+        !s20_allow_full_lds(k_traverse_s20<2, false, false, false, true, true>) ||
+        !s20_allow_full_lds(k_traverse_s20<1, false, false, false, true, true>))
       return PLL_FAILURE;
 #undef PLLHIP_ALLOW
     attr_set.store(true, std::memory_order_release);
@@ -1831,8 +1860,20 @@ static int launch_traverse_s20(Engine * e, const PlanView & plan, unsigned lds_d
     set_error(PLL_ERROR_PARAM_INVALID, "folded cherries in a schedule with wide tips or per-rate scalers");
     return PLL_FAILURE;
   }
+  // (class tables are read by the fold-capable instantiation, in storing traversals: plan_lookups)
+  if (look && (wide || e->rate_scalers || transient))
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "class-table children in a schedule with wide tips, per-rate scalers or unstored vectors");
+    return PLL_FAILURE;
+  }
+  if (look)
+  {
+    if (e->R == 4) { PLLHIP_CALL((k_traverse_s20<4, false, false, false, true, true>)); }
+    else if (e->R == 2) { PLLHIP_CALL((k_traverse_s20<2, false, false, false, true, true>)); }
+    else { PLLHIP_CALL((k_traverse_s20<1, false, false, false, true, true>)); }
+  }
   // (wide tips -- site repeats, tips kept per class -- exist with per-site scaling only)
-  if (fold) { if (transient) PLLHIP_BY_RATES(false, false, true, true); else PLLHIP_BY_RATES(false, false, false, true); }
+  else if (fold) { if (transient) PLLHIP_BY_RATES(false, false, true, true); else PLLHIP_BY_RATES(false, false, false, true); }
   else if (wide && !e->rate_scalers) { if (transient) PLLHIP_BY_RATES(false, true, true, false); else PLLHIP_BY_RATES(false, true, false, false); }
   else if (e->rate_scalers) { if (transient) PLLHIP_BY_RATES(true, false, true, false); else PLLHIP_BY_RATES(true, false, false, false); }
   else { if (transient) PLLHIP_BY_RATES(false, false, true, false); else PLLHIP_BY_RATES(false, false, false, false); }

@@ -731,7 +731,7 @@ static int launch_chains_s4(Engine * e, const ChainBatch & batch, unsigned nchai
 // `extent`: sites of the largest partition the chains [chain_begin, chain_end) belong to; `longest`: operations of
 // the longest chain (DevicePlan::lds_doubles of this family)
 static int launch_traverse_s4(Engine * e, const PlanView & plan, unsigned longest, unsigned extent, unsigned chain_begin,
-                              unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu, bool wide, bool transient, bool /*fold*/)
+                              unsigned chain_end, unsigned rows, unsigned row_wgs_per_cu, bool wide, bool transient, bool /*fold*/, bool /*look*/)
 {
   const unsigned nchunks = (extent + 63) / 64;
   const size_t lds = sizeof(double) * longest * s4_chain_op_lds(e->R);

@@ -410,6 +410,7 @@ void engine_destroy(Engine * e)
   (void)hipFree(e->d_class_seen);
   if (e->h_class_total) (void)hipHostFree(e->h_class_total);
   (void)hipFree(e->d_pairlut);
+  (void)hipFree(e->d_looktab);
   (void)hipFree(e->d_newton);
   if (e->newton_ready) (void)hipEventDestroy(e->newton_ready);
   if (e->newton_done) (void)hipEventDestroy(e->newton_done);
@@ -1085,13 +1086,16 @@ struct ChainFamily
   // the family folds lone cherries into the chain that reads them (plan_folds): LDS doubles of one fold in its
   // consumer's chain (null: the family has no folds; 0: none at this partition's shape)
   unsigned (*fold_lds)(const Engine * e, unsigned lut_used);
+  // the family reads small light subtrees through class tables (plan_lookups): the most classes of such a child
+  // (null: the family has no such reads; 0: none at this partition's shape)
+  unsigned (*look_classes)(const Engine * e, unsigned lut_used);
   const double * (*pair_pfrag)(const Engine * e, unsigned matrix);        // PairLutJob::pfrag of a branch
   bool (*fills_chip)(const Engine * e);                 // the site blocks alone keep the chip busy: one launch
   unsigned (*units)(const Engine * e);                  // workgroups a member of a batch can use side by side
   unsigned batch_wgs;                                   // workgroups per CU and row of a batch in one launch
   // a resident schedule (DevicePlan, upload_plan): chains [begin, end) in `rows` grid rows
   int (*traverse)(Engine * e, const PlanView & view, unsigned lds_doubles, unsigned extent, unsigned begin,
-                  unsigned end, unsigned rows, unsigned wgs, bool wide, bool transient, bool fold);
+                  unsigned end, unsigned rows, unsigned wgs, bool wide, bool transient, bool fold, bool look);
   // chains by value in the kernel arguments (null: none)
   int (*chains)(Engine * e, const ChainBatch & batch, unsigned nchains, unsigned lds, unsigned lut_used);
   // class nodes (kernels_repeats.hpp): row tables, class tables, the site-indexed vector of one node
@@ -1100,13 +1104,31 @@ struct ChainFamily
   void (*class_expand)(Engine * e, const Engine::Cherry & c, double * out);
 };
 
+// 20 states: the most classes of a light child that its consumer reads through the child's class table.  Default: a
+// cherry (U^2 classes for U codes in use) and a cherry x tip (U^3); PLLHIP_LOOKUP_CLASSES sets another limit.  Two
+// class codes share a register in the kernel (S20_LOOK_MAX).
+// The read pays where the child's vector would come back from HBM.  A partition small enough for the one-launch
+// traversal reads it from the caches (its wave wrote it a few chains ago), and there the gather and the table launches
+// only cost (C3's 125 k-site slice: 4.09 -> 4.25 ms per traversal, against 28.19 -> 27.62 ms at 1 M sites): a floor
+// of S20_LOOK_MIN_BLOCKS site blocks.  PLLHIP_LOOKUP=1 plans the reads at any size, PLLHIP_LOOKUP=0 at none.
+constexpr unsigned S20_LOOK_MIN_BLOCKS = 8192;          // 262 144 sites
+static unsigned s20_look_classes(const Engine * e, unsigned lut_used)
+{
+  static const int use_look = getenv("PLLHIP_LOOKUP") ? atoi(getenv("PLLHIP_LOOKUP")) : -1;
+  static const long env_classes = getenv("PLLHIP_LOOKUP_CLASSES") ? atol(getenv("PLLHIP_LOOKUP_CLASSES")) : -1;
+  if (!use_look || !e->d_pfrag || (use_look < 0 && e->nblk < S20_LOOK_MIN_BLOCKS)) return 0u;
+  const unsigned long long limit = env_classes >= 0 ? (unsigned long long)env_classes
+                                                    : (unsigned long long)lut_used * lut_used * lut_used;
+  return (unsigned)std::min<unsigned long long>(limit, S20_LOOK_MAX);
+}
+
 static const ChainFamily CHAINS_S4 = {
   .supported = chains_supported_s4, .chain_max = S4_CHAIN_MAX, .chain_lds = ~0u, .lds_is_length = true,
   .extent = [](const Engine * e) { return e->N; },
   .child_lds = [](const Engine *, bool, unsigned) { return 0u; },
   .wide_lds = [](const Engine *, unsigned) { return 0u; },
   .tables_in_lds = [](const Engine *, unsigned) { return false; },
-  .fold_lds = nullptr,
+  .fold_lds = nullptr, .look_classes = nullptr,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pmat + (size_t)m * e->R * 16; },
   .fills_chip = [](const Engine * e) { return (e->N + 63) / 64 >= 48u * e->cu_count; },
   .units = [](const Engine * e) { return (e->N + 255u) / 256u; }, .batch_wgs = 3,
@@ -1128,7 +1150,7 @@ static const ChainFamily CHAINS_S16 = {
   .child_lds = [](const Engine * e, bool tip, unsigned) { return s16_chain_slot(e, tip); },
   .wide_lds = [](const Engine * e, unsigned rows) { return e->R * rows * e->S <= S16_LUT_LDS ? ((e->R * rows * e->S + 7u) & ~7u) : 0u; },
   .tables_in_lds = [](const Engine * e, unsigned) { return s16_chain_lut_lds(e); },
-  .fold_lds = nullptr,
+  .fold_lds = nullptr, .look_classes = nullptr,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pmat + (size_t)m * e->R * e->S * e->Sp; },
   .fills_chip = [](const Engine * e) { return e->nblk >= 12u * e->cu_count && e->nblk < 48u * e->cu_count && e->S > 8; },
   .units = [](const Engine * e) { return (e->nblk + 7u) / 8u; }, .batch_wgs = 1,
@@ -1164,7 +1186,7 @@ static const ChainFamily CHAINS_S20 = {
   .child_lds = s20_chain_slot,
   .wide_lds = [](const Engine * e, unsigned rows) { return e->R * rows * S20_LUT_RS <= 2560u ? ((e->R * rows * S20_LUT_RS + 7u) & ~7u) : 0u; },
   .tables_in_lds = s20_chain_lut_lds,
-  .fold_lds = s20_fold_lds,
+  .fold_lds = s20_fold_lds, .look_classes = s20_look_classes,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pfrag + (size_t)m * e->R * 400; },
   .fills_chip = [](const Engine * e) { return e->nblk >= 6u * e->cu_count && e->nblk < 24u * e->cu_count; },
   .units = [](const Engine * e) { return (e->nblk + 7u) / 8u; }, .batch_wgs = 1,
@@ -1362,6 +1384,17 @@ struct ChainPlan
   // per op: 1 / 2 = a lone cherry that the next operation of its chain builds in registers as its child 1 / 2
   // (plan_folds; empty: no folds).  Such an operation sits in front of its consumer in `chains`
   std::vector<unsigned char> folded;
+  // children that their consumer reads through a class table instead of the stored vector (plan_lookups), and per op
+  // which child that is (1 / 2; empty: none)
+  struct Lookup
+  {
+    unsigned consumer, top;                      // the operation that reads the child; the one that makes it
+    int cherry;                                  // top is cherry x tip: the cherry's operation (-1: top is the cherry)
+    unsigned nclasses;
+    size_t off_table[2], off_flags[2], off_counts[2], off_rows[2];   // bytes in Engine::d_looktab: [0] top, [1] the cherry below it
+  };
+  std::vector<Lookup> lookups;
+  std::vector<unsigned char> looked;
   int rounds = 0;
 };
 
@@ -1591,6 +1624,62 @@ static void plan_folds(const Engine * e, const ChainFamily & f, const pll_operat
     out.rounds = std::max(out.rounds, out.launch[chain_of[k]] + 1);
   }
   plan = std::move(out);
+}
+
+// Children read through class tables.  The vector of a cherry depends on the pair of tip codes of a site alone, the one
+// of a cherry x tip operation on three codes: at most U^2 / U^3 different columns for U codes in use, however long the
+// alignment.  Where a chain meets such a child as its light child -- the vector that comes back from memory next to the
+// handed-over one --, the consumer gathers rows of P . vector(class) from a table of all classes instead (built per
+// traversal by the class kernels of site repeats, emit_lookup_tables; the class code is arithmetic on the tip codes).
+// Nothing else changes: the child's own chain runs and stores vector and counts as before, no chain, cut or fold moves.
+// Marked: an operation's inner child that is neither handed over nor folded, made by an operation of the list that is
+// a cherry of coded tips or such a cherry x a coded tip, with at most max_classes classes; one child per operation
+// (it becomes child 2, as a folded cherry does), none next to a fold.
+static void plan_lookups(const Engine * e, const pll_operation_t * ops, unsigned count, unsigned lut_used, unsigned max_classes,
+                         ChainPlan & plan)
+{
+  plan.lookups.clear();
+  plan.looked.clear();
+  if (!max_classes || count < 2) return;
+  std::vector<int> producer(e->nodes, -1);
+  std::vector<char> fold_consumer(count, 0);
+  if (!plan.folded.empty())
+    for (const std::vector<unsigned> & ch : plan.chains)
+      for (size_t i = 0; i + 1 < ch.size(); ++i)
+        if (plan.folded[ch[i]]) fold_consumer[ch[i + 1]] = 1;
+  auto plain_tip = [&](unsigned idx, int scaler) { return coded_tip(e, idx) && scaler == PLL_SCALE_BUFFER_NONE; };
+  auto is_cherry = [&](const pll_operation_t & o)
+  { return plain_tip(o.child1_clv_index, o.child1_scaler_index) && plain_tip(o.child2_clv_index, o.child2_scaler_index); };
+  const unsigned long long u = lut_used;
+  for (unsigned k = 0; k < count; ++k)
+  {
+    const pll_operation_t & op = ops[k];
+    const unsigned child[2] = {op.child1_clv_index, op.child2_clv_index};
+    for (unsigned x = 0; x < 2 && !fold_consumer[k]; ++x)
+    {
+      const int top = child[x] < e->nodes ? producer[child[x]] : -1;
+      if (top < 0 || plan.carried[k] == x + 1 || (!plan.folded.empty() && plan.folded[top])) continue;
+      const pll_operation_t & t = ops[top];
+      int cherry = -1;
+      unsigned long long classes = u * u;
+      if (!is_cherry(t))
+      {
+        const bool tip1 = plain_tip(t.child1_clv_index, t.child1_scaler_index), tip2 = plain_tip(t.child2_clv_index, t.child2_scaler_index);
+        if (tip1 == tip2) continue;
+        cherry = producer[tip1 ? t.child2_clv_index : t.child1_clv_index];
+        if (cherry < 0 || !is_cherry(ops[cherry])) continue;
+        classes *= u;
+      }
+      if (classes > max_classes) continue;
+      if (plan.looked.empty()) plan.looked.assign(count, 0);
+      plan.looked[k] = (unsigned char)(x + 1);
+      ChainPlan::Lookup l = {};
+      l.consumer = k; l.top = (unsigned)top; l.cherry = cherry; l.nclasses = (unsigned)classes;
+      plan.lookups.push_back(l);
+      break;
+    }
+    producer[op.parent_clv_index] = (int)k;
+  }
 }
 
 // make DevicePlan::bytes resident on the device (stream-ordered; nothing is copied when the
@@ -2028,6 +2117,7 @@ struct ScheduleBuild                             // the schedule being built (De
   size_t pairlut_used = 0;                       // doubles of e->d_pairlut handed out
   unsigned nops = 0, lds_max = 0;
   unsigned nfolds = 0, inner_reads = 0;          // folded cherries; inner vectors that the chains read from memory
+  unsigned nlookups = 0;                         // children read through their class tables
 };
 
 // site repeats: children that are cherries kept per class are read as wide tips (kernels_repeats.hpp);
@@ -2065,18 +2155,19 @@ static bool mark_wide_tips(Engine * e, const pll_operation_t * ops, unsigned cou
 // in use, the mode, the wide tips, and which operations are kept per class (the same list can meet other class nodes
 // of earlier calls)
 static std::vector<unsigned char> schedule_key(const ScheduleRequest & rq, unsigned lut_used, const std::vector<unsigned char> & wide,
-                                               bool fold)
+                                               bool fold, unsigned look_classes)
 {
   std::vector<unsigned char> tracked(rq.rp ? rq.count : 0, 0);
   if (rq.rp) for (unsigned k : rq.rp->cherry_ops) tracked[k] = 1;
   const size_t list_bytes = (size_t)rq.count * sizeof(pll_operation_t);
-  std::vector<unsigned char> key(3 * sizeof(unsigned) + list_bytes + wide.size() + tracked.size());
+  std::vector<unsigned char> key(4 * sizeof(unsigned) + list_bytes + wide.size() + tracked.size());
   const unsigned mode_key = rq.mode | (rq.transient ? 0x100u : 0u) | (fold ? 0x200u : 0u);
   memcpy(key.data(), &rq.count, sizeof(unsigned));
   memcpy(key.data() + sizeof(unsigned), &lut_used, sizeof(unsigned));
   memcpy(key.data() + 2 * sizeof(unsigned), &mode_key, sizeof(unsigned));
-  memcpy(key.data() + 3 * sizeof(unsigned), rq.ops, list_bytes);
-  if (!wide.empty()) memcpy(key.data() + 3 * sizeof(unsigned) + list_bytes, wide.data(), wide.size());
+  memcpy(key.data() + 3 * sizeof(unsigned), &look_classes, sizeof(unsigned));      // (the class limit of plan_lookups)
+  memcpy(key.data() + 4 * sizeof(unsigned), rq.ops, list_bytes);
+  if (!wide.empty()) memcpy(key.data() + 4 * sizeof(unsigned) + list_bytes, wide.data(), wide.size());
   if (!tracked.empty()) memcpy(key.data() + key.size() - tracked.size(), tracked.data(), tracked.size());
   return key;
 }
@@ -2106,6 +2197,33 @@ static bool reserve_pair_tables(Engine * e, const ScheduleRequest & rq, const pl
   e->pairlut_cap = 0;
   if (!dev_alloc(&e->d_pairlut, 2 * need, "wide-tip lookup tables")) return false;
   e->pairlut_cap = 2 * need;
+  return true;
+}
+
+// room in e->d_looktab for the tables of the children read by tip codes (plan_lookups): per child, and per cherry below
+// a cherry x tip child, the class table (blocked like a vector over the classes), its scaling flags and scaler counts
+// per class, and its rows through the branch above it.  Allocated here, with the schedule: a traversal allocates nothing
+static bool reserve_lookup_tables(Engine * e, ChainPlan & plan, unsigned lut_used)
+{
+  if (plan.lookups.empty()) return true;
+  size_t need = 0;
+  auto take = [&](size_t bytes) { const size_t at = need; need += (bytes + 255) & ~(size_t)255; return at; };
+  for (ChainPlan::Lookup & l : plan.lookups)
+    for (int x = 0; x < (l.cherry >= 0 ? 2 : 1); ++x)
+    {
+      const size_t classes = x ? (size_t)lut_used * lut_used : l.nclasses, npblk = (classes + S20_BS - 1) / S20_BS;
+      l.off_table[x] = take(npblk * e->R * S20_UNIT * sizeof(double));
+      l.off_flags[x] = take(npblk * S20_BS);
+      l.off_counts[x] = take(npblk * S20_BS * sizeof(unsigned));
+      l.off_rows[x] = take(classes * e->R * e->S * sizeof(double));
+    }
+  if (need <= e->looktab_cap) return true;
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return false;      // a running traversal may still read the old tables
+  (void)hipFree(e->d_looktab);
+  e->d_looktab = nullptr;
+  e->looktab_cap = 0;
+  if (!dev_alloc(&e->d_looktab, need, "class tables of looked-up children")) return false;
+  e->looktab_cap = need;
   return true;
 }
 
@@ -2224,15 +2342,16 @@ static void emit_chains(const Engine * e, const ChainFamily & f, const pll_opera
       memset(&po, 0, sizeof(po));
       const double before = dp.algo_bytes;
       const unsigned folded = plan.folded.empty() ? 0u : plan.folded[ch[i]];
+      const unsigned looked = plan.looked.empty() ? 0u : plan.looked[ch[i]];
       po.carried = first ? 0 : plan.carried[ch[i]];
       if (!folded) first = false;
-      if (fold_side == 1)                         // the folded cherry is child 2 (products commute)
+      if (fold_side == 1 || looked == 1)          // the folded cherry / the child read by tip codes is child 2 (products commute)
       {
         std::swap(o.child1_clv_index, o.child2_clv_index);
         std::swap(o.child1_matrix_index, o.child2_matrix_index);
         std::swap(o.child1_scaler_index, o.child2_scaler_index);
         if (po.carried) po.carried = 3 - po.carried;
-        fold_side = 2;
+        if (fold_side) fold_side = 2;
       }
       fill_desc(e, o, po.d, dp.algo_bytes, dp.algo_flops);
       // an evaluate-only traversal: the vectors inside a chain are handed on in registers only
@@ -2256,7 +2375,7 @@ static void emit_chains(const Engine * e, const ChainFamily & f, const pll_opera
       {
         const unsigned idx = x == 1 ? o.child1_clv_index : o.child2_clv_index;
         const bool w_x = !wide.empty() && wide[2 * ch[i] + x - 1];
-        if (idx >= e->tips && !w_x && po.carried != x && fold_side != x) ++sb.inner_reads;
+        if (idx >= e->tips && !w_x && po.carried != x && fold_side != x && !(looked && x == 2)) ++sb.inner_reads;
       }
       double wide_saved = (po.flags & 1u) ? (double)e->N * e->R * 8.0 * e->S : 0.0;
       const bool w[2] = {!wide.empty() && wide[2 * ch[i]], !wide.empty() && wide[2 * ch[i] + 1]};
@@ -2284,6 +2403,14 @@ static void emit_chains(const Engine * e, const ChainFamily & f, const pll_opera
       if (fold_side)
         dp.min_bytes -= (double)e->N * e->R * 8.0 * e->S + ((fold_side == 1 ? po.d.scaler1 : po.d.scaler2) ? 4.0 * (double)e->N : 0.0);
       fold_side = 0;
+      // ... and a child read through its class table: two or three code bytes per site instead of vector and counts
+      // (emit_lookup_tables completes the entry)
+      if (looked)
+      {
+        po.flags |= 32u;
+        ++sb.nlookups;
+        dp.min_bytes -= (double)e->N * e->R * 8.0 * e->S + (po.d.scaler2 ? 4.0 * (double)e->N : 0.0);
+      }
       po.slot1 = off;
       off += child_table_lds(e, f, o.child1_clv_index, lut_used, w[0]);
       po.slot2 = off;
@@ -2367,6 +2494,106 @@ static void emit_repeat_levels(const Engine * e, const ChainFamily & f, const Sc
   }
 }
 
+// The tables of the children read by tip codes (plan_lookups), dense over all U^2 / U^3 tuples of codes, through the
+// class kernels of site repeats (kernels_repeats.hpp) -- whose consumers are pinned to give, bit for bit, what they
+// compute from the stored vector -- in two levels that all such children of the schedule share:
+//   the cherries' tables (class = code1 * U + code2: the kernel's own arithmetic, no class map);
+//   their rows through the branch above each, then the tables of the cherry x tip operations from those rows and
+//   the tip's (class = cherry class * U + tip code: the same arithmetic with U^2 rows on one side), with the scaling
+//   decision and the summed counts per class;
+//   the rows of those through the branch above them (pack_schedule's last level).
+// The consumers' entries get the tip code arrays, the rows and the counts (PlanOp::flags bit 5).
+static void emit_lookup_tables(const Engine * e, const ChainFamily & f, const pll_operation_t * ops, const ChainPlan & plan,
+                               unsigned lut_used, DevicePlan & dp, ScheduleBuild & sb)
+{
+  if (plan.lookups.empty()) return;
+  const size_t lut_stride = (size_t)e->R * e->lut_codes * e->S;
+  const unsigned pairs = lut_used * lut_used;
+  std::vector<int> entry_of(e->nodes, -1);
+  for (unsigned i = 0; i < sb.nops; ++i) entry_of[sb.pops[i].d.parent_index] = (int)i;
+  auto table = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<double *>(e->d_looktab + l.off_table[x]); };
+  auto counts = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<unsigned *>(e->d_looktab + l.off_counts[x]); };
+  auto rows = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<double *>(e->d_looktab + l.off_rows[x]); };
+  // the matrix of the branch above `child` in operation o
+  auto matrix_above = [&](const pll_operation_t & o, unsigned child)
+  { return o.child1_clv_index == child ? o.child1_matrix_index : o.child2_matrix_index; };
+  DevicePlan::RepeatLevel L0 = {(unsigned)sb.cherry_jobs.size(), 0, (unsigned)sb.level_pairs.size(), (unsigned)sb.level_pairs.size(), pairs, 0};
+  for (const ChainPlan::Lookup & l : plan.lookups)
+  {
+    const int x = l.cherry >= 0 ? 1 : 0;
+    const pll_operation_t & c = ops[x ? (unsigned)l.cherry : l.top];
+    CherryJob j;
+    memset(&j, 0, sizeof(j));
+    j.lut1 = e->d_lut + lut_stride * c.child1_matrix_index; j.rows1 = e->lut_codes;
+    j.lut2 = e->d_lut + lut_stride * c.child2_matrix_index; j.rows2 = e->lut_codes;
+    j.nclasses = pairs;
+    j.table = table(l, x);
+    j.flags = e->d_looktab + l.off_flags[x];
+    j.counts = c.parent_scaler_index >= 0 ? counts(l, x) : nullptr;
+    sb.cherry_jobs.push_back(j);
+  }
+  L0.job_end = (unsigned)sb.cherry_jobs.size();
+  dp.repeat_levels.push_back(L0);
+  DevicePlan::RepeatLevel L1 = {L0.job_end, 0, L0.pair_end, 0, 0, pairs};
+  for (const ChainPlan::Lookup & l : plan.lookups)
+  {
+    const pll_operation_t & t = ops[l.top], & k = ops[l.consumer];
+    const int x = l.cherry >= 0 ? 1 : 0;
+    const pll_operation_t & c = ops[x ? (unsigned)l.cherry : l.top];
+    // the cherry's rows through the branch above it: into the cherry x tip operation, or into the consumer
+    PairLutJob pj;
+    pj.table = table(l, x);
+    pj.pfrag = f.pair_pfrag(e, matrix_above(x ? t : k, c.parent_clv_index));
+    pj.out = rows(l, x);
+    pj.nrows = pairs;
+    sb.level_pairs.push_back(pj);
+    if (!x) continue;
+    const bool cherry_first = t.child1_clv_index == c.parent_clv_index;
+    const unsigned tip = cherry_first ? t.child2_clv_index : t.child1_clv_index;
+    CherryJob j;
+    memset(&j, 0, sizeof(j));
+    j.lut1 = rows(l, 1); j.rows1 = pairs;
+    j.lut2 = e->d_lut + lut_stride * matrix_above(t, tip); j.rows2 = e->lut_codes;
+    j.cnt1 = (cherry_first ? t.child1_scaler_index : t.child2_scaler_index) >= 0 ? counts(l, 1) : nullptr;
+    j.nclasses = l.nclasses;
+    j.table = table(l, 0);
+    j.flags = e->d_looktab + l.off_flags[0];
+    j.counts = t.parent_scaler_index >= 0 ? counts(l, 0) : nullptr;
+    sb.cherry_jobs.push_back(j);
+    L1.max_classes = std::max(L1.max_classes, l.nclasses);
+    PairLutJob top;
+    top.table = table(l, 0);
+    top.pfrag = f.pair_pfrag(e, matrix_above(k, t.parent_clv_index));
+    top.out = rows(l, 0);
+    top.nrows = l.nclasses;
+    sb.pair_jobs.push_back(top);
+  }
+  L1.job_end = (unsigned)sb.cherry_jobs.size();
+  L1.pair_end = (unsigned)sb.level_pairs.size();
+  dp.repeat_levels.push_back(L1);
+  // the consumers' entries (the child is child 2 there: emit_chains)
+  for (const ChainPlan::Lookup & l : plan.lookups)
+  {
+    const pll_operation_t & t = ops[l.top];
+    PlanOp & po = sb.pops[entry_of[ops[l.consumer].parent_clv_index]];
+    unsigned tips[3] = {t.child1_clv_index, t.child2_clv_index, ~0u};
+    if (l.cherry >= 0)
+    {
+      const pll_operation_t & c = ops[l.cherry];
+      tips[2] = t.child1_clv_index == c.parent_clv_index ? t.child2_clv_index : t.child1_clv_index;
+      tips[0] = c.child1_clv_index; tips[1] = c.child2_clv_index;
+    }
+    po.d.clv2 = reinterpret_cast<const double *>(e->d_codes[tips[0]]);
+    po.d.pmat2 = reinterpret_cast<const double *>(e->d_codes[tips[1]]);
+    po.d.pfrag2 = l.cherry >= 0 ? reinterpret_cast<const double *>(e->d_codes[tips[2]]) : nullptr;
+    po.d.codes2 = nullptr;
+    po.d.lut2 = rows(l, 0);
+    po.d.child2_index = l.nclasses;
+    if (po.d.scaler2) po.d.scaler2 = counts(l, 0);
+    dp.min_bytes += (double)e->N * (l.cherry >= 0 ? 3.0 : 2.0);
+  }
+}
+
 // DevicePlan::bytes: [PlanOp][PlanChain][CherryJob][PairLutJob]; the row tables of the wide tips of the chains go after
 // the last level of class operations
 static void pack_schedule(DevicePlan & dp, ScheduleBuild & sb, unsigned lut_used)
@@ -2425,16 +2652,21 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   if (!mark_wide_tips(e, ops, count, lut_used, wide, nwide)) return false;
   // (folds: not next to class nodes; PLLHIP_FOLD and the family decide the rest)
   const unsigned fold_lds = rq.fold && !rq.rp && !nwide ? fold_table_lds(e, f, lut_used) : 0u;
-  std::vector<unsigned char> key = schedule_key(rq, lut_used, wide, fold_lds != 0);
+  // (children read through class tables: where folds are planned, in storing traversals)
+  const unsigned look_classes = fold_lds && f.look_classes && !rq.transient && !e->transient_mode ? f.look_classes(e, lut_used) : 0u;
+  std::vector<unsigned char> key = schedule_key(rq, lut_used, wide, fold_lds != 0, look_classes);
   if (!dp.key.empty() && dp.key == key) return true;
   if ((nwide || rq.rp) && !reserve_pair_tables(e, rq, ops, count, wide)) return false;
   ChainPlan plan;
   if (!plan_chains(e, &f, ops, count, f.chain_max, f.chain_lds, lut_used, plan, &wide)) return false;
   plan_folds(e, f, ops, count, f.chain_max, f.chain_lds, lut_used, fold_lds, plan);
+  plan_lookups(e, ops, count, lut_used, look_classes, plan);
+  if (!reserve_lookup_tables(e, plan, lut_used)) return false;
   ScheduleBuild sb;
   sb.pops.resize(count);
   emit_chains(e, f, ops, plan, chain_order(e, ops, count, plan, rq.mode == 0), wide, lut_used, rq, dp, sb);
   emit_repeat_levels(e, f, rq, dp, sb);
+  emit_lookup_tables(e, f, ops, plan, lut_used, dp, sb);
   pack_schedule(dp, sb, lut_used);
   close_launch(dp, sb);                           // (the last launch also carries the class operations' bytes)
   if (rq.mode == 0) merge_single_chain_rounds(dp);
@@ -2444,6 +2676,7 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   dp.lds_doubles = sb.lds_max;
   dp.nfolds = sb.nfolds;
   dp.inner_reads = sb.inner_reads;
+  dp.nlookups = sb.nlookups;
   dp.max_extent = f.extent(e);
   dp.generation = ++plan_generation;
   dp.key.swap(key);
@@ -2677,7 +2910,7 @@ static int launch_resident(Engine * e, const ChainFamily & f, const DevicePlan &
 {
   for (const DevicePlan::Launch & l : dp.launches)
     if (!counted_launch(e, l.bytes, l.flops, l.ops, l.min_bytes, [&]()
-        { return f.traverse(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, l.rows, wgs, wide, transient, dp.nfolds != 0); }))
+        { return f.traverse(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, l.rows, wgs, wide, transient, dp.nfolds != 0, dp.nlookups != 0); }))
       return PLL_FAILURE;
   return PLL_SUCCESS;
 }
@@ -2697,9 +2930,12 @@ static int run_resident(Engine * e, const ChainFamily & f, const pll_operation_t
     if (rp.active)
       for (unsigned k : rp.cherry_ops)
         if (ops[k].parent_scaler_index >= 0) e->scaler_lazy[ops[k].parent_scaler_index] = (int)ops[k].parent_clv_index;
-    e->repeat_stats.cherries += dp.ncherry_jobs;
-    e->repeat_stats.classes += dp.repeat_classes;
-    e->repeat_stats.sites += (unsigned long long)dp.ncherry_jobs * e->N;
+    if (!dp.nlookups)                             // (the statistics of site repeats: not the tables of looked-up children)
+    {
+      e->repeat_stats.cherries += dp.ncherry_jobs;
+      e->repeat_stats.classes += dp.repeat_classes;
+      e->repeat_stats.sites += (unsigned long long)dp.ncherry_jobs * e->N;
+    }
   }
   if (!launch_resident(e, f, dp, view, 0, !e->cherries.empty(), transient)) return PLL_FAILURE;
   if (transient) transient_after_list(e, ops, count, dp);
@@ -4497,6 +4733,7 @@ int pllhip_schedule_stats(const pll_partition_t * p, pllhip_schedule_stats_t * o
   out->operations = resident ? dp.nops : 0;
   out->inner_reads = resident ? dp.inner_reads : 0;
   out->folded_cherries = resident ? dp.nfolds : 0;
+  out->lookup_children = resident ? dp.nlookups : 0;
   return PLL_SUCCESS;
 }
 

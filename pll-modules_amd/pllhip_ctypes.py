@@ -111,7 +111,7 @@ class TransientStats(C.Structure):
 
 
 class ScheduleStats(C.Structure):
-    _fields_ = [(n, C.c_uint) for n in ("chains", "operations", "inner_reads", "folded_cherries")]
+    _fields_ = [(n, C.c_uint) for n in ("chains", "operations", "inner_reads", "folded_cherries", "lookup_children")]
 
 
 class Profile(C.Structure):
