@@ -559,6 +559,45 @@ PLL_EXPORT int pllhip_consensus_needs(unsigned int tree_count, double threshold,
    candidates of one round tested against each other */
 PLL_EXPORT void pllhip_treeset_last_consensus_counts(unsigned long long * accepted_tests, unsigned long long * pair_tests);
 
+/* ---- marginal ancestral states of many nodes ("Ancestral states") ----
+ * The value of pll_compute_node_ancestral (scaler counts and p-inv ignored; a site whose sum is 0 keeps an all-zero
+ * row), computed into a device staging buffer, plus the summary most callers want per site: states[n] = the smallest
+ * state index with the largest probability of row n (0 for an all-zero row), state_probs[n] = that probability --
+ * both taken from the very doubles `probs` would hold, so states[n] == argmax(probs[n]) holds exactly.
+ * The staging buffer is allocated once per batch; when the entries do not fit PLLHIP_ANC_STAGING_BYTES (environment,
+ * read at the call; default 1 GiB, never less than one entry) they go through it in chunks with one wait and one
+ * round of copies per chunk.  Results do not depend on the chunk size. */
+#define PLLHIP_ANC_PROBS (1u << 0)   /* also return the full sites x states table */
+
+/* One (node, other, matrix) triple per entry, same meaning as the arguments of pll_compute_node_ancestral.
+   Enqueues everything, waits once.  states[k], state_probs[k] (and probs[k] with PLLHIP_ANC_PROBS, else probs may be
+   NULL) are host arrays of partition->sites (x states) elements per entry. */
+PLL_EXPORT int pllhip_node_ancestral_batch(pll_partition_t * partition, unsigned int count,
+                                           const unsigned int * node_clv, const unsigned int * other_clv,
+                                           const unsigned int * matrix_indices, const unsigned int * freqs_indices,
+                                           unsigned int flags,
+                                           unsigned char * const * states, double * const * state_probs,
+                                           double * const * probs);
+
+/* The same batch entry by entry, for callers whose vectors are not all valid at the same time (a re-rooting loop:
+   pllhip_eval_compute_ancestral).  add() prepares both vectors as pll_compute_node_ancestral does and enqueues the
+   entry's kernel, which writes into the staging buffer in stream order: whatever the caller enqueues next on the
+   partition may overwrite the two vectors.  The host waits only when a staging chunk is full, and in finish().  The
+   result arrays of an entry are complete after finish() (a full chunk delivers earlier).  `expected`: the number of
+   entries to come, which bounds the staging buffer (0: size it by the budget alone).  After a failed add() no
+   further entry is taken; finish() must still be called, releases everything and reports the failure. */
+typedef struct pllhip_anc_batch pllhip_anc_batch_t;
+PLL_EXPORT pllhip_anc_batch_t * pllhip_node_ancestral_begin(pll_partition_t * partition, unsigned int flags,
+                                                            unsigned int expected);
+PLL_EXPORT int pllhip_node_ancestral_add(pllhip_anc_batch_t * batch, unsigned int node_clv_index,
+                                         unsigned int other_clv_index, unsigned int matrix_index,
+                                         const unsigned int * freqs_indices, unsigned char * states,
+                                         double * state_probs, double * probs);
+PLL_EXPORT int pllhip_node_ancestral_finish(pllhip_anc_batch_t * batch);
+/* the batch this thread finished last: device time of its kernels in ms between HIP events (summed over the devices
+   of a sharded partition), and its staging chunks (the largest count of any device) */
+PLL_EXPORT void pllhip_node_ancestral_last_times(double * kernel_ms, unsigned long long * chunks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,38 @@ typedef struct pllhip_spr_stats
 PLL_EXPORT double pllhip_eval_spr_round(pllhip_eval_t * ev, const pllhip_spr_params_t * params,
                                         pllhip_spr_cutoff_t * cutoff, pllhip_spr_stats_t * stats);
 
+/* ---------------------------------------------------------------------------
+ * Marginal ancestral states of every inner node: the counterpart of pllmod_treeinfo_compute_ancestral
+ * (src/tree/treeinfo.c:1611-1718) on this driver.  Node order is the reference's: a full post-order
+ * pll_utree_traverse from the tree's vroot, inner nodes kept, so probs[i] lines up element for element with
+ * pllmod_ancestral_t::probs[i].  The driver's own tree is used (no clone, no labels invented); per node the root is
+ * set to the node's record, the invalid P-matrices and vectors of that root are computed, and the triple
+ * (node->clv_index, node->back->clv_index, node->pmatrix_index) of every local partition gives the node's rows.
+ * The root is restored before returning.
+ * Per site: states = the smallest state index with the largest probability (0 for an all-zero row), state_probs =
+ * that probability; with PLLHIP_ANC_PROBS (include/pllhip.h) also the full table.  Scaler counts and p-inv are
+ * ignored, as pll_compute_node_ancestral ignores them.
+ * On the HIP engine every entry goes through pllhip_node_ancestral_begin / _add / _finish: the host never waits
+ * between nodes, only once per staging chunk.  Where the library has no such call (the CPU oracle) the driver calls
+ * pll_compute_node_ancestral per node and partition and derives the summary on the host by the same rule.
+ * NULL on error (pll_errno set; everything freed, the root restored).
+ * ------------------------------------------------------------------------- */
+typedef struct pllhip_ancestral
+{
+  unsigned int node_count;             /* inner nodes of the tree */
+  unsigned int partition_count;        /* local (non-NULL) partitions */
+  pll_unode_t ** nodes;                /* records of the driver's tree, in the reference's order */
+  unsigned int * partition_indices;
+  size_t * site_offset;                /* partition_count + 1: first site of each local partition in a node's row */
+  size_t * prob_offset;                /* partition_count + 1: same for the sites x states rows */
+  unsigned char ** states;             /* [node][site_offset[partition_count]] */
+  double ** state_probs;
+  double ** probs;                     /* [node][prob_offset[partition_count]], NULL without PLLHIP_ANC_PROBS */
+} pllhip_ancestral_t;
+
+PLL_EXPORT pllhip_ancestral_t * pllhip_eval_compute_ancestral(pllhip_eval_t * ev, unsigned int flags);
+PLL_EXPORT void pllhip_eval_destroy_ancestral(pllhip_ancestral_t * anc);
+
 PLL_EXPORT unsigned long pllhip_eval_ops(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_pmatrix_updates(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_derivative_calls(const pllhip_eval_t * ev);   /* sumtable scans */

@@ -11,6 +11,10 @@
 #pragma weak pllhip_newton_branch_multi
 #pragma weak pllhip_set_transient      /* HIP engine only: the CPU oracle stores every vector */
 #pragma weak pllhip_discard_transient
+#pragma weak pllhip_node_ancestral_batch   /* HIP engine only: the CPU oracle computes node by node */
+#pragma weak pllhip_node_ancestral_begin
+#pragma weak pllhip_node_ancestral_add
+#pragma weak pllhip_node_ancestral_finish
 #include <stdarg.h>
 
 static __thread pllhip_eval_t * cb_self;   /* pll_utree_traverse callbacks carry no user pointer */
@@ -457,20 +461,11 @@ static void partitions_transient(pllhip_eval_t * ev, int on, int discard)
   }
 }
 
-double pllhip_eval_loglh(pllhip_eval_t * ev, int incremental)
+/* P-matrices and vectors of the current root up to date (the invalid ones only); 0 if that failed */
+static int update_vectors(pllhip_eval_t * ev, int failed)
 {
   unsigned int n = 0, nops = 0, i;
-  int failed = 0;
-  /* a full evaluation recomputes every vector: what the last one kept in registers only is given up BEFORE the
-     P-matrices change (nothing is recomputed for them), and this one may keep its own in registers */
-  const int transient = !incremental && (ev->transient == PLLHIP_EVAL_TRANSIENT_ON ||
-                                         (ev->transient == PLLHIP_EVAL_TRANSIENT_AUTO && ev->last_was_full));
-  ev->last_was_full = !incremental;
-  if (!incremental) pllhip_eval_invalidate_all(ev);
-  pll_errno = 0;
-  if (!incremental && ev->transient != PLLHIP_EVAL_TRANSIENT_OFF) partitions_transient(ev, transient, 1);
-  failed = injected_fault() || !update_pmatrices(ev);
-
+  if (!failed && !update_pmatrices(ev)) failed = 1;
   cb_self = ev;
   if (!failed && !pll_utree_traverse(ev->root, PLL_TREE_TRAVERSE_POSTORDER, cb_invalid_only, ev->trav, &n))
     failed = 1;
@@ -487,8 +482,228 @@ double pllhip_eval_loglh(pllhip_eval_t * ev, int incremental)
       ev->n_ops += nops;
     }
   }
+  return !failed;
+}
+
+double pllhip_eval_loglh(pllhip_eval_t * ev, int incremental)
+{
+  int failed = 0;
+  /* a full evaluation recomputes every vector: what the last one kept in registers only is given up BEFORE the
+     P-matrices change (nothing is recomputed for them), and this one may keep its own in registers */
+  const int transient = !incremental && (ev->transient == PLLHIP_EVAL_TRANSIENT_ON ||
+                                         (ev->transient == PLLHIP_EVAL_TRANSIENT_AUTO && ev->last_was_full));
+  ev->last_was_full = !incremental;
+  if (!incremental) pllhip_eval_invalidate_all(ev);
+  pll_errno = 0;
+  if (!incremental && ev->transient != PLLHIP_EVAL_TRANSIENT_OFF) partitions_transient(ev, transient, 1);
+  failed = !update_vectors(ev, injected_fault());
   if (transient) partitions_transient(ev, 0, 0);
   return edge_loglh(ev, ev->root, failed);
+}
+
+/* ---------------------------------------------------------------------- */
+/* Marginal ancestral states of every inner node                          */
+/* (pllmod_treeinfo_compute_ancestral, src/tree/treeinfo.c:1611-1718)      */
+/* ---------------------------------------------------------------------- */
+
+void pllhip_eval_destroy_ancestral(pllhip_ancestral_t * anc)
+{
+  unsigned int i;
+  if (!anc) return;
+  for (i = 0; i < anc->node_count; ++i)
+  {
+    if (anc->states) free(anc->states[i]);
+    if (anc->state_probs) free(anc->state_probs[i]);
+    if (anc->probs) free(anc->probs[i]);
+  }
+  free(anc->nodes); free(anc->partition_indices); free(anc->site_offset); free(anc->prob_offset);
+  free(anc->states); free(anc->state_probs); free(anc->probs);
+  free(anc);
+}
+
+/* first index of the row maximum (0 for an all-zero row) and the maximum: the rule of the device summary */
+static void summarise_rows(const double * probs, size_t sites, unsigned int states, unsigned char * st, double * sp)
+{
+  size_t n;
+  unsigned int i;
+  for (n = 0; n < sites; ++n)
+  {
+    const double * row = probs + n * states;
+    double best = row[0];
+    unsigned int idx = 0;
+    for (i = 1; i < states; ++i)
+      if (row[i] > best) { best = row[i]; idx = i; }
+    st[n] = (unsigned char)idx;
+    sp[n] = best;
+  }
+}
+
+pllhip_ancestral_t * pllhip_eval_compute_ancestral(pllhip_eval_t * ev, unsigned int flags)
+{
+  unsigned int i, p, k, n = 0, local = 0;
+  int failed = 0;
+  pll_unode_t * const old_root = ev->root;
+  pllhip_ancestral_t * anc = NULL;
+  pllhip_anc_batch_t ** batches = NULL;     /* [local]: one device batch per partition (the product) */
+  double * scratch = NULL;                  /* the oracle without PLLHIP_ANC_PROBS: one node's table */
+  const int device = pllhip_node_ancestral_batch && pllhip_node_ancestral_begin && pllhip_node_ancestral_add &&
+                     pllhip_node_ancestral_finish;
+  const int want_probs = (flags & PLLHIP_ANC_PROBS) != 0;
+
+  pll_errno = 0;
+  if (flags & ~PLLHIP_ANC_PROBS)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "unknown flags for the ancestral states");
+    return NULL;
+  }
+  for (p = 0; p < ev->nparts; ++p)
+    if (ev->parts[p])
+    {
+      if (ev->parts[p]->states > 256)
+      {
+        pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "partition %u: more than 256 states do not fit the state array", p);
+        return NULL;
+      }
+      ++local;
+    }
+  anc = (pllhip_ancestral_t *)calloc(1, sizeof(*anc));
+  if (!anc) goto nomem;
+  anc->node_count = ev->inner;
+  anc->partition_count = local;
+  anc->nodes = (pll_unode_t **)calloc(ev->inner ? ev->inner : 1, sizeof(*anc->nodes));
+  anc->partition_indices = (unsigned int *)calloc(local ? local : 1, sizeof(unsigned int));
+  anc->site_offset = (size_t *)calloc((size_t)local + 1, sizeof(size_t));
+  anc->prob_offset = (size_t *)calloc((size_t)local + 1, sizeof(size_t));
+  anc->states = (unsigned char **)calloc(ev->inner ? ev->inner : 1, sizeof(*anc->states));
+  anc->state_probs = (double **)calloc(ev->inner ? ev->inner : 1, sizeof(*anc->state_probs));
+  if (want_probs) anc->probs = (double **)calloc(ev->inner ? ev->inner : 1, sizeof(*anc->probs));
+  if (!anc->nodes || !anc->partition_indices || !anc->site_offset || !anc->prob_offset || !anc->states ||
+      !anc->state_probs || (want_probs && !anc->probs))
+    goto nomem;
+  for (p = 0, k = 0; p < ev->nparts; ++p)
+  {
+    if (!ev->parts[p]) continue;
+    anc->partition_indices[k] = p;
+    anc->site_offset[k + 1] = anc->site_offset[k] + ev->parts[p]->sites;
+    anc->prob_offset[k + 1] = anc->prob_offset[k] + (size_t)ev->parts[p]->sites * ev->parts[p]->states;
+    ++k;
+  }
+  /* the reference's order: a full post-order traversal from the tree's vroot, inner nodes kept */
+  if (!pll_utree_traverse(ev->tree->vroot, PLL_TREE_TRAVERSE_POSTORDER, cb_all, ev->trav, &n)) goto fail;
+  for (i = 0, k = 0; i < n; ++i)
+    if (ev->trav[i]->next)
+    {
+      if (k == anc->node_count)
+      {
+        pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "the tree holds more inner nodes than it declares");
+        goto fail;
+      }
+      anc->nodes[k++] = ev->trav[i];
+    }
+  if (k != anc->node_count)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "the traversal from vroot does not reach every inner node");
+    goto fail;
+  }
+  for (i = 0; i < anc->node_count; ++i)
+  {
+    const size_t ns = anc->site_offset[local], np = anc->prob_offset[local];
+    anc->states[i] = (unsigned char *)calloc(ns ? ns : 1, 1);
+    anc->state_probs[i] = (double *)calloc(ns ? ns : 1, sizeof(double));
+    if (want_probs) anc->probs[i] = (double *)calloc(np ? np : 1, sizeof(double));
+    if (!anc->states[i] || !anc->state_probs[i] || (want_probs && !anc->probs[i])) goto nomem;
+  }
+  if (device)
+  {
+    batches = (pllhip_anc_batch_t **)calloc(local ? local : 1, sizeof(*batches));
+    if (!batches) goto nomem;
+    for (k = 0; k < local; ++k)
+    {
+      batches[k] = pllhip_node_ancestral_begin(ev->parts[anc->partition_indices[k]], flags, anc->node_count);
+      if (!batches[k]) goto fail;
+    }
+  }
+  else if (!want_probs)
+  {
+    size_t widest = 1;
+    for (k = 0; k < local; ++k)
+      if (anc->prob_offset[k + 1] - anc->prob_offset[k] > widest) widest = anc->prob_offset[k + 1] - anc->prob_offset[k];
+    scratch = (double *)calloc(widest, sizeof(double));
+    if (!scratch) goto nomem;
+  }
+
+  /* per node: root at its record, the invalid vectors and P-matrices of that root, one entry per partition.  On the
+     device nothing waits here: an entry's kernel reads the two vectors in stream order, before the next re-rooting
+     overwrites their slots. */
+  ev->last_was_full = 0;
+  for (i = 0; i < anc->node_count && !failed; ++i)
+  {
+    const pll_unode_t * node = anc->nodes[i];
+    ev->root = anc->nodes[i];
+    if (!update_vectors(ev, 0)) { failed = 1; break; }
+    for (k = 0; k < local && !failed; ++k)
+    {
+      pll_partition_t * part = ev->parts[anc->partition_indices[k]];
+      const unsigned int * params = ev->params[anc->partition_indices[k]];
+      unsigned char * st = anc->states[i] + anc->site_offset[k];
+      double * sp = anc->state_probs[i] + anc->site_offset[k];
+      double * pr = want_probs ? anc->probs[i] + anc->prob_offset[k] : NULL;
+      if (device)
+      {
+        if (!pllhip_node_ancestral_add(batches[k], node->clv_index, node->back->clv_index, node->pmatrix_index,
+                                       params, st, sp, pr))
+          failed = 1;
+      }
+      else
+      {
+        double * table = want_probs ? pr : scratch;
+        if (!pll_compute_node_ancestral(part, node->clv_index, node->scaler_index, node->back->clv_index,
+                                        node->back->scaler_index, node->pmatrix_index, params, table))
+          failed = 1;
+        else summarise_rows(table, part->sites, part->states, st, sp);
+      }
+    }
+  }
+  if (batches)
+  {
+    /* one wait per staging chunk: here for the last one.  Every batch is finished, also after a failure. */
+    const int code = pll_errno;
+    char msg[200];
+    memcpy(msg, pll_errmsg, sizeof(msg));
+    for (k = 0; k < local; ++k)
+      if (batches[k] && !pllhip_node_ancestral_finish(batches[k]) && !failed)
+      {
+        failed = 1;
+        memcpy(msg, pll_errmsg, sizeof(msg));
+      }
+    if (failed && code) { pll_errno = code; memcpy(pll_errmsg, msg, sizeof(msg)); }
+    free(batches);
+    batches = NULL;
+  }
+  if (failed) goto fail;
+  free(scratch);
+  ev->root = old_root;
+  return anc;
+
+nomem:
+  pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the ancestral states");
+fail:
+  if (batches)
+  {
+    const int code = pll_errno;
+    char msg[200];
+    memcpy(msg, pll_errmsg, sizeof(msg));
+    for (k = 0; k < local; ++k)
+      if (batches[k]) (void)pllhip_node_ancestral_finish(batches[k]);
+    free(batches);
+    pll_errno = code;
+    memcpy(pll_errmsg, msg, sizeof(msg));
+  }
+  if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "ancestral states: the traversal failed");
+  free(scratch);
+  pllhip_eval_destroy_ancestral(anc);
+  ev->root = old_root;
+  return NULL;
 }
 
 /* ---------------------------------------------------------------------- */

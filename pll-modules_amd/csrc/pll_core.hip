@@ -26,6 +26,7 @@
 #include "kernels_s16.hpp"
 #include "kernels_repeats.hpp"
 #include "kernels_newton_s4.hpp"
+#include "kernels_ancestral.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -4597,6 +4598,317 @@ int pll_compute_node_ancestral(pll_partition_t * p, unsigned int node_clv_index,
   PLLHIP_TRY(hipStreamSynchronize(e->stream));
   (void)hipFree(d_out);
   return PLL_SUCCESS;
+}
+
+}   // extern "C"
+
+namespace pllhip {
+
+// ---------------------------------------------------------------------------
+// pllhip_node_ancestral_begin / _add / _finish / _batch: marginal ancestral states of many nodes with the results
+// staged on the device (kernels_ancestral.hpp).  An entry's kernel writes its summary (and, with PLLHIP_ANC_PROBS,
+// its table) into a slot of one staging buffer per device, allocated once per batch; the host copies are enqueued
+// and waited for once per staging chunk.  A slot is written in stream order, so the vectors of an entry may be
+// overwritten by whatever the caller enqueues next.
+// ---------------------------------------------------------------------------
+struct AncPending { unsigned slot; unsigned char * states; double * state_probs; double * probs; };
+
+struct AncStage                       // one device's part of a batch: an ordinary partition, or a shard
+{
+  pll_partition_t * p = nullptr;
+  size_t first = 0;                   // first site of this part in the caller's arrays
+  unsigned char * d_buf = nullptr;
+  size_t off_probs_state = 0, off_probs = 0, entry_bytes = 0;
+  unsigned cap = 0;
+  bool table = false;                 // the slot holds a sites x states table (asked for, or the family needs it)
+  std::vector<AncPending> pending;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+  double kernel_ms = 0.0;             // between the events of the entries delivered so far
+  unsigned long long chunks = 0;
+};
+
+}   // namespace pllhip
+
+struct pllhip_anc_batch
+{
+  pll_partition_t * p;
+  unsigned flags;
+  bool failed;
+  std::vector<pllhip::AncStage> stages;
+};
+
+namespace pllhip {
+
+static thread_local double g_anc_kernel_ms = 0.0;
+static thread_local unsigned long long g_anc_chunks = 0;
+
+static size_t anc_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+static size_t anc_budget()
+{
+  const char * env = getenv("PLLHIP_ANC_STAGING_BYTES");
+  const long long v = env ? atoll(env) : 0;
+  return v > 0 ? (size_t)v : (size_t)1 << 30;
+}
+
+static bool anc_family_fused(const Engine * e)
+{
+  return e->family == KernelFamily::S4 || e->family == KernelFamily::S20 || e->family == KernelFamily::S16;
+}
+
+static int anc_stage_init(AncStage & st, pll_partition_t * p, size_t first, unsigned flags, unsigned expected)
+{
+  Engine * e = engine_of(p);
+  st.p = p;
+  st.first = first;
+  st.table = (flags & PLLHIP_ANC_PROBS) || !anc_family_fused(e);
+  const size_t n = e->Nreal;
+  st.off_probs_state = anc_align(n);
+  st.off_probs = st.off_probs_state + anc_align(n * sizeof(double));
+  st.entry_bytes = st.off_probs + (st.table ? anc_align(n * e->S * sizeof(double)) : 0);
+  // (an entry is the unit: a budget below one entry still stages one)
+  const size_t fit = std::max<size_t>(1, anc_budget() / st.entry_bytes);
+  st.cap = (unsigned)std::min<size_t>(fit, expected ? expected : 0xffffffffu);
+  if (!n) return PLL_SUCCESS;
+  PLLHIP_TRY(hipSetDevice(e->device));
+  return dev_alloc(&st.d_buf, st.entry_bytes * st.cap, "ancestral-state staging") ? PLL_SUCCESS : PLL_FAILURE;
+}
+
+// copies of every staged entry to the caller's arrays, one wait
+static int anc_stage_flush(AncStage & st, unsigned flags)
+{
+  if (st.pending.empty()) return PLL_SUCCESS;
+  Engine * e = engine_of(st.p);
+  const size_t n = e->Nreal;
+  PLLHIP_TRY(hipSetDevice(e->device));
+  for (const AncPending & pd : st.pending)
+  {
+    const unsigned char * slot = st.d_buf + st.entry_bytes * pd.slot;
+    PLLHIP_TRY(hipMemcpyAsync(pd.states + st.first, slot, n, hipMemcpyDeviceToHost, e->stream));
+    PLLHIP_TRY(hipMemcpyAsync(pd.state_probs + st.first, slot + st.off_probs_state, n * sizeof(double),
+                              hipMemcpyDeviceToHost, e->stream));
+    if (flags & PLLHIP_ANC_PROBS)
+      PLLHIP_TRY(hipMemcpyAsync(pd.probs + st.first * e->S, slot + st.off_probs, n * e->S * sizeof(double),
+                                hipMemcpyDeviceToHost, e->stream));
+  }
+  const size_t staged = st.pending.size();
+  st.pending.clear();
+  PLLHIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t k = 0; k < staged && k < st.events.size(); ++k)
+  {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, st.events[k].first, st.events[k].second) == hipSuccess) st.kernel_ms += ms;
+  }
+  st.chunks++;
+  return PLL_SUCCESS;
+}
+
+static int anc_allow_lds()
+{
+#define PLLHIP_ATTR(KK) \
+  PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_anc_s16<KK>), hipFuncAttributeMaxDynamicSharedMemorySize, S16_MAX_LDS_BYTES))
+  PLLHIP_ATTR(5); PLLHIP_ATTR(6); PLLHIP_ATTR(7); PLLHIP_ATTR(8);
+#undef PLLHIP_ATTR
+  return PLL_SUCCESS;
+}
+
+static int anc_stage_add(AncStage & st, unsigned flags, unsigned node_clv_index, unsigned other_clv_index,
+                         unsigned matrix_index, const unsigned * freqs_indices, unsigned char * states,
+                         double * state_probs, double * probs)
+{
+  pll_partition_t * p = st.p;
+  Engine * e = engine_of(p);
+  PLLHIP_TRY(hipSetDevice(e->device));
+  if (!check_clv_index(e, node_clv_index, "node") || !check_clv_index(e, other_clv_index, "other")) return PLL_FAILURE;
+  if (matrix_index >= e->nmat)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "matrix index out of range");
+    return PLL_FAILURE;
+  }
+  if (!sync_model(p) || !flush_pmatrices(p) || !ensure_luts(p)) return PLL_FAILURE;
+  const unsigned N = e->Nreal;
+  if (!N) return PLL_SUCCESS;
+  if (!need_clv(e, node_clv_index) || !need_clv(e, other_clv_index)) return PLL_FAILURE;
+  if (st.pending.size() == st.cap && !anc_stage_flush(st, flags)) return PLL_FAILURE;
+  const unsigned slot = (unsigned)st.pending.size();
+  unsigned char * base = st.d_buf + st.entry_bytes * slot;
+  AncOut out;
+  out.states = base;
+  out.state_probs = reinterpret_cast<double *>(base + st.off_probs_state);
+  out.probs = st.table ? reinterpret_cast<double *>(base + st.off_probs) : nullptr;
+
+  const ModelView mv = model_view(e);
+  const ParamIdx fidx = make_params(p, freqs_indices);
+  const NodeRef node = node_ref(e, node_clv_index), other = node_ref(e, other_clv_index);
+  const double * pm = e->d_pmat + (size_t)matrix_index * e->R * e->S * e->Sp;
+  const double * lut = other.codes ? e->d_lut + (size_t)matrix_index * e->R * e->lut_codes * e->S : nullptr;
+  if (st.events.size() <= slot)
+  {
+    std::pair<hipEvent_t, hipEvent_t> ev;
+    PLLHIP_TRY(hipEventCreate(&ev.first));
+    if (hipEventCreate(&ev.second) != hipSuccess) { (void)hipEventDestroy(ev.first); set_error(PLL_ERROR_HIP_RUNTIME, "hipEventCreate"); return PLL_FAILURE; }
+    st.events.push_back(ev);
+  }
+  PLLHIP_TRY(hipEventRecord(st.events[slot].first, e->stream));
+  if (e->family == KernelFamily::S20 || e->family == KernelFamily::S16)
+  {
+    const unsigned nblk = (N + S20_BS - 1) / S20_BS;
+    const unsigned grid = std::max(1u, std::min((nblk + 3) / 4, e->cu_count * 8));
+    const bool tbl = out.probs != nullptr;
+    if (e->family == KernelFamily::S20)
+      hipLaunchKernelGGL(k_anc_s20, dim3(grid), dim3(256), sizeof(double) * anc_blocked_lds<5>(e->R, e->S, tbl), e->stream,
+                         mv, fidx, node, other, pm, lut, e->lut_codes, e->d_tipmap, N, nblk, e->R, out);
+    else
+    {
+      const unsigned ks = s16_ks(e);
+      if (sizeof(double) * (e->R * s16_frags(e) + 4 * S20_BS * anc_tile_stride(e->S)) > 64 * 1024 && !anc_allow_lds())
+        return PLL_FAILURE;
+#define PLLHIP_CALL(KK) \
+      hipLaunchKernelGGL(k_anc_s16<KK>, dim3(grid), dim3(256), sizeof(double) * anc_blocked_lds<KK>(e->R, e->S, tbl), e->stream, \
+                         mv, fidx, node, other, pm, lut, e->lut_codes, e->d_tipmap, N, nblk, e->R, out)
+      PLLHIP_DISPATCH_KS(ks, PLLHIP_CALL);
+#undef PLLHIP_CALL
+    }
+  }
+  else
+  {
+    const unsigned gx = (unsigned)std::min<unsigned long long>(((unsigned long long)N + 255) / 256, 4096);
+    if (e->family == KernelFamily::S4)
+      hipLaunchKernelGGL(k_anc_s4, dim3(gx), dim3(256), 0, e->stream,
+                         mv, fidx, node, other, pm, lut, e->lut_codes, e->d_tipmap, N, e->R, out);
+    else
+    {
+      hipLaunchKernelGGL(k_anc_generic, dim3(gx), dim3(256), 0, e->stream,
+                         mv, fidx, node, other, pm, e->d_tipmap, e->rows, N, e->R, out.probs);
+      PLLHIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_anc_summary, dim3(gx), dim3(256), 0, e->stream,
+                         out.probs, N, e->S, out.states, out.state_probs);
+    }
+  }
+  PLLHIP_TRY(hipGetLastError());
+  PLLHIP_TRY(hipEventRecord(st.events[slot].second, e->stream));
+  st.pending.push_back(AncPending{slot, states, state_probs, probs});
+  return PLL_SUCCESS;
+}
+
+static void anc_stage_release(AncStage & st)
+{
+  if (!st.p) return;
+  (void)hipSetDevice(engine_of(st.p)->device);
+  for (auto & ev : st.events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+  st.events.clear();
+  if (st.d_buf) (void)hipFree(st.d_buf);
+  st.d_buf = nullptr;
+}
+
+}   // namespace pllhip
+
+extern "C" {
+
+pllhip_anc_batch_t * pllhip_node_ancestral_begin(pll_partition_t * p, unsigned int flags, unsigned int expected)
+{
+  if (!p || (flags & ~PLLHIP_ANC_PROBS))
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "ancestral states: no partition, or unknown flags");
+    return nullptr;
+  }
+  if (p->states > 256)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "ancestral states: more than 256 states do not fit the state array");
+    return nullptr;
+  }
+  Engine * e = engine_of(p);
+  pllhip_anc_batch_t * b = new pllhip_anc_batch;
+  b->p = p;
+  b->flags = flags;
+  b->failed = false;
+  const size_t parts = e->shards.empty() ? 1 : e->shards.size();
+  b->stages.resize(parts);
+  for (size_t k = 0; k < parts; ++k)
+    if (!anc_stage_init(b->stages[k], e->shards.empty() ? p : e->shards[k], e->shards.empty() ? 0 : e->shard_first[k],
+                        flags, expected))
+    {
+      for (AncStage & st : b->stages) anc_stage_release(st);
+      delete b;
+      return nullptr;
+    }
+  return b;
+}
+
+int pllhip_node_ancestral_add(pllhip_anc_batch_t * b, unsigned int node_clv_index, unsigned int other_clv_index,
+                              unsigned int matrix_index, const unsigned int * freqs_indices,
+                              unsigned char * states, double * state_probs, double * probs)
+{
+  if (!b || !states || !state_probs || !freqs_indices || ((b->flags & PLLHIP_ANC_PROBS) && !probs))
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "ancestral states: a result array is missing");
+    if (b) b->failed = true;
+    return PLL_FAILURE;
+  }
+  if (b->failed)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "ancestral states: the batch has failed already");
+    return PLL_FAILURE;
+  }
+  Engine * e = engine_of(b->p);
+  for (size_t k = 0; k < b->stages.size(); ++k)
+  {
+    if (!e->shards.empty()) push_model(b->p, e->shards[k]);
+    if (!anc_stage_add(b->stages[k], b->flags, node_clv_index, other_clv_index, matrix_index, freqs_indices,
+                       states, state_probs, probs))
+    {
+      b->failed = true;
+      return PLL_FAILURE;
+    }
+  }
+  return PLL_SUCCESS;
+}
+
+int pllhip_node_ancestral_finish(pllhip_anc_batch_t * b)
+{
+  if (!b) return PLL_SUCCESS;
+  int ok = b->failed ? PLL_FAILURE : PLL_SUCCESS;
+  double ms = 0.0;
+  unsigned long long chunks = 0;
+  for (AncStage & st : b->stages)
+  {
+    // (after a failure: whatever is in flight still has to leave the caller's arrays alone before they go away)
+    if (b->failed) { if (st.p && st.d_buf) (void)hipStreamSynchronize(engine_of(st.p)->stream); }
+    else if (!anc_stage_flush(st, b->flags)) ok = PLL_FAILURE;
+    ms += st.kernel_ms;
+    chunks = std::max(chunks, st.chunks);
+    anc_stage_release(st);
+  }
+  g_anc_kernel_ms = ms;
+  g_anc_chunks = chunks;
+  delete b;
+  return ok;
+}
+
+int pllhip_node_ancestral_batch(pll_partition_t * p, unsigned int count, const unsigned int * node_clv,
+                                const unsigned int * other_clv, const unsigned int * matrix_indices,
+                                const unsigned int * freqs_indices, unsigned int flags,
+                                unsigned char * const * states, double * const * state_probs, double * const * probs)
+{
+  if (!count) return PLL_SUCCESS;
+  if (!node_clv || !other_clv || !matrix_indices || !states || !state_probs || ((flags & PLLHIP_ANC_PROBS) && !probs))
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "ancestral states: an argument array is missing");
+    return PLL_FAILURE;
+  }
+  pllhip_anc_batch_t * b = pllhip_node_ancestral_begin(p, flags, count);
+  if (!b) return PLL_FAILURE;
+  for (unsigned k = 0; k < count; ++k)
+    if (!pllhip_node_ancestral_add(b, node_clv[k], other_clv[k], matrix_indices[k], freqs_indices, states[k],
+                                   state_probs[k], (flags & PLLHIP_ANC_PROBS) ? probs[k] : nullptr))
+      break;
+  return pllhip_node_ancestral_finish(b);
+}
+
+void pllhip_node_ancestral_last_times(double * kernel_ms, unsigned long long * chunks)
+{
+  if (kernel_ms) *kernel_ms = g_anc_kernel_ms;
+  if (chunks) *chunks = g_anc_chunks;
 }
 
 // ===========================================================================

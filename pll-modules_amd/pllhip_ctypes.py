@@ -193,7 +193,9 @@ pllhip_treeset_create pllhip_treeset_destroy pllhip_treeset_count pllhip_treeset
 pllhip_treeset_rf_matrix pllhip_treeset_rf_to pllhip_treeset_support pllhip_treeset_last_sums pllhip_treeset_plan
 pllhip_treeset_last_times pllhip_treeset_last_counts
 pllhip_treeset_consensus pllhip_treeset_consensus_tree pllhip_treeset_tree_from_splits pllhip_consensus_needs
-pllhip_treeset_last_consensus_counts""".split()
+pllhip_treeset_last_consensus_counts
+pllhip_node_ancestral_batch pllhip_node_ancestral_begin pllhip_node_ancestral_add pllhip_node_ancestral_finish
+pllhip_node_ancestral_last_times""".split()
 
 
 def _u32(a):
@@ -219,6 +221,28 @@ class CompressResult:
     site_pattern_map (uint32 per original site; the _msa form only), probe_steps / compares (pllhip_compress_last_counts)"""
     ok, errno, errmsg, length, rows, weights, site_pattern_map = False, 0, "", 0, None, None, None
     probe_steps, compares = 0, 0
+
+
+PLLHIP_ANC_PROBS = 1
+
+
+class AncestralResult(C.Structure):
+    """pllhip_ancestral_t (include/pllhip_eval.h)"""
+    _fields_ = [("node_count", C.c_uint), ("partition_count", C.c_uint),
+                ("nodes", C.POINTER(C.c_void_p)), ("partition_indices", c_uint_p),
+                ("site_offset", C.POINTER(C.c_size_t)), ("prob_offset", C.POINTER(C.c_size_t)),
+                ("states", C.POINTER(C.POINTER(C.c_ubyte))), ("state_probs", C.POINTER(c_double_p)),
+                ("probs", C.POINTER(c_double_p))]
+
+
+class Ancestral:
+    """numpy copy of a pllhip_ancestral_t: node_clv / node_index of the records in the reference's order,
+    partition_indices, site_offset / prob_offset, states [node][sites] (uint8), state_probs [node][sites],
+    probs [node][sum of sites x states] or None; rows(i, k) = the sites x states table of node i, local partition k"""
+
+    def rows(self, i, k, states):
+        a, b = self.prob_offset[k], self.prob_offset[k + 1]
+        return self.probs[i, a:b].reshape(-1, states)
 
 
 class PllLib:
@@ -344,6 +368,11 @@ class PllLib:
             L.pllhip_eval_spr_round.restype = C.c_double
             L.pllhip_eval_spr_round.argtypes = [C.c_void_p, C.POINTER(SprParams), C.POINTER(SprCutoff),
                                                 C.POINTER(SprStats)]
+            if hasattr(L, "pllhip_eval_compute_ancestral"):
+                L.pllhip_eval_compute_ancestral.restype = C.POINTER(AncestralResult)
+                L.pllhip_eval_compute_ancestral.argtypes = [C.c_void_p, C.c_uint]
+                L.pllhip_eval_destroy_ancestral.restype = None
+                L.pllhip_eval_destroy_ancestral.argtypes = [C.POINTER(AncestralResult)]
             for fn in ("pllhip_eval_ops", "pllhip_eval_pmatrix_updates", "pllhip_eval_derivative_calls",
                        "pllhip_eval_newton_iterations"):
                 getattr(L, fn).restype = C.c_ulong
@@ -404,6 +433,17 @@ class PllLib:
             L.pllhip_results_fetch.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_int, c_double_p]
             L.pllhip_results_poison.argtypes = [C.c_void_p]
             L.pllhip_results_poison.restype = None
+        if hasattr(L, "pllhip_node_ancestral_batch"):
+            L.pllhip_node_ancestral_batch.argtypes = [pp, C.c_uint, c_uint_p, c_uint_p, c_uint_p, c_uint_p, C.c_uint,
+                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                      C.POINTER(C.c_void_p)]
+            L.pllhip_node_ancestral_begin.restype = C.c_void_p
+            L.pllhip_node_ancestral_begin.argtypes = [pp, C.c_uint, C.c_uint]
+            L.pllhip_node_ancestral_add.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, c_uint_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]
+            L.pllhip_node_ancestral_finish.argtypes = [C.c_void_p]
+            L.pllhip_node_ancestral_last_times.restype = None
+            L.pllhip_node_ancestral_last_times.argtypes = [c_double_p, C.POINTER(C.c_ulonglong)]
         if hasattr(L, "pllhip_msa_compute_stats"):
             L.pllhip_empirical_frequencies.restype = c_double_p
             L.pllhip_empirical_frequencies.argtypes = [pp]
@@ -757,6 +797,34 @@ class Instance:
                                                  self.params_p, out.ctypes.data_as(c_double_p)):
             raise RuntimeError(self.lib.errmsg)
         return out.reshape(self.N, self.S)
+
+    def node_ancestral_batch(self, nodes, others, matrices, flags=0, pad=0):
+        """pllhip_node_ancestral_batch over the triples (nodes[k], others[k], matrices[k]):
+        (states [count][N] uint8, state_probs [count][N], probs [count][N][S] or None).  pad: that many canary
+        elements (0xA5 bytes / -7.0) in front of and behind every host array, returned as a fourth value
+        `intact` (bool) -- for tests of the bounds of what the library writes"""
+        nd, ot, mi = _u32(nodes), _u32(others), _u32(matrices)
+        cnt, N, S = len(nd), self.N, self.S
+        want = bool(flags & PLLHIP_ANC_PROBS)
+        st = np.full((cnt, N + 2 * pad), 0xA5, dtype=np.uint8)
+        sp = np.full((cnt, N + 2 * pad), -7.0)
+        pr = np.full((cnt, N * S + 2 * pad), -7.0) if want else None
+
+        def ptrs(a, item):
+            return (C.c_void_p * max(1, cnt))(*[a.ctypes.data + (k * a.shape[1] + pad) * item for k in range(cnt)])
+        self.lib.errno = 0
+        if not self.L.pllhip_node_ancestral_batch(self.p, cnt, nd.ctypes.data_as(c_uint_p), ot.ctypes.data_as(c_uint_p),
+                                                  mi.ctypes.data_as(c_uint_p), self.params_p, flags, ptrs(st, 1),
+                                                  ptrs(sp, 8), ptrs(pr, 8) if want else None):
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        out = (st[:, pad:pad + N].copy(), sp[:, pad:pad + N].copy(),
+               pr[:, pad:pad + N * S].reshape(cnt, N, S).copy() if want else None)
+        if not pad:
+            return out
+        intact = bool((st[:, :pad] == 0xA5).all() and (st[:, pad + N:] == 0xA5).all() and
+                      (sp[:, :pad] == -7.0).all() and (sp[:, pad + N:] == -7.0).all() and
+                      (not want or ((pr[:, :pad] == -7.0).all() and (pr[:, pad + N * S:] == -7.0).all())))
+        return out + (intact,)
 
     def alloc_sumtable(self):
         """caller-owned buffer exactly as src/tree/treeinfo.c:336-340 allocates it"""
@@ -1407,6 +1475,35 @@ class Evaluation:
         if v != v:
             raise RuntimeError(self.lib.errmsg)
         return v
+
+    def compute_ancestral(self, flags=0):
+        """pllhip_eval_compute_ancestral -> Ancestral (numpy copies; the C object is destroyed here)"""
+        self.lib.errno = 0
+        ptr = self.L.pllhip_eval_compute_ancestral(self.ev, flags)
+        if not ptr:
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        try:
+            a, out = ptr.contents, Ancestral()
+            nn, npart = a.node_count, a.partition_count
+            recs = [C.cast(a.nodes[i], C.POINTER(UNode)).contents for i in range(nn)]
+            out.node_clv = np.array([r.clv_index for r in recs], dtype=np.uint32)
+            out.node_index = np.array([r.node_index for r in recs], dtype=np.uint32)
+            out.partition_indices = np.array([a.partition_indices[k] for k in range(npart)], dtype=np.uint32)
+            out.site_offset = np.array([a.site_offset[k] for k in range(npart + 1)], dtype=np.int64)
+            out.prob_offset = np.array([a.prob_offset[k] for k in range(npart + 1)], dtype=np.int64)
+            ns, npr = int(out.site_offset[-1]), int(out.prob_offset[-1])
+            out.states = np.zeros((nn, ns), dtype=np.uint8)
+            out.state_probs = np.zeros((nn, ns))
+            out.probs = np.zeros((nn, npr)) if a.probs else None
+            for i in range(nn):
+                if ns:
+                    out.states[i] = np.ctypeslib.as_array(a.states[i], shape=(ns,))
+                    out.state_probs[i] = np.ctypeslib.as_array(a.state_probs[i], shape=(ns,))
+                if a.probs and npr:
+                    out.probs[i] = np.ctypeslib.as_array(a.probs[i], shape=(npr,))
+            return out
+        finally:
+            self.L.pllhip_eval_destroy_ancestral(ptr)
 
     def optimize_branches(self, bl_min=1e-4, bl_max=10.0, eps=0.01, iters=8, radius=-1):
         self.lib.errno = 0
