@@ -566,7 +566,8 @@ PLL_EXPORT void pllhip_treeset_last_consensus_counts(unsigned long long * accept
  * both taken from the very doubles `probs` would hold, so states[n] == argmax(probs[n]) holds exactly.
  * The staging buffer is allocated once per batch; when the entries do not fit PLLHIP_ANC_STAGING_BYTES (environment,
  * read at the call; default 1 GiB, never less than one entry) they go through it in chunks with one wait and one
- * round of copies per chunk.  Results do not depend on the chunk size. */
+ * round of copies per chunk.  Results do not depend on the chunk size, nor on PLLHIP_ANC_BLOCKS (environment, read at
+ * the call; unset or 0: no cap), a cap on the workgroups of each of its launches that the tests use. */
 #define PLLHIP_ANC_PROBS (1u << 0)   /* also return the full sites x states table */
 
 /* One (node, other, matrix) triple per entry, same meaning as the arguments of pll_compute_node_ancestral.

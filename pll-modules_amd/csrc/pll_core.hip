@@ -4651,6 +4651,16 @@ static size_t anc_budget()
   return v > 0 ? (size_t)v : (size_t)1 << 30;
 }
 
+// PLLHIP_ANC_BLOCKS: a cap on the workgroups of every ancestral-state launch (0 or unset: none), read at every call.
+// For tests: with a small cap a wave walks many site blocks, which the default grid asks for only above ~260 000 sites.
+static unsigned anc_grid(unsigned long long wanted)
+{
+  const char * env = getenv("PLLHIP_ANC_BLOCKS");
+  const long long cap = env ? atoll(env) : 0;
+  if (cap > 0 && (unsigned long long)cap < wanted) wanted = (unsigned long long)cap;
+  return (unsigned)std::max<unsigned long long>(1, wanted);
+}
+
 static bool anc_family_fused(const Engine * e)
 {
   return e->family == KernelFamily::S4 || e->family == KernelFamily::S20 || e->family == KernelFamily::S16;
@@ -4753,7 +4763,7 @@ static int anc_stage_add(AncStage & st, unsigned flags, unsigned node_clv_index,
   if (e->family == KernelFamily::S20 || e->family == KernelFamily::S16)
   {
     const unsigned nblk = (N + S20_BS - 1) / S20_BS;
-    const unsigned grid = std::max(1u, std::min((nblk + 3) / 4, e->cu_count * 8));
+    const unsigned grid = anc_grid(std::min((nblk + 3) / 4, e->cu_count * 8));
     const bool tbl = out.probs != nullptr;
     if (e->family == KernelFamily::S20)
       hipLaunchKernelGGL(k_anc_s20, dim3(grid), dim3(256), sizeof(double) * anc_blocked_lds<5>(e->R, e->S, tbl), e->stream,
@@ -4772,7 +4782,7 @@ static int anc_stage_add(AncStage & st, unsigned flags, unsigned node_clv_index,
   }
   else
   {
-    const unsigned gx = (unsigned)std::min<unsigned long long>(((unsigned long long)N + 255) / 256, 4096);
+    const unsigned gx = anc_grid(std::min<unsigned long long>(((unsigned long long)N + 255) / 256, 4096));
     if (e->family == KernelFamily::S4)
       hipLaunchKernelGGL(k_anc_s4, dim3(gx), dim3(256), 0, e->stream,
                          mv, fidx, node, other, pm, lut, e->lut_codes, e->d_tipmap, N, e->R, out);
