@@ -599,6 +599,69 @@ PLL_EXPORT int pllhip_node_ancestral_finish(pllhip_anc_batch_t * batch);
    of a sharded partition), and its staging chunks (the largest count of any device) */
 PLL_EXPORT void pllhip_node_ancestral_last_times(double * kernel_ms, unsigned long long * chunks);
 
+/* ---- topology tests and bootstrap weights ("Topology tests and bootstrap weights"; DESIGN.md
+ *      section 20) ----
+ * A site-likelihood set holds, on the device pllhip_get_device() names at its creation, a matrix L[trees][patterns]
+ * of per-pattern log-likelihoods -- unweighted, what `persite_lnl` of pll_compute_edge_loglikelihood holds -- and the
+ * pattern weights w (NULL: all 1).  `patterns` is the caller's concatenation of all partitions.  The ascertainment
+ * correction is not a per-site quantity and is in no row. */
+typedef struct pllhip_sitelh pllhip_sitelh_t;
+PLL_EXPORT pllhip_sitelh_t * pllhip_sitelh_create(unsigned int patterns, const unsigned int * weights);
+PLL_EXPORT void pllhip_sitelh_destroy(pllhip_sitelh_t * set);
+PLL_EXPORT unsigned int pllhip_sitelh_count(const pllhip_sitelh_t * set);
+/* row `tree` -> out[patterns] */
+PLL_EXPORT int pllhip_sitelh_get(pllhip_sitelh_t * set, unsigned int tree, double * out);
+/* appends row[patterns] from the host; returns the tree index, or -1 (PLL_ERROR_PARAM_INVALID for a non-finite value) */
+PLL_EXPORT int pllhip_sitelh_add(pllhip_sitelh_t * set, const double * row);
+/* pll_compute_edge_loglikelihood of `partition` with its partition->sites per-pattern values left in row `tree` at
+   `offset`, device to device (through the host for a sharded partition or one on another device).  tree == count opens
+   a new row, whose other patterns are 0 until written.  *lnl (may be NULL) = the value the edge function returns, the
+   ascertainment correction included; the row does not hold that correction.  A non-finite value written this way is
+   found when the set is used: pllhip_sitelh_rell then fails and names row and pattern. */
+PLL_EXPORT int pllhip_sitelh_add_edge(pllhip_sitelh_t * set, unsigned int tree, unsigned int offset,
+                                      pll_partition_t * partition, unsigned int parent_clv_index,
+                                      int parent_scaler_index, unsigned int child_clv_index, int child_scaler_index,
+                                      unsigned int matrix_index, const unsigned int * freqs_indices, double * lnl);
+
+#define PLLHIP_RELL_REPLICATES (1u << 0)   /* also return the replicates x trees matrix of replicate log-likelihoods */
+
+typedef struct pllhip_rell_params
+{
+  unsigned int replicates;      /* B, 1 .. 2^24 - 1 */
+  unsigned long long seed;
+  unsigned int flags;
+  unsigned int batch;           /* replicates per pass (rounded up to 16); 0: chosen from the free device memory */
+} pllhip_rell_params_t;
+
+/* Replicate b draws N = sum of w patterns with the counter-based generator INTEGRATION.md defines (N < 2^40);
+   R[b][t] = sum_s C[b][s] L[t][s].  lnl[t] = sum_s w[s] L[t][s]; best = argmax lnl (lowest index on ties);
+   bp_count / kh_count / sh_count = numerators of the RELL bootstrap proportion and of the one-sided KH and the SH
+   p-values (denominator: replicates); elw = expected likelihood weights.  R, and with it every field, is bit-identical
+   across runs and across `batch`. */
+typedef struct pllhip_rell_result
+{
+  unsigned int trees;
+  unsigned int replicates;
+  unsigned int best;
+  unsigned int batch;           /* the batch used */
+  double * lnl;                 /* [trees] */
+  unsigned int * bp_count;      /* [trees] */
+  unsigned int * kh_count;      /* [trees] */
+  unsigned int * sh_count;      /* [trees] */
+  double * elw;                 /* [trees] */
+  double * replicate_lnl;       /* [replicates][trees] with PLLHIP_RELL_REPLICATES, else NULL */
+} pllhip_rell_result_t;
+
+PLL_EXPORT pllhip_rell_result_t * pllhip_sitelh_rell(pllhip_sitelh_t * set, const pllhip_rell_params_t * params);
+PLL_EXPORT void pllhip_rell_destroy(pllhip_rell_result_t * result);
+/* the last pllhip_sitelh_rell of this thread: device time of its stages in ms between HIP events */
+PLL_EXPORT void pllhip_rell_last_times(double * draw_ms, double * product_ms, double * stats_ms);
+
+/* the count vectors of replicates first .. first + count - 1 for (weights, seed) -- the very vectors
+   pllhip_sitelh_rell uses -- as out[count][patterns], each ready for pll_set_pattern_weights; weights NULL: all 1 */
+PLL_EXPORT int pllhip_bootstrap_weights(const unsigned int * weights, unsigned int patterns, unsigned long long seed,
+                                        unsigned int first, unsigned int count, unsigned int * out);
+
 #ifdef __cplusplus
 }
 #endif

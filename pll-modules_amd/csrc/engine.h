@@ -384,7 +384,7 @@ int eigen_decompose(unsigned S, unsigned Sp, const double * ex, const double * p
 // --- engine services (pll_core.hip) ---
 double loglikelihood_impl(pll_partition_t * p, unsigned pc, int psc, unsigned cc, int csc,
                           int matrix_index, const unsigned * freqs_indices,
-                          double * persite_lnl, const Engine::Sink * deferred);
+                          double * persite_lnl, const Engine::Sink * deferred, double * persite_dev = nullptr);
 int derivatives_impl(pll_partition_t * p, int parent_scaler_index, int child_scaler_index,
                      const double * brlens, unsigned count, const unsigned * params_indices,
                      const double * sumtable, const Engine::Sink * deferred,

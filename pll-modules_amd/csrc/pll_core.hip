@@ -3640,10 +3640,12 @@ namespace pllhip {
 // lnL at an edge (matrix_index >= 0) or at a root vector.  `deferred` == nullptr: the
 // value comes back (one wait); otherwise the total is left at deferred->dst (a device
 // slot or mapped memory, with deferred->flag / seq if the host is to be told), nothing
-// is waited for and the return value is 0.
+// is waited for and the return value is 0.  `persite_dev` (blocking form only): device memory
+// on this engine's device that receives the per-site values of the alignment patterns, copied
+// on the engine's stream and not waited for.
 double loglikelihood_impl(pll_partition_t * p, unsigned pc, int psc, unsigned cc, int csc,
                           int matrix_index, const unsigned * freqs_indices,
-                          double * persite_lnl, const Engine::Sink * deferred)
+                          double * persite_lnl, const Engine::Sink * deferred, double * persite_dev)
 {
   Engine * e = engine_of(p);
   const double fail = -std::numeric_limits<double>::infinity();
@@ -3667,7 +3669,7 @@ double loglikelihood_impl(pll_partition_t * p, unsigned pc, int psc, unsigned cc
     return fail;
   }
   double * const ps_out_req = persite_lnl;
-  if ((persite_lnl || asc) && !e->d_persite)
+  if ((persite_lnl || persite_dev || asc) && !e->d_persite)
     if (!dev_alloc(&e->d_persite, (size_t)e->N, "per-site lnL")) return fail;
   if (asc && !persite_lnl) persite_lnl = e->h_asc;      // any non-null value: "per-site output on"
 
@@ -3691,7 +3693,7 @@ double loglikelihood_impl(pll_partition_t * p, unsigned pc, int psc, unsigned cc
   const bool edge = matrix_index >= 0;
   if (!(edge ? f->lnl : f->root_lnl)(e, mv, fidx, parent, child, pm, lut, scaler_ptr(e, psc),
                                       (edge || f->root_child_scaler) ? scaler_ptr(e, csc) : nullptr,
-                                      persite_lnl ? e->d_persite : nullptr, nblocks)) return fail;
+                                      (persite_lnl || persite_dev) ? e->d_persite : nullptr, nblocks)) return fail;
   double total = 0.0;
   e->counters.lnl_calls++;
   if (deferred)
@@ -3722,6 +3724,10 @@ double loglikelihood_impl(pll_partition_t * p, unsigned pc, int psc, unsigned cc
                                hipMemcpyDeviceToHost, e->stream), "persite copy") ||
         !hip_ok(hipStreamSynchronize(e->stream), "persite sync")) return fail;
   }
+  // a site-likelihood set (pll_rell_dev.hip) takes the alignment patterns on the device, in stream order
+  if (persite_dev && e->Nreal &&
+      !hip_ok(hipMemcpyAsync(persite_dev, e->d_persite, sizeof(double) * e->Nreal, hipMemcpyDeviceToDevice, e->stream),
+              "persite device copy")) return fail;
   return total;
 }
 

@@ -195,7 +195,10 @@ pllhip_treeset_last_times pllhip_treeset_last_counts
 pllhip_treeset_consensus pllhip_treeset_consensus_tree pllhip_treeset_tree_from_splits pllhip_consensus_needs
 pllhip_treeset_last_consensus_counts
 pllhip_node_ancestral_batch pllhip_node_ancestral_begin pllhip_node_ancestral_add pllhip_node_ancestral_finish
-pllhip_node_ancestral_last_times""".split()
+pllhip_node_ancestral_last_times
+pllhip_sitelh_create pllhip_sitelh_destroy pllhip_sitelh_count pllhip_sitelh_get pllhip_sitelh_add
+pllhip_sitelh_add_edge pllhip_sitelh_rell pllhip_rell_destroy pllhip_rell_last_times
+pllhip_bootstrap_weights""".split()
 
 
 def _u32(a):
@@ -243,6 +246,26 @@ class Ancestral:
     def rows(self, i, k, states):
         a, b = self.prob_offset[k], self.prob_offset[k + 1]
         return self.probs[i, a:b].reshape(-1, states)
+
+
+PLLHIP_RELL_REPLICATES = 1
+
+
+class RellParams(C.Structure):
+    """pllhip_rell_params_t"""
+    _fields_ = [("replicates", C.c_uint), ("seed", C.c_ulonglong), ("flags", C.c_uint), ("batch", C.c_uint)]
+
+
+class RellResult(C.Structure):
+    """pllhip_rell_result_t"""
+    _fields_ = [("trees", C.c_uint), ("replicates", C.c_uint), ("best", C.c_uint), ("batch", C.c_uint),
+                ("lnl", c_double_p), ("bp_count", c_uint_p), ("kh_count", c_uint_p), ("sh_count", c_uint_p),
+                ("elw", c_double_p), ("replicate_lnl", c_double_p)]
+
+
+class Rell:
+    """numpy copy of a pllhip_rell_result_t: trees, replicates, best, batch, lnl, bp_count, kh_count, sh_count, elw,
+    R [replicates][trees] or None, times = (draw, product, statistics) in ms"""
 
 
 class PllLib:
@@ -444,6 +467,24 @@ class PllLib:
             L.pllhip_node_ancestral_finish.argtypes = [C.c_void_p]
             L.pllhip_node_ancestral_last_times.restype = None
             L.pllhip_node_ancestral_last_times.argtypes = [c_double_p, C.POINTER(C.c_ulonglong)]
+        if hasattr(L, "pllhip_sitelh_rell"):
+            L.pllhip_sitelh_create.restype = C.c_void_p
+            L.pllhip_sitelh_create.argtypes = [C.c_uint, c_uint_p]
+            L.pllhip_sitelh_destroy.restype = None
+            L.pllhip_sitelh_destroy.argtypes = [C.c_void_p]
+            L.pllhip_sitelh_count.restype = C.c_uint
+            L.pllhip_sitelh_count.argtypes = [C.c_void_p]
+            L.pllhip_sitelh_get.argtypes = [C.c_void_p, C.c_uint, c_double_p]
+            L.pllhip_sitelh_add.argtypes = [C.c_void_p, c_double_p]
+            L.pllhip_sitelh_add_edge.argtypes = [C.c_void_p, C.c_uint, C.c_uint, pp, C.c_uint, C.c_int, C.c_uint,
+                                                 C.c_int, C.c_uint, c_uint_p, c_double_p]
+            L.pllhip_sitelh_rell.restype = C.POINTER(RellResult)
+            L.pllhip_sitelh_rell.argtypes = [C.c_void_p, C.POINTER(RellParams)]
+            L.pllhip_rell_destroy.restype = None
+            L.pllhip_rell_destroy.argtypes = [C.POINTER(RellResult)]
+            L.pllhip_rell_last_times.restype = None
+            L.pllhip_rell_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
+            L.pllhip_bootstrap_weights.argtypes = [c_uint_p, C.c_uint, C.c_ulonglong, C.c_uint, C.c_uint, c_uint_p]
         if hasattr(L, "pllhip_msa_compute_stats"):
             L.pllhip_empirical_frequencies.restype = c_double_p
             L.pllhip_empirical_frequencies.argtypes = [pp]
@@ -1330,6 +1371,82 @@ class TreeSet:
         probes, compares = C.c_ulonglong(0), C.c_ulonglong(0)
         self.L.pllhip_treeset_last_counts(C.byref(probes), C.byref(compares))
         return probes.value, compares.value
+
+
+class SiteLikelihoods:
+    """pllhip_sitelh_* (include/pllhip.h): per-pattern log-likelihoods of several trees on the device.  A failed call
+    returns None / False with lib.errno set."""
+
+    def __init__(self, lib, patterns, weights=None):
+        self.lib, self.L, self.S = lib, lib.lib, patterns
+        w = None if weights is None else _u32(weights)
+        self.h = self.L.pllhip_sitelh_create(patterns, None if w is None else w.ctypes.data_as(c_uint_p))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.h:
+            self.L.pllhip_sitelh_destroy(self.h)
+            self.h = None
+
+    @property
+    def count(self):
+        return self.L.pllhip_sitelh_count(self.h)
+
+    def add(self, row):
+        """appends a host row; the tree index, or None"""
+        r = _f64(row)
+        assert r.shape == (self.S,)
+        k = self.L.pllhip_sitelh_add(self.h, r.ctypes.data_as(c_double_p))
+        return None if k < 0 else k
+
+    def add_edge(self, tree, offset, inst, pc, psc, cc, csc, matrix):
+        """the edge log-likelihood of Instance `inst` with its per-pattern values left in row `tree` at `offset`;
+        the log-likelihood, or None"""
+        v = C.c_double(0.0)
+        ok = self.L.pllhip_sitelh_add_edge(self.h, tree, offset, inst.p, pc, psc, cc, csc, matrix, inst.params_p,
+                                           C.byref(v))
+        return v.value if ok else None
+
+    def get(self, tree):
+        out = np.zeros(self.S)
+        return out if self.L.pllhip_sitelh_get(self.h, tree, out.ctypes.data_as(c_double_p)) else None
+
+    def rell(self, replicates, seed, flags=0, batch=0):
+        """pllhip_sitelh_rell as a Rell, or None"""
+        params = RellParams(replicates, seed, flags, batch)
+        rp = self.L.pllhip_sitelh_rell(self.h, C.byref(params))
+        if not rp:
+            return None
+        try:
+            r, out = rp.contents, Rell()
+            T, B = r.trees, r.replicates
+            out.trees, out.replicates, out.best, out.batch = T, B, r.best, r.batch
+            out.lnl = np.ctypeslib.as_array(r.lnl, (T,)).copy()
+            out.bp_count = np.ctypeslib.as_array(r.bp_count, (T,)).copy()
+            out.kh_count = np.ctypeslib.as_array(r.kh_count, (T,)).copy()
+            out.sh_count = np.ctypeslib.as_array(r.sh_count, (T,)).copy()
+            out.elw = np.ctypeslib.as_array(r.elw, (T,)).copy()
+            out.R = np.ctypeslib.as_array(r.replicate_lnl, (B, T)).copy() if r.replicate_lnl else None
+        finally:
+            self.L.pllhip_rell_destroy(rp)
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self.L.pllhip_rell_last_times(C.byref(a), C.byref(b), C.byref(c))
+        out.times = (a.value, b.value, c.value)
+        return out
+
+
+def bootstrap_weights(lib, weights, patterns, seed, first, count):
+    """pllhip_bootstrap_weights: [count][patterns] uint32, or None"""
+    w = None if weights is None else _u32(weights)
+    out = np.zeros((count, patterns), np.uint32)
+    ok = lib.lib.pllhip_bootstrap_weights(None if w is None else w.ctypes.data_as(c_uint_p), patterns, seed, first,
+                                          count, out.ctypes.data_as(c_uint_p))
+    return out if ok else None
 
 
 def state_charmap(nstates):
