@@ -175,8 +175,8 @@ PLL_EXPORT int pllhip_profile_read(pll_partition_t * partition, pllhip_profile_t
    device memory; all zero when the partition has none).  An operation chain hands its vector on in registers; the
    vector next to it comes back from memory -- except a lone cherry (a tip x tip operation), which the 20-state
    family builds in registers inside the chain that reads it, from the two tip tables ("folded"; per-site scalers,
-   coded tips, no site repeats; PLLHIP_FOLD=0 in the environment plans without folds).  A folded cherry's vector and
-   scaler counts are stored like any other's. */
+   coded tips, no site repeats; PLLHIP_FOLD=0 in the environment plans without folds).  A folded cherry's scaler
+   counts are stored like any other's; its vector is stored when somebody needs it (pllhip_deferred_stats). */
 typedef struct pllhip_schedule_stats
 {
   unsigned int chains;                 /* operation chains of the schedule */
@@ -216,6 +216,24 @@ typedef struct pllhip_transient_stats
 PLL_EXPORT int pllhip_set_transient(pll_partition_t * partition, int enable);
 PLL_EXPORT int pllhip_discard_transient(pll_partition_t * partition);
 PLL_EXPORT int pllhip_transient_stats(const pll_partition_t * partition, pllhip_transient_stats_t * out);
+
+/* Deferred stores.  A storing traversal of the 20-state family (the mode above being off; partitions of 122 880 sites
+   and more, PLLHIP_DEFER=1 in the environment: of any size) leaves out the stores of vectors that none of its
+   operations reads from memory and that coded tips alone recompute: folded cherries, and the one or two operations of a
+   cherry / cherry x tip subtree that the operation above reads through its class table.  Their scaler counts are
+   stored as always.  Such a vector is kept as its operation, exactly like a vector the mode above left out, and is
+   stored for its first reader or before one of its inputs changes -- by a launch of its own, which costs two to three
+   times what leaving the store out of the traversal saved.  A caller observes nothing but
+   timing: whatever it reads is bit-identical to PLLHIP_DEFER=0 in the environment (which plans every store).
+   pllhip_discard_transient leaves these vectors alone (the caller never asked for them to be left out);
+   pllhip_transient_stats does not count them. */
+typedef struct pllhip_deferred_stats
+{
+  unsigned long long deferred;         /* stores that storing traversals left out */
+  unsigned long long stored_later;     /* ... that were made up for: a reader needed the vector, or an input changed */
+  unsigned long long given_up;         /* ... that never happened: the vector was overwritten before anybody asked */
+} pllhip_deferred_stats_t;
+PLL_EXPORT int pllhip_deferred_stats(const pll_partition_t * partition, pllhip_deferred_stats_t * out);
 
 /* kernel family actually used for pll_update_partials on this partition:
    "s4-valu", "s20-mfma", "generic" ... (for tests that must prove the

@@ -100,7 +100,8 @@ struct PlanOp
   unsigned carried;      // 0 = both children from memory, 1 / 2 = child 1 / 2 is the previous op's parent
   unsigned slot1, slot2; // 20 states: LDS offsets (doubles) of the two children's tables
   unsigned flags;        // bit 0: the parent vector is not stored (an evaluate-only traversal hands it to the next
-                         // operation of its chain in registers; pllhip_set_transient)
+                         // operation of its chain in registers, pllhip_set_transient; or a storing traversal defers the
+                         // store of a tip-only subtree that none of its operations reads from memory, plan_defers)
                          // bit 1 / 2: the rows of wide tip 1 / 2 are staged in LDS
                          // bit 3: a cherry that the NEXT entry builds in registers instead of reading its vector
                          // (20 states; slot1 / slot2 = its tip tables, the scaling decisions per code pair behind them)
@@ -142,6 +143,7 @@ struct DevicePlan                                 // the schedule resident on th
   unsigned nfolds = 0;                            // lone cherries folded into the chains that read them (PlanOp::flags bit 3)
   unsigned inner_reads = 0;                       // inner vectors that the chains read from memory
   unsigned nlookups = 0;                          // children read through their class tables (PlanOp::flags bit 5)
+  unsigned ndeferred = 0;                         // stores a storing traversal leaves out (plan_defers; PlanOp::flags bit 0)
   double algo_bytes = 0.0, algo_flops = 0.0;      // algorithmic traffic / work of the traversal
   double min_bytes = 0.0;                         // traffic without the child vectors handed over in registers
   // launches of the schedule: one for a whole traversal, or one per round of chains (chains
@@ -174,6 +176,9 @@ struct BatchPlan
 };
 
 enum class KernelFamily { Generic, S4, S16, S20, S61 };
+
+// why a vector exists as its operation only (Engine::transient_live)
+constexpr char TRANSIENT_MODE = 1, TRANSIENT_DEFERRED = 2;
 
 struct Engine
 {
@@ -248,10 +253,11 @@ struct Engine
   bool transient_mode = false;
   bool transient_busy = false;                  // a materialisation is running (its lists are exempt from the checks)
   unsigned ntransient = 0;                      // vectors that exist as their operation only
-  std::vector<char> transient_live;             // [nodes]
+  std::vector<char> transient_live;             // [nodes] 1: the mode left the vector out, 2: a deferred store (plan_defers)
   std::vector<pll_operation_t> transient_op;    // [nodes] what recomputes the vector
   std::vector<unsigned> transient_mat_users;    // [nmat] live operations that read the matrix
   pllhip_transient_stats_t transient_stats = {};
+  pllhip_deferred_stats_t deferred_stats = {};  // the same records, for the stores that storing traversals defer
   size_t sc_len = 0;                  // entries per scale buffer on the device
   KernelFamily family = KernelFamily::Generic;
   unsigned cu_count = 256;

@@ -545,15 +545,17 @@ __device__ inline const unsigned * s20_wide_codes(const double * clv, const uint
 // on that side: products commute).  fentry is the cherry's own entry of the schedule (its tip codes, the LDS offsets
 // from `lds` of its two tip tables with the scaling decisions per pair of codes behind them: s20_fold_bits; bit 0 of
 // its flags counts with ftrans).  The cherry's vector and scaler buffer are the consumer's clv2 / scaler2.  Vector and
-// counts are what the cherry's own operation would have stored (the same product, the same factor), and they are
-// stored -- only never read back.  (Only what is needed of the entry is fetched, and only in front of a fold: both entries in scalar
+// counts are what the cherry's own operation would have stored (the same product, the same factor); the counts are
+// stored, the vector unless bit 0 of the cherry's entry says that nobody reads it (an evaluate-only traversal, or a
+// store that the planner deferred: plan_defers).  (Only what is needed of the entry is fetched, and only in front of a fold: both entries in scalar
 // registers at once spilled over a hundred of them.)
 // LOOK: child 2 may be a small subtree read through its class table (`look`; PlanOp::flags bit 5, plan_lookups): a
 // cherry or a cherry x tip, whose vector depends on the two or three tip codes below it alone.  The entry carries those
 // codes' arrays in clv2 / pmat2 / pfrag2 (pfrag2 null: a cherry), the rows P . vector(class) of all U^2 / U^3 classes in
 // lut2 ([rate][child2_index classes][20], k_pair_lut) and the scaler counts per class in scaler2: the wide-tip gather of
 // kernels_repeats.hpp, with the class code formed here from the tip codes.  No vector is read, no product taken for
-// that child; the child's own operation has stored vector and counts as always.  The two class codes share the
+// that child; the child's own operation has stored its counts as always (and its vector, unless the planner deferred
+// that store: `store` of that operation, PlanOp::flags bit 0).  The two class codes share the
 // register that holds a folded cherry's tip codes (an operation has one or the other).
 template <unsigned RT, bool RS, bool WIDE, bool FOLD = false, bool LOOK = false>
 __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2 X[RT][5],
@@ -846,7 +848,8 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_chain_s20(ChainBatc
 // workgroup's own barrier around the re-staging of the LDS tables.
 // grid = gx, block = 512, dynamic LDS = the largest chain area of the schedule.
 // TRANS: an evaluate-only traversal -- operations whose PlanOp::flags bit 0 is set hand their result on in registers only
-// (a compile-time switch: as a run-time flag in front of every store it cost the storing traversal 3.5 %)
+// (a compile-time switch: as a run-time flag in front of every store it cost the storing traversal 3.5 %; the FOLD
+// instantiations read the flag whatever TRANS says -- their storing schedules defer stores, plan_defers)
 // FOLD: the schedule holds folded cherries -- PlanOp::flags bit 3: the entry is a cherry whose block the NEXT entry
 // builds in registers (bit 4 there: its child 2 is that cherry).  Its tip tables are staged like any other entry's, the
 // scaling decisions per pair of codes go behind them (PlanChain::flags bit 1: the chain has such entries), and the
@@ -919,9 +922,12 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_traverse_s20(PlanVi
           {
             if (po.flags & 8u) continue;                // built by the next entry
             // (tip tables are staged wherever cherries are folded: s20_fold_lds)
+            // (bit 0 counts here without TRANS as well: a storing schedule with folds defers the stores of folded
+            // cherries and of the chains of looked-up children -- plan_defers; the flag of a folded cherry comes with
+            // the tail of its entry that the consumer fetches anyway)
             s20_chain_op<RT, RS, WIDE, FOLD, LOOK>(po.d, po.carried, X, lds + po.slot1, lds + po.slot2, lut_codes, lut_used, true,
-                                                   blk, lane, nt_ld, nt_st, xe, xo, TRANS ? !(po.flags & 1u) : true, 0u,
-                                                   (po.flags & 16u) != 0, plan_ops_ + ch.first + i - 1, lds, TRANS,
+                                                   blk, lane, nt_ld, nt_st, xe, xo, !(po.flags & 1u), 0u,
+                                                   (po.flags & 16u) != 0, plan_ops_ + ch.first + i - 1, lds, true,
                                                    LOOK && (po.flags & 32u) != 0);
             continue;
           }

@@ -1090,6 +1090,9 @@ struct ChainFamily
   // the family reads small light subtrees through class tables (plan_lookups): the most classes of such a child
   // (null: the family has no such reads; 0: none at this partition's shape)
   unsigned (*look_classes)(const Engine * e, unsigned lut_used);
+  // the family's storing schedules leave out the stores nobody reads (plan_defers; null: never; 0: not at this
+  // partition's shape; 2: those of folded cherries alone)
+  unsigned (*defer)(const Engine * e);
   const double * (*pair_pfrag)(const Engine * e, unsigned matrix);        // PairLutJob::pfrag of a branch
   bool (*fills_chip)(const Engine * e);                 // the site blocks alone keep the chip busy: one launch
   unsigned (*units)(const Engine * e);                  // workgroups a member of a batch can use side by side
@@ -1123,13 +1126,28 @@ static unsigned s20_look_classes(const Engine * e, unsigned lut_used)
   return (unsigned)std::min<unsigned long long>(limit, S20_LOOK_MAX);
 }
 
+// 20 states: whether a storing schedule leaves out the stores nobody reads (plan_defers): 0 = no, 1 = those of folded
+// cherries and of looked-up children, 2 = those of folded cherries alone.  A store that is made up for later costs a
+// launch of its own on top of its bytes, which a small partition never saved in the traversal: a floor of
+// S20_DEFER_MIN_BLOCKS site blocks, just under the smallest partition measured to gain (C3's 125 k-site slice, 3 907
+// blocks: 4.07 -> 3.96 ms per evaluation).  PLLHIP_DEFER=1 defers at any size (the tests do), PLLHIP_DEFER=0 at none
+// (every vector is stored by the traversal that computes it: the reference of the A/B runs and of the bitwise tests),
+// PLLHIP_DEFER=2 defers the folded half alone, at any size (the A/B runs that weigh the two halves separately).
+constexpr unsigned S20_DEFER_MIN_BLOCKS = 3840;         // 122 880 sites
+static unsigned s20_defer(const Engine * e)
+{
+  static const int use_defer = getenv("PLLHIP_DEFER") ? atoi(getenv("PLLHIP_DEFER")) : -1;
+  if (!use_defer || (use_defer < 0 && e->nblk < S20_DEFER_MIN_BLOCKS)) return 0u;
+  return use_defer == 2 ? 2u : 1u;
+}
+
 static const ChainFamily CHAINS_S4 = {
   .supported = chains_supported_s4, .chain_max = S4_CHAIN_MAX, .chain_lds = ~0u, .lds_is_length = true,
   .extent = [](const Engine * e) { return e->N; },
   .child_lds = [](const Engine *, bool, unsigned) { return 0u; },
   .wide_lds = [](const Engine *, unsigned) { return 0u; },
   .tables_in_lds = [](const Engine *, unsigned) { return false; },
-  .fold_lds = nullptr, .look_classes = nullptr,
+  .fold_lds = nullptr, .look_classes = nullptr, .defer = nullptr,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pmat + (size_t)m * e->R * 16; },
   .fills_chip = [](const Engine * e) { return (e->N + 63) / 64 >= 48u * e->cu_count; },
   .units = [](const Engine * e) { return (e->N + 255u) / 256u; }, .batch_wgs = 3,
@@ -1151,7 +1169,7 @@ static const ChainFamily CHAINS_S16 = {
   .child_lds = [](const Engine * e, bool tip, unsigned) { return s16_chain_slot(e, tip); },
   .wide_lds = [](const Engine * e, unsigned rows) { return e->R * rows * e->S <= S16_LUT_LDS ? ((e->R * rows * e->S + 7u) & ~7u) : 0u; },
   .tables_in_lds = [](const Engine * e, unsigned) { return s16_chain_lut_lds(e); },
-  .fold_lds = nullptr, .look_classes = nullptr,
+  .fold_lds = nullptr, .look_classes = nullptr, .defer = nullptr,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pmat + (size_t)m * e->R * e->S * e->Sp; },
   .fills_chip = [](const Engine * e) { return e->nblk >= 12u * e->cu_count && e->nblk < 48u * e->cu_count && e->S > 8; },
   .units = [](const Engine * e) { return (e->nblk + 7u) / 8u; }, .batch_wgs = 1,
@@ -1187,7 +1205,7 @@ static const ChainFamily CHAINS_S20 = {
   .child_lds = s20_chain_slot,
   .wide_lds = [](const Engine * e, unsigned rows) { return e->R * rows * S20_LUT_RS <= 2560u ? ((e->R * rows * S20_LUT_RS + 7u) & ~7u) : 0u; },
   .tables_in_lds = s20_chain_lut_lds,
-  .fold_lds = s20_fold_lds, .look_classes = s20_look_classes,
+  .fold_lds = s20_fold_lds, .look_classes = s20_look_classes, .defer = s20_defer,
   .pair_pfrag = [](const Engine * e, unsigned m) -> const double * { return e->d_pfrag + (size_t)m * e->R * 400; },
   .fills_chip = [](const Engine * e) { return e->nblk >= 6u * e->cu_count && e->nblk < 24u * e->cu_count; },
   .units = [](const Engine * e) { return (e->nblk + 7u) / 8u; }, .batch_wgs = 1,
@@ -1366,6 +1384,15 @@ static unsigned fold_table_lds(const Engine * e, const ChainFamily & f, unsigned
   return use_fold && f.fold_lds && e->coded_tips ? f.fold_lds(e, lut_used) : 0u;
 }
 
+// whether a storing schedule with folds leaves out the stores nobody reads (plan_defers; the family says which and
+// from what size on: ChainFamily::defer)
+static unsigned defer_stores(const Engine * e, const ChainFamily & f, bool transient)
+{
+  // (an evaluate-only traversal leaves these vectors out already; the lists that store vectors later store them)
+  if (!f.defer || transient || e->transient_mode || e->transient_busy || e->site_repeats) return 0u;
+  return f.defer(e);
+}
+
 // LDS doubles of the table of child `idx` in a chain kernel; wide: the child is read as a wide tip
 static unsigned child_table_lds(const Engine * e, const ChainFamily & f, unsigned idx, unsigned lut_used, bool wide)
 {
@@ -1396,6 +1423,8 @@ struct ChainPlan
   };
   std::vector<Lookup> lookups;
   std::vector<unsigned char> looked;
+  // per op: the traversal does not store the parent vector (plan_defers; empty: every vector is stored)
+  std::vector<unsigned char> deferred;
   int rounds = 0;
 };
 
@@ -1683,6 +1712,35 @@ static void plan_lookups(const Engine * e, const pll_operation_t * ops, unsigned
   }
 }
 
+// Deferred stores.  Folds and class tables took the READS of small tip-only subtrees out of the traversal; their
+// vectors were still written, 8 * S * R bytes per site each, although no operation of the list reads them from memory:
+//   a folded cherry             -- its consumer builds the block in registers;
+//   a looked-up child           -- its consumer gathers rows of the class table; the child's own chain (the cherry, or
+//                                  the cherry handed over in registers to the cherry x tip operation) feeds nobody else.
+// Such an operation is marked "parent vector not stored" (PlanOp::flags bit 0).  Coded tips and P-matrices alone
+// recompute it, so the engine keeps it as its operation (transient_mark, as for an evaluate-only traversal) and stores it
+// for the first reader or before an input changes.  Scaler counts are written as always.  Nothing else is marked: the
+// cherry below a looked-up cherry x tip only where that operation takes it over in registers.
+// `plan`: after plan_folds and plan_lookups.
+// folds_only: the looked-up children keep their stores (defer_stores)
+static void plan_defers(const pll_operation_t * ops, unsigned count, bool folds_only, ChainPlan & plan)
+{
+  plan.deferred.clear();
+  if (plan.folded.empty() && (folds_only || plan.lookups.empty())) return;
+  plan.deferred.assign(count, 0);
+  for (unsigned k = 0; k < count && !plan.folded.empty(); ++k)
+    if (plan.folded[k]) plan.deferred[k] = 1;
+  if (folds_only) return;
+  for (const ChainPlan::Lookup & l : plan.lookups)
+  {
+    plan.deferred[l.top] = 1;
+    if (l.cherry < 0) continue;
+    const pll_operation_t & t = ops[l.top];
+    const unsigned side = t.child1_clv_index == ops[l.cherry].parent_clv_index ? 1u : 2u;
+    if (plan.carried[l.top] == side) plan.deferred[l.cherry] = 1;
+  }
+}
+
 // make DevicePlan::bytes resident on the device (stream-ordered; nothing is copied when the
 // device already holds exactly these bytes) and point `view` at it
 static int upload_plan(DevicePlan & dp, hipStream_t stream, PlanView & view)
@@ -1942,22 +2000,27 @@ static void transient_drop(Engine * e, unsigned node, bool dead)
 {
   if (!e->ntransient || !e->transient_live[node]) return;
   const pll_operation_t & o = e->transient_op[node];
+  const bool deferred = e->transient_live[node] == TRANSIENT_DEFERRED;
   e->transient_live[node] = 0;
   --e->transient_mat_users[o.child1_matrix_index];
   --e->transient_mat_users[o.child2_matrix_index];
   --e->ntransient;
-  if (dead) e->transient_stats.discarded++;
+  if (dead && deferred) e->deferred_stats.given_up++;
+  else if (dead) e->transient_stats.discarded++;
 }
 
-static void transient_mark(Engine * e, const pll_operation_t & o)
+// kind: TRANSIENT_MODE = an evaluate-only traversal left the vector out, TRANSIENT_DEFERRED = a storing traversal
+// deferred its store (plan_defers); the two are counted apart (pllhip_transient_stats / pllhip_deferred_stats)
+static void transient_mark(Engine * e, const pll_operation_t & o, char kind)
 {
   transient_drop(e, o.parent_clv_index, true);
-  e->transient_live[o.parent_clv_index] = 1;
+  e->transient_live[o.parent_clv_index] = kind;
   e->transient_op[o.parent_clv_index] = o;
   ++e->transient_mat_users[o.child1_matrix_index];
   ++e->transient_mat_users[o.child2_matrix_index];
   ++e->ntransient;
-  e->transient_stats.skipped++;
+  if (kind == TRANSIENT_DEFERRED) e->deferred_stats.deferred++;
+  else e->transient_stats.skipped++;
 }
 
 // store the vectors of `want` that exist as their operation only: the operations that made them run again (and,
@@ -1967,6 +2030,7 @@ static int transient_materialize(Engine * e, const std::vector<unsigned> & want)
 {
   if (!e->ntransient) return PLL_SUCCESS;
   std::vector<pll_operation_t> list;
+  unsigned long long ndeferred = 0;                   // of them: deferred stores
   std::vector<char> seen(e->nodes, 0);
   std::vector<std::pair<unsigned, unsigned>> stack;   // (node, children looked at)
   for (unsigned w : want)
@@ -1983,7 +2047,12 @@ static int transient_materialize(Engine * e, const std::vector<unsigned> & want)
         const unsigned c = stack.back().second++ ? o.child2_clv_index : o.child1_clv_index;
         if (e->transient_live[c] && !seen[c]) { seen[c] = 1; stack.emplace_back(c, 0u); }
       }
-      else { list.push_back(o); stack.pop_back(); }
+      else
+      {
+        if (e->transient_live[node] == TRANSIENT_DEFERRED) ++ndeferred;
+        list.push_back(o);
+        stack.pop_back();
+      }
     }
   }
   if (list.empty()) return PLL_SUCCESS;
@@ -1993,7 +2062,11 @@ static int transient_materialize(Engine * e, const std::vector<unsigned> & want)
   const int rc = update_partials_impl(e->owner, list.data(), (unsigned)list.size());
   e->transient_mode = mode;
   e->transient_busy = false;
-  if (rc) e->transient_stats.materialized += list.size();
+  if (rc)
+  {
+    e->transient_stats.materialized += list.size() - ndeferred;
+    e->deferred_stats.stored_later += ndeferred;
+  }
   return rc;
 }
 
@@ -2038,8 +2111,8 @@ static int transient_before_list(Engine * e, const pll_operation_t * ops, unsign
   return PLL_SUCCESS;
 }
 
-// after the launches of a resident schedule: the operations whose vectors stayed in registers
-static void transient_after_list(Engine * e, const pll_operation_t * ops, unsigned count, const DevicePlan & dp)
+// after the launches of a resident schedule: the operations whose vectors stayed in registers (kind: transient_mark)
+static void transient_after_list(Engine * e, const pll_operation_t * ops, unsigned count, const DevicePlan & dp, char kind)
 {
   const PlanOp * pops = reinterpret_cast<const PlanOp *>(dp.bytes.data());
   std::vector<int> by_parent;
@@ -2052,7 +2125,7 @@ static void transient_after_list(Engine * e, const pll_operation_t * ops, unsign
       for (unsigned k = 0; k < count; ++k) by_parent[ops[k].parent_clv_index] = (int)k;
     }
     const int k = by_parent[pops[i].d.parent_index];
-    if (k >= 0) transient_mark(e, ops[k]);
+    if (k >= 0) transient_mark(e, ops[k], kind);
   }
 }
 
@@ -2119,6 +2192,7 @@ struct ScheduleBuild                             // the schedule being built (De
   unsigned nops = 0, lds_max = 0;
   unsigned nfolds = 0, inner_reads = 0;          // folded cherries; inner vectors that the chains read from memory
   unsigned nlookups = 0;                         // children read through their class tables
+  unsigned ndeferred = 0;                        // stores left out of a storing traversal
 };
 
 // site repeats: children that are cherries kept per class are read as wide tips (kernels_repeats.hpp);
@@ -2156,13 +2230,13 @@ static bool mark_wide_tips(Engine * e, const pll_operation_t * ops, unsigned cou
 // in use, the mode, the wide tips, and which operations are kept per class (the same list can meet other class nodes
 // of earlier calls)
 static std::vector<unsigned char> schedule_key(const ScheduleRequest & rq, unsigned lut_used, const std::vector<unsigned char> & wide,
-                                               bool fold, unsigned look_classes)
+                                               bool fold, unsigned look_classes, unsigned defer)
 {
   std::vector<unsigned char> tracked(rq.rp ? rq.count : 0, 0);
   if (rq.rp) for (unsigned k : rq.rp->cherry_ops) tracked[k] = 1;
   const size_t list_bytes = (size_t)rq.count * sizeof(pll_operation_t);
   std::vector<unsigned char> key(4 * sizeof(unsigned) + list_bytes + wide.size() + tracked.size());
-  const unsigned mode_key = rq.mode | (rq.transient ? 0x100u : 0u) | (fold ? 0x200u : 0u);
+  const unsigned mode_key = rq.mode | (rq.transient ? 0x100u : 0u) | (fold ? 0x200u : 0u) | (defer << 10);
   memcpy(key.data(), &rq.count, sizeof(unsigned));
   memcpy(key.data() + sizeof(unsigned), &lut_used, sizeof(unsigned));
   memcpy(key.data() + 2 * sizeof(unsigned), &mode_key, sizeof(unsigned));
@@ -2357,6 +2431,8 @@ static void emit_chains(const Engine * e, const ChainFamily & f, const pll_opera
       fill_desc(e, o, po.d, dp.algo_bytes, dp.algo_flops);
       // an evaluate-only traversal: the vectors inside a chain are handed on in registers only
       po.flags = (rq.transient && i + 1 < ch.size()) ? 1u : 0u;
+      // a storing traversal: the stores nobody reads are left for later (plan_defers)
+      if (!plan.deferred.empty() && plan.deferred[ch[i]]) { po.flags |= 1u; ++sb.ndeferred; }
       if (folded)
       {
         // a folded cherry: bit 3 here, bit 4 on its consumer (the next entry); its two tip tables and, behind
@@ -2655,13 +2731,16 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   const unsigned fold_lds = rq.fold && !rq.rp && !nwide ? fold_table_lds(e, f, lut_used) : 0u;
   // (children read through class tables: where folds are planned, in storing traversals)
   const unsigned look_classes = fold_lds && f.look_classes && !rq.transient && !e->transient_mode ? f.look_classes(e, lut_used) : 0u;
-  std::vector<unsigned char> key = schedule_key(rq, lut_used, wide, fold_lds != 0, look_classes);
+  // (deferred stores: where folds are planned, in storing traversals)
+  const unsigned defer = fold_lds ? defer_stores(e, f, rq.transient) : 0u;
+  std::vector<unsigned char> key = schedule_key(rq, lut_used, wide, fold_lds != 0, look_classes, defer);
   if (!dp.key.empty() && dp.key == key) return true;
   if ((nwide || rq.rp) && !reserve_pair_tables(e, rq, ops, count, wide)) return false;
   ChainPlan plan;
   if (!plan_chains(e, &f, ops, count, f.chain_max, f.chain_lds, lut_used, plan, &wide)) return false;
   plan_folds(e, f, ops, count, f.chain_max, f.chain_lds, lut_used, fold_lds, plan);
   plan_lookups(e, ops, count, lut_used, look_classes, plan);
+  if (defer) plan_defers(ops, count, defer == 2, plan);
   if (!reserve_lookup_tables(e, plan, lut_used)) return false;
   ScheduleBuild sb;
   sb.pops.resize(count);
@@ -2678,6 +2757,7 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   dp.nfolds = sb.nfolds;
   dp.inner_reads = sb.inner_reads;
   dp.nlookups = sb.nlookups;
+  dp.ndeferred = sb.ndeferred;
   dp.max_extent = f.extent(e);
   dp.generation = ++plan_generation;
   dp.key.swap(key);
@@ -2939,7 +3019,8 @@ static int run_resident(Engine * e, const ChainFamily & f, const pll_operation_t
     }
   }
   if (!launch_resident(e, f, dp, view, 0, !e->cherries.empty(), transient)) return PLL_FAILURE;
-  if (transient) transient_after_list(e, ops, count, dp);
+  // (a storing schedule marks only the stores it deferred: plan_defers)
+  if (transient || dp.ndeferred) transient_after_list(e, ops, count, dp, transient ? TRANSIENT_MODE : TRANSIENT_DEFERRED);
   count_list(e, count);
   return PLL_SUCCESS;
 }
@@ -3418,7 +3499,7 @@ static int update_partials_group(const std::vector<pll_partition_t *> & g, const
   for (pll_partition_t * p : g)
   {
     Engine * e = engine_of(p);
-    if (e->transient_mode && !e->site_repeats) transient_after_list(e, ops, count, e->plan);
+    if (e->transient_mode && !e->site_repeats) transient_after_list(e, ops, count, e->plan, TRANSIENT_MODE);
     count_list(e, count);
   }
   return 1;
@@ -5043,13 +5124,21 @@ int pllhip_discard_transient(pll_partition_t * p)
 {
   Engine * e = engine_of(p);
   for (pll_partition_t * c : e->shards) (void)pllhip_discard_transient(c);
-  for (unsigned n = 0; n < e->nodes && e->ntransient; ++n) transient_drop(e, n, true);
+  // (a deferred store is not the caller's doing: it stays recomputable)
+  for (unsigned n = 0; n < e->nodes && e->ntransient; ++n)
+    if (e->transient_live[n] == TRANSIENT_MODE) transient_drop(e, n, true);
   return PLL_SUCCESS;
 }
 
 int pllhip_transient_stats(const pll_partition_t * p, pllhip_transient_stats_t * out)
 {
   *out = exec_engine(p)->transient_stats;
+  return PLL_SUCCESS;
+}
+
+int pllhip_deferred_stats(const pll_partition_t * p, pllhip_deferred_stats_t * out)
+{
+  *out = exec_engine(p)->deferred_stats;
   return PLL_SUCCESS;
 }
 

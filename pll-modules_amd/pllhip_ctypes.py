@@ -110,6 +110,10 @@ class TransientStats(C.Structure):
     _fields_ = [(n, C.c_ulonglong) for n in ("skipped", "materialized", "discarded")]
 
 
+class DeferredStats(C.Structure):
+    _fields_ = [(n, C.c_ulonglong) for n in ("deferred", "stored_later", "given_up")]
+
+
 class ScheduleStats(C.Structure):
     _fields_ = [(n, C.c_uint) for n in ("chains", "operations", "inner_reads", "folded_cherries", "lookup_children")]
 
@@ -185,7 +189,7 @@ pllhip_shard_count pllhip_results_create pllhip_results_destroy
 pllhip_results_edge_loglikelihood pllhip_results_derivatives pllhip_results_fetch
 pllhip_eval_attach_comm pllhip_update_partials_batch pllhip_results_poison pllhip_newton_branch pllhip_repeat_stats
 pllhip_set_transient pllhip_discard_transient pllhip_transient_stats pllhip_newton_branch_multi
-pllhip_schedule_stats
+pllhip_schedule_stats pllhip_deferred_stats
 pllhip_parsimony_tree_score pllhip_compress_last_times pllhip_compress_last_counts
 pllhip_empirical_frequencies pllhip_empirical_subst_rates pllhip_empirical_invariant_sites
 pllhip_msa_compute_stats pllhip_msa_destroy_stats pllhip_msa_stats_last_times
@@ -427,6 +431,7 @@ class PllLib:
             L.pllhip_discard_transient.argtypes = [pp]
             L.pllhip_transient_stats.argtypes = [pp, C.POINTER(TransientStats)]
             L.pllhip_schedule_stats.argtypes = [pp, C.POINTER(ScheduleStats)]
+            L.pllhip_deferred_stats.argtypes = [pp, C.POINTER(DeferredStats)]
             L.pllhip_comm_get_unique_id.argtypes = [C.c_char_p]
             L.pllhip_comm_create.restype = C.c_void_p
             L.pllhip_comm_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -973,6 +978,12 @@ class Instance:
     def schedule_stats(self):
         st = ScheduleStats()
         self.L.pllhip_schedule_stats(self.p, C.byref(st))
+        return st
+
+    # stores that storing traversals deferred (include/pllhip.h, pllhip_deferred_stats)
+    def deferred_stats(self):
+        st = DeferredStats()
+        self.L.pllhip_deferred_stats(self.p, C.byref(st))
         return st
 
 
