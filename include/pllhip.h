@@ -220,9 +220,13 @@ PLL_EXPORT int pllhip_transient_stats(const pll_partition_t * partition, pllhip_
 /* Deferred stores.  A storing traversal of the 20-state family (the mode above being off; partitions of 122 880 sites
    and more, PLLHIP_DEFER=1 in the environment: of any size) leaves out the stores of vectors that none of its
    operations reads from memory and that coded tips alone recompute: folded cherries, and the one or two operations of a
-   cherry / cherry x tip subtree that the operation above reads through its class table.  Their scaler counts are
-   stored as always.  Such a vector is kept as its operation, exactly like a vector the mode above left out, and is
-   stored for its first reader or before one of its inputs changes -- by a launch of its own, which costs two to three
+   cherry / cherry x tip subtree that the operation above reads through its class table; and, while the caller keeps
+   evaluating without reading such vectors (two such lists in a row of which none was stored later; PLLHIP_DEFER=3: always),
+   the tip-only run at the bottom of every operation chain -- the cherry a chain starts with and the "that vector x
+   coded tip" operations above it whose result the next operation takes in registers (PLLHIP_DEFER_DEPTH=D: the
+   first D operations of a run).  Their scaler counts are stored as always.  Such a vector is kept as its operation, exactly like a vector the mode above left out, and is
+   stored for its first reader or before one of its inputs changes -- by a launch of its own (the members of a run at
+   the bottom of a chain: by one launch for the run; PLLHIP_DEFER_GROUP=0: one per reader), which costs two to three
    times what leaving the store out of the traversal saved.  A caller observes nothing but
    timing: whatever it reads is bit-identical to PLLHIP_DEFER=0 in the environment (which plans every store).
    pllhip_discard_transient leaves these vectors alone (the caller never asked for them to be left out);

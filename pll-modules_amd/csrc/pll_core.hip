@@ -61,7 +61,7 @@ static int current_device()
 int flush_pmatrices(pll_partition_t * p);
 static int ensure_luts(pll_partition_t * p);
 static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops, unsigned count);
-static int transient_materialize(Engine * e, const std::vector<unsigned> & want);
+static int transient_materialize(Engine * e, const std::vector<unsigned> & want, const std::vector<char> * going = nullptr);
 static int transient_flush_all(Engine * e);
 static bool cherry_storage(Engine * e, unsigned node, unsigned nclasses);
 // tip lookup tables exist: PLL_ATTRIB_PATTERN_TIP, or the engine's own codes (Engine::shadow_codes)
@@ -348,6 +348,7 @@ Engine * engine_create(pll_partition_t * p)
   e->owner = p;
   e->transient_live.assign(e->nodes, 0);
   e->transient_op.assign(e->nodes, pll_operation_t());
+  e->transient_run_up.assign(e->nodes, -1);
   e->transient_mat_users.assign(e->nmat, 0);
   e->transient_mode = getenv("PLLHIP_TRANSIENT") && atoi(getenv("PLLHIP_TRANSIENT")) != 0;
 
@@ -1091,7 +1092,8 @@ struct ChainFamily
   // (null: the family has no such reads; 0: none at this partition's shape)
   unsigned (*look_classes)(const Engine * e, unsigned lut_used);
   // the family's storing schedules leave out the stores nobody reads (plan_defers; null: never; 0: not at this
-  // partition's shape; 2: those of folded cherries alone)
+  // partition's shape; bits 0 - 7: which -- 1, 2: those of folded cherries alone, 3: also the tip-only runs at the
+  // bottom of the chains --, bits 8 and up: the most operations of such a run, 0 = all)
   unsigned (*defer)(const Engine * e);
   const double * (*pair_pfrag)(const Engine * e, unsigned matrix);        // PairLutJob::pfrag of a branch
   bool (*fills_chip)(const Engine * e);                 // the site blocks alone keep the chip busy: one launch
@@ -1127,18 +1129,30 @@ static unsigned s20_look_classes(const Engine * e, unsigned lut_used)
 }
 
 // 20 states: whether a storing schedule leaves out the stores nobody reads (plan_defers): 0 = no, 1 = those of folded
-// cherries and of looked-up children, 2 = those of folded cherries alone.  A store that is made up for later costs a
-// launch of its own on top of its bytes, which a small partition never saved in the traversal: a floor of
-// S20_DEFER_MIN_BLOCKS site blocks, just under the smallest partition measured to gain (C3's 125 k-site slice, 3 907
-// blocks: 4.07 -> 3.96 ms per evaluation).  PLLHIP_DEFER=1 defers at any size (the tests do), PLLHIP_DEFER=0 at none
-// (every vector is stored by the traversal that computes it: the reference of the A/B runs and of the bitwise tests),
-// PLLHIP_DEFER=2 defers the folded half alone, at any size (the A/B runs that weigh the two halves separately).
+// cherries and of looked-up children, 2 = those of folded cherries alone, 3 = level 1 and the tip-only runs at the
+// bottom of the chains; bits 8 and up: the most operations of such a run that are left out (0: the whole run).  A store
+// that is made up for later costs a launch of its own on top of its bytes, which a small partition never saved in the
+// traversal: a floor of S20_DEFER_MIN_BLOCKS site blocks, just under the smallest partition measured to gain (C3's
+// 125 k-site slice, 3 907 blocks: 4.07 -> 3.96 ms per evaluation).  PLLHIP_DEFER=1 / 3 defers at any size (the tests
+// do), PLLHIP_DEFER=0 at none (every vector is stored by the traversal that computes it: the reference of the A/B runs
+// and of the bitwise tests), PLLHIP_DEFER=2 defers the folded half alone, at any size (the A/B runs that weigh the two
+// halves separately).  PLLHIP_DEFER_DEPTH=D caps the runs of level 3 at D operations (0: no cap).
+// Without PLLHIP_DEFER the level follows what the caller does with the vectors that were left out (DESIGN.md section
+// 22): level 3 gains 11 % on an evaluation that is followed by another evaluation, and costs an evaluation that is
+// followed by a pass over all branches more than it saved, at any depth.  So level 1 is planned until two lists in a row
+// that left stores out have come and gone without one deferred vector being stored later (Engine::defer_unread, run_resident), level 3 from
+// then on, and level 1 again as soon as a reader asks for a deferred vector.
 constexpr unsigned S20_DEFER_MIN_BLOCKS = 3840;         // 122 880 sites
+constexpr unsigned S20_DEFER_DEPTH = 0;                 // without PLLHIP_DEFER_DEPTH
 static unsigned s20_defer(const Engine * e)
 {
   static const int use_defer = getenv("PLLHIP_DEFER") ? atoi(getenv("PLLHIP_DEFER")) : -1;
+  static const int env_depth = getenv("PLLHIP_DEFER_DEPTH") ? atoi(getenv("PLLHIP_DEFER_DEPTH")) : -1;
   if (!use_defer || (use_defer < 0 && e->nblk < S20_DEFER_MIN_BLOCKS)) return 0u;
-  return use_defer == 2 ? 2u : 1u;
+  const bool unread = e->defer_unread && e->deferred_stats.stored_later == e->defer_stored_mark;
+  const unsigned level = use_defer < 0 ? (unread ? 3u : 1u) : use_defer == 2 ? 2u : use_defer >= 3 ? 3u : 1u;
+  const unsigned depth = env_depth < 0 ? S20_DEFER_DEPTH : (unsigned)std::min(env_depth, 1023);
+  return level == 3 ? level | depth << 8 : level;
 }
 
 static const ChainFamily CHAINS_S4 = {
@@ -1425,6 +1439,8 @@ struct ChainPlan
   std::vector<unsigned char> looked;
   // per op: the traversal does not store the parent vector (plan_defers; empty: every vector is stored)
   std::vector<unsigned char> deferred;
+  // per op: the operation above it in the same deferred chain-bottom run (-1: none; empty: no such runs)
+  std::vector<int> run_up;
   int rounds = 0;
 };
 
@@ -1719,14 +1735,24 @@ static void plan_lookups(const Engine * e, const pll_operation_t * ops, unsigned
 //                                  the cherry handed over in registers to the cherry x tip operation) feeds nobody else.
 // Such an operation is marked "parent vector not stored" (PlanOp::flags bit 0).  Coded tips and P-matrices alone
 // recompute it, so the engine keeps it as its operation (transient_mark, as for an evaluate-only traversal) and stores it
-// for the first reader or before an input changes.  Scaler counts are written as always.  Nothing else is marked: the
-// cherry below a looked-up cherry x tip only where that operation takes it over in registers.
+// for the first reader or before an input changes.  Scaler counts are written as always.  The cherry below a looked-up
+// cherry x tip is marked only where that operation takes it over in registers.
+//   a tip-only run at the bottom of a chain (level 3)
+//                               -- a chain that starts with a cherry of coded tips hands its vector to the next operation
+//                                  in registers; where that one is "handed-over child x coded tip" its result depends on
+//                                  tip codes alone again, and so on up the chain.  An operation of such a run whose vector
+//                                  the next operation of the chain takes in registers is marked, the first `depth` of a
+//                                  run at the most (0: all of them): never the last operation of a chain, never a vector
+//                                  that an operation reads from memory.  plan.run_up links the marked operations of a
+//                                  run bottom-up (transient_materialize stores a run in one list).
 // `plan`: after plan_folds and plan_lookups.
-// folds_only: the looked-up children keep their stores (defer_stores)
-static void plan_defers(const pll_operation_t * ops, unsigned count, bool folds_only, ChainPlan & plan)
+// level 2: the looked-up children keep their stores (defer_stores)
+static void plan_defers(const Engine * e, const pll_operation_t * ops, unsigned count, unsigned level, unsigned depth, ChainPlan & plan)
 {
   plan.deferred.clear();
-  if (plan.folded.empty() && (folds_only || plan.lookups.empty())) return;
+  plan.run_up.clear();
+  const bool folds_only = level == 2;
+  if ((level < 3 || count < 2) && plan.folded.empty() && (folds_only || plan.lookups.empty())) return;
   plan.deferred.assign(count, 0);
   for (unsigned k = 0; k < count && !plan.folded.empty(); ++k)
     if (plan.folded[k]) plan.deferred[k] = 1;
@@ -1738,6 +1764,51 @@ static void plan_defers(const pll_operation_t * ops, unsigned count, bool folds_
     const pll_operation_t & t = ops[l.top];
     const unsigned side = t.child1_clv_index == ops[l.cherry].parent_clv_index ? 1u : 2u;
     if (plan.carried[l.top] == side) plan.deferred[l.cherry] = 1;
+  }
+  if (level < 3 || count < 2) return;
+  std::vector<unsigned> readers(e->nodes, 0);
+  for (unsigned k = 0; k < count; ++k) { ++readers[ops[k].child1_clv_index]; ++readers[ops[k].child2_clv_index]; }
+  auto plain_tip = [&](unsigned idx, int scaler) { return coded_tip(e, idx) && scaler == PLL_SCALE_BUFFER_NONE; };
+  auto is_folded = [&](unsigned k) { return !plan.folded.empty() && plan.folded[k]; };
+  // the child of `o` that comes from operation `from` in registers (0: none)
+  auto taken_over = [&](unsigned o, unsigned from) -> unsigned
+  {
+    const unsigned side = plan.carried[o];
+    if (!side) return 0u;
+    return (side == 1 ? ops[o].child1_clv_index : ops[o].child2_clv_index) == ops[from].parent_clv_index ? side : 0u;
+  };
+  for (const std::vector<unsigned> & ch : plan.chains)
+  {
+    size_t i = 0;
+    while (i < ch.size() && is_folded(ch[i])) ++i;
+    if (i >= ch.size()) continue;
+    const pll_operation_t & c = ops[ch[i]];
+    if (!plain_tip(c.child1_clv_index, c.child1_scaler_index) || !plain_tip(c.child2_clv_index, c.child2_scaler_index)) continue;
+    int below = -1;                                  // the marked operation of the run under ch[i]
+    for (unsigned len = 1; i + 1 < ch.size() && (!depth || len <= depth); ++i, ++len)
+    {
+      const unsigned k = ch[i];
+      if (len > 1)
+      {
+        // handed-over child x coded tip
+        const unsigned side = taken_over(k, ch[i - 1]);
+        if (!side) break;
+        const pll_operation_t & o = ops[k];
+        if (!(side == 1 ? plain_tip(o.child2_clv_index, o.child2_scaler_index) : plain_tip(o.child1_clv_index, o.child1_scaler_index))) break;
+      }
+      // its vector goes up in registers and nowhere else (the next entry may be a cherry folded into the operation
+      // behind it: that operation is the one that takes the vector, and the run ends under it)
+      const size_t next = i + 1 + (is_folded(ch[i + 1]) ? 1 : 0);
+      if (next >= ch.size() || !taken_over(ch[next], k) || readers[ops[k].parent_clv_index] != 1) break;
+      plan.deferred[k] = 1;
+      if (below >= 0)
+      {
+        if (plan.run_up.empty()) plan.run_up.assign(count, -1);
+        plan.run_up[below] = (int)k;
+      }
+      below = (int)k;
+      if (next != i + 1) break;
+    }
   }
 }
 
@@ -1996,6 +2067,8 @@ static bool class_map(Engine * e, unsigned node, unsigned c1, unsigned c2, unsig
 // evaluate-only traversals (include/pllhip.h, pllhip_set_transient): host side
 // ---------------------------------------------------------------------------
 // the vector of `node` stops being "its operation only": it is being stored (dead = false) or replaced / given up
+static int transient_materialize_list(Engine * e, const std::vector<unsigned> & want);
+
 static void transient_drop(Engine * e, unsigned node, bool dead)
 {
   if (!e->ntransient || !e->transient_live[node]) return;
@@ -2016,6 +2089,7 @@ static void transient_mark(Engine * e, const pll_operation_t & o, char kind)
   transient_drop(e, o.parent_clv_index, true);
   e->transient_live[o.parent_clv_index] = kind;
   e->transient_op[o.parent_clv_index] = o;
+  e->transient_run_up[o.parent_clv_index] = -1;
   ++e->transient_mat_users[o.child1_matrix_index];
   ++e->transient_mat_users[o.child2_matrix_index];
   ++e->ntransient;
@@ -2025,10 +2099,38 @@ static void transient_mark(Engine * e, const pll_operation_t & o, char kind)
 
 // store the vectors of `want` that exist as their operation only: the operations that made them run again (and,
 // below them, the ones of the children that were not stored either), as an ordinary list -- the same kernels on the
-// same inputs, so what is stored is what the traversal would have stored
-static int transient_materialize(Engine * e, const std::vector<unsigned> & want)
+// same inputs, so what is stored is what the traversal would have stored.
+// A member of a deferred chain-bottom run (plan_defers, level 3) brings the members above it along: one list, one
+// chain, one launch for the run instead of a launch per member that re-reads what the one before just wrote
+// (PLLHIP_DEFER_GROUP=0: every reader stores what it reads and what lies below, as for every other vector).
+// going: [nodes] vectors that the caller is about to overwrite -- a run is not followed into them (null: none)
+static int transient_materialize(Engine * e, const std::vector<unsigned> & want, const std::vector<char> * going)
 {
   if (!e->ntransient) return PLL_SUCCESS;
+  static const int env_group = getenv("PLLHIP_DEFER_GROUP") ? atoi(getenv("PLLHIP_DEFER_GROUP")) : 1;
+  std::vector<unsigned> grouped;
+  if (env_group)
+  {
+    for (unsigned w : want)
+    {
+      if (w >= e->nodes || e->transient_live[w] != TRANSIENT_DEFERRED) { grouped.push_back(w); continue; }
+      // (the link holds while the vector above is still the deferred operation that takes this one as a child)
+      for (unsigned steps = 0; steps < e->nodes; ++steps)
+      {
+        const int up = e->transient_run_up[w];
+        if (up < 0 || e->transient_live[up] != TRANSIENT_DEFERRED || (going && (*going)[up])) break;
+        const pll_operation_t & o = e->transient_op[up];
+        if (o.child1_clv_index != w && o.child2_clv_index != w) break;
+        w = (unsigned)up;
+      }
+      grouped.push_back(w);
+    }
+  }
+  return transient_materialize_list(e, env_group ? grouped : want);
+}
+
+static int transient_materialize_list(Engine * e, const std::vector<unsigned> & want)
+{
   std::vector<pll_operation_t> list;
   unsigned long long ndeferred = 0;                   // of them: deferred stores
   std::vector<char> seen(e->nodes, 0);
@@ -2105,7 +2207,7 @@ static int transient_before_list(Engine * e, const pll_operation_t * ops, unsign
           (o.parent_scaler_index >= 0 && swritten[o.parent_scaler_index]))
         want.push_back(t);
     }
-    if (!want.empty() && !transient_materialize(e, want)) return PLL_FAILURE;
+    if (!want.empty() && !transient_materialize(e, want, &written)) return PLL_FAILURE;
   }
   for (unsigned k = 0; k < count && e->ntransient; ++k) transient_drop(e, ops[k].parent_clv_index, !e->transient_busy);
   return PLL_SUCCESS;
@@ -2127,6 +2229,11 @@ static void transient_after_list(Engine * e, const pll_operation_t * ops, unsign
     const int k = by_parent[pops[i].d.parent_index];
     if (k >= 0) transient_mark(e, ops[k], kind);
   }
+  // the deferred runs at the bottom of chains: which vector stands above which (transient_materialize)
+  if (kind == TRANSIENT_DEFERRED)
+    for (const std::pair<unsigned, unsigned> & r : dp.defer_runs)
+      if (e->transient_live[r.first] == TRANSIENT_DEFERRED && e->transient_live[r.second] == TRANSIENT_DEFERRED)
+        e->transient_run_up[r.first] = (int)r.second;
 }
 
 // resolve one operation to device pointers and add its algorithmic bytes
@@ -2740,7 +2847,7 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   if (!plan_chains(e, &f, ops, count, f.chain_max, f.chain_lds, lut_used, plan, &wide)) return false;
   plan_folds(e, f, ops, count, f.chain_max, f.chain_lds, lut_used, fold_lds, plan);
   plan_lookups(e, ops, count, lut_used, look_classes, plan);
-  if (defer) plan_defers(ops, count, defer == 2, plan);
+  if (defer) plan_defers(e, ops, count, defer & 255u, defer >> 8, plan);
   if (!reserve_lookup_tables(e, plan, lut_used)) return false;
   ScheduleBuild sb;
   sb.pops.resize(count);
@@ -2758,6 +2865,9 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   dp.inner_reads = sb.inner_reads;
   dp.nlookups = sb.nlookups;
   dp.ndeferred = sb.ndeferred;
+  dp.defer_runs.clear();
+  for (unsigned k = 0; k < count && !plan.run_up.empty(); ++k)
+    if (plan.run_up[k] >= 0) dp.defer_runs.emplace_back(ops[k].parent_clv_index, ops[plan.run_up[k]].parent_clv_index);
   dp.max_extent = f.extent(e);
   dp.generation = ++plan_generation;
   dp.key.swap(key);
@@ -2989,9 +3099,12 @@ static int select_class_ops(Engine * e, const pll_operation_t * ops, unsigned co
 static int launch_resident(Engine * e, const ChainFamily & f, const DevicePlan & dp, const PlanView & view, unsigned wgs,
                            bool wide, bool transient)
 {
+  // (a storing schedule that defers stores but has neither folds nor looked-up children -- a caterpillar, many partial
+  // lists -- runs the instantiation of evaluate-only traversals: the plain one does not read PlanOp::flags bit 0)
+  const bool unstored = transient || (dp.ndeferred && !dp.nfolds && !dp.nlookups);
   for (const DevicePlan::Launch & l : dp.launches)
     if (!counted_launch(e, l.bytes, l.flops, l.ops, l.min_bytes, [&]()
-        { return f.traverse(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, l.rows, wgs, wide, transient, dp.nfolds != 0, dp.nlookups != 0); }))
+        { return f.traverse(e, view, dp.lds_doubles, dp.max_extent, l.begin, l.end, l.rows, wgs, wide, unstored, dp.nfolds != 0, dp.nlookups != 0); }))
       return PLL_FAILURE;
   return PLL_SUCCESS;
 }
@@ -3021,6 +3134,15 @@ static int run_resident(Engine * e, const ChainFamily & f, const pll_operation_t
   if (!launch_resident(e, f, dp, view, 0, !e->cherries.empty(), transient)) return PLL_FAILURE;
   // (a storing schedule marks only the stores it deferred: plan_defers)
   if (transient || dp.ndeferred) transient_after_list(e, ops, count, dp, transient ? TRANSIENT_MODE : TRANSIENT_DEFERRED);
+  // what became of the vectors that the deferring lists before this one left out: all given up unread since the end of
+  // the last but one, or some stored for a reader (the family's default level goes by it: s20_defer; lists that leave
+  // nothing out -- the single operations of a smoothing pass -- say nothing about it)
+  if (dp.ndeferred)
+  {
+    e->defer_unread = e->defer_counted && e->deferred_stats.stored_later == e->defer_stored_mark;
+    e->defer_counted = true;
+    e->defer_stored_mark = e->deferred_stats.stored_later;
+  }
   count_list(e, count);
   return PLL_SUCCESS;
 }
