@@ -684,6 +684,66 @@ PLL_EXPORT void pllhip_rell_last_times(double * draw_ms, double * product_ms, do
 PLL_EXPORT int pllhip_bootstrap_weights(const unsigned int * weights, unsigned int patterns, unsigned long long seed,
                                         unsigned int first, unsigned int count, unsigned int * out);
 
+/* ---- pairwise distances and neighbour joining ("Pairwise distances and neighbour joining";
+ *      DESIGN.md section 23) ----
+ * Every character becomes a code: its state where its mask has exactly one bit, "nothing" otherwise (gaps and
+ * ambiguities: pairwise deletion).  N[i][j][a][b] = sum over sites of w * [code_i = a] * [code_j = b], 32-bit integers
+ * made by an integer matrix product, so they are exact and the same from run to run; n_ij = sum over a, b of N_ij is
+ * the number of compared sites.  Distances (fp64, symmetric, zero diagonal) come from the counts:
+ *   PLLHIP_DIST_P    (n - tr N) / n
+ *   PLLHIP_DIST_JC   -b log(1 - p / b), b = (S - 1) / S; max_dist where p >= b
+ *   PLLHIP_DIST_ML   (partition form) the maximiser over [min_dist, max_dist] of
+ *                    sum_ab N_ab log(pi_a ((1 - pinv) sum_r w_r P^r_ab(t) + pinv [a = b])), P^r(t) what
+ *                    pll_update_prob_matrices gives for length t and rate r with parameter set 0; within
+ *                    1e-8 d + 1e-10 of the exact maximiser
+ * A pair without a compared site gets max_dist and is counted (pllhip_distmat_no_overlap).  The calls fail with
+ * PLL_ERROR_PARAM_INVALID for a sharded partition, a tip vector with an entry other than 0 and 1, a sum of weights of
+ * 2^31 or more, PLLHIP_DIST_ML with more than one rate matrix, and PLLHIP_DIST_KEEP_COUNTS where the whole table
+ * exceeds the budget; a character that maps to 0 fails as in pllhip_msa_compute_stats. */
+#define PLLHIP_DIST_P  0
+#define PLLHIP_DIST_JC 1
+#define PLLHIP_DIST_ML 2
+#define PLLHIP_DIST_KEEP_COUNTS (1u << 0)   /* keep N on the device for pllhip_distmat_counts */
+
+typedef struct pllhip_dist_params
+{
+  int method;                      /* PLLHIP_DIST_* */
+  unsigned int flags;
+  double min_dist;                 /* 0: 1e-6 */
+  double max_dist;                 /* 0: 10 */
+  unsigned long long budget_bytes; /* device memory for one band of counts; 0: PLLHIP_DIST_BUDGET_MB or 1 GiB */
+  unsigned int chunk_columns;      /* staged columns per workgroup (rounded up to 64); 0: chosen from the shape */
+} pllhip_dist_params_t;
+
+typedef struct pllhip_distmat pllhip_distmat_t;
+
+PLL_EXPORT pllhip_distmat_t * pllhip_distances_partition(pll_partition_t * partition,
+                                                         const pllhip_dist_params_t * params);
+/* raw characters and a character -> state map; weights NULL: all 1; PLLHIP_DIST_P and PLLHIP_DIST_JC only */
+PLL_EXPORT pllhip_distmat_t * pllhip_distances_msa(const pll_msa_t * msa, unsigned int states,
+                                                   const pll_state_t * tipmap, const unsigned int * weights,
+                                                   const pllhip_dist_params_t * params);
+/* matrix[T][T], finite, T >= 3; only neighbour joining reads it (no counts, compared = 0) */
+PLL_EXPORT pllhip_distmat_t * pllhip_distmat_from_host(unsigned int T, const double * matrix);
+PLL_EXPORT void pllhip_distmat_destroy(pllhip_distmat_t * dm);
+PLL_EXPORT unsigned int pllhip_distmat_size(const pllhip_distmat_t * dm);
+PLL_EXPORT int pllhip_distmat_get(const pllhip_distmat_t * dm, double * out /* [T][T] */);
+PLL_EXPORT int pllhip_distmat_compared(const pllhip_distmat_t * dm, unsigned int * out /* [T][T]: n_ij */);
+/* N_ij -> out[S][S]; needs PLLHIP_DIST_KEEP_COUNTS */
+PLL_EXPORT int pllhip_distmat_counts(const pllhip_distmat_t * dm, unsigned int i, unsigned int j, int * out);
+PLL_EXPORT unsigned long long pllhip_distmat_no_overlap(const pllhip_distmat_t * dm);
+/* Neighbour joining on the device by the rules of INTEGRATION.md (tests/nj_reference.py restates them): the join
+ * order is a function of the matrix alone.  Tips carry clv_index = taxon index and labels[i] (NULL: no labels);
+ * negative lengths are clamped to 0 in the tree only.  T = 3 gives the star. */
+PLL_EXPORT pll_utree_t * pllhip_distmat_nj(pllhip_distmat_t * dm, const char * const * labels);
+/* the joins of that run (made on demand): T - 3 rounds (slot i, slot j, l_i, l_j), then the last three slots and
+ * their lengths: slots[2 (T - 3) + 3], lengths[2 (T - 3) + 3], not clamped */
+PLL_EXPORT int pllhip_distmat_nj_joins(pllhip_distmat_t * dm, unsigned int * slots, double * lengths);
+/* this thread's last distance / neighbour-joining calls, in ms: rows and site list up, the code kernel, the integer
+ * product, the distance kernels (between HIP events); neighbour joining (host clock, its launches included) */
+PLL_EXPORT void pllhip_distances_last_times(double * upload_ms, double * codes_ms, double * counts_ms,
+                                            double * estimate_ms, double * nj_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,7 +202,10 @@ pllhip_node_ancestral_batch pllhip_node_ancestral_begin pllhip_node_ancestral_ad
 pllhip_node_ancestral_last_times
 pllhip_sitelh_create pllhip_sitelh_destroy pllhip_sitelh_count pllhip_sitelh_get pllhip_sitelh_add
 pllhip_sitelh_add_edge pllhip_sitelh_rell pllhip_rell_destroy pllhip_rell_last_times
-pllhip_bootstrap_weights""".split()
+pllhip_bootstrap_weights
+pllhip_distances_partition pllhip_distances_msa pllhip_distmat_from_host pllhip_distmat_destroy pllhip_distmat_size
+pllhip_distmat_get pllhip_distmat_compared pllhip_distmat_counts pllhip_distmat_no_overlap pllhip_distmat_nj
+pllhip_distmat_nj_joins pllhip_distances_last_times""".split()
 
 
 def _u32(a):
@@ -265,6 +268,16 @@ class RellResult(C.Structure):
     _fields_ = [("trees", C.c_uint), ("replicates", C.c_uint), ("best", C.c_uint), ("batch", C.c_uint),
                 ("lnl", c_double_p), ("bp_count", c_uint_p), ("kh_count", c_uint_p), ("sh_count", c_uint_p),
                 ("elw", c_double_p), ("replicate_lnl", c_double_p)]
+
+
+DIST_P, DIST_JC, DIST_ML = 0, 1, 2
+DIST_KEEP_COUNTS = 1
+
+
+class DistParams(C.Structure):
+    """pllhip_dist_params_t"""
+    _fields_ = [("method", C.c_int), ("flags", C.c_uint), ("min_dist", C.c_double), ("max_dist", C.c_double),
+                ("budget_bytes", C.c_ulonglong), ("chunk_columns", C.c_uint)]
 
 
 class Rell:
@@ -490,6 +503,27 @@ class PllLib:
             L.pllhip_rell_last_times.restype = None
             L.pllhip_rell_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
             L.pllhip_bootstrap_weights.argtypes = [c_uint_p, C.c_uint, C.c_ulonglong, C.c_uint, C.c_uint, c_uint_p]
+        if hasattr(L, "pllhip_distances_partition"):
+            L.pllhip_distances_partition.restype = C.c_void_p
+            L.pllhip_distances_partition.argtypes = [pp, C.POINTER(DistParams)]
+            L.pllhip_distances_msa.restype = C.c_void_p
+            L.pllhip_distances_msa.argtypes = [mp, C.c_uint, C.POINTER(C.c_ulonglong), c_uint_p, C.POINTER(DistParams)]
+            L.pllhip_distmat_from_host.restype = C.c_void_p
+            L.pllhip_distmat_from_host.argtypes = [C.c_uint, c_double_p]
+            L.pllhip_distmat_destroy.restype = None
+            L.pllhip_distmat_destroy.argtypes = [C.c_void_p]
+            L.pllhip_distmat_size.restype = C.c_uint
+            L.pllhip_distmat_size.argtypes = [C.c_void_p]
+            L.pllhip_distmat_get.argtypes = [C.c_void_p, c_double_p]
+            L.pllhip_distmat_compared.argtypes = [C.c_void_p, c_uint_p]
+            L.pllhip_distmat_counts.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.POINTER(C.c_int)]
+            L.pllhip_distmat_no_overlap.restype = C.c_ulonglong
+            L.pllhip_distmat_no_overlap.argtypes = [C.c_void_p]
+            L.pllhip_distmat_nj.restype = tp
+            L.pllhip_distmat_nj.argtypes = [C.c_void_p, C.POINTER(C.c_char_p)]
+            L.pllhip_distmat_nj_joins.argtypes = [C.c_void_p, c_uint_p, c_double_p]
+            L.pllhip_distances_last_times.restype = None
+            L.pllhip_distances_last_times.argtypes = [c_double_p] * 5
         if hasattr(L, "pllhip_msa_compute_stats"):
             L.pllhip_empirical_frequencies.restype = c_double_p
             L.pllhip_empirical_frequencies.argtypes = [pp]
@@ -1449,6 +1483,102 @@ class SiteLikelihoods:
         self.L.pllhip_rell_last_times(C.byref(a), C.byref(b), C.byref(c))
         out.times = (a.value, b.value, c.value)
         return out
+
+
+class DistMat:
+    """pllhip_distmat_t (include/pllhip.h): made by distances_partition / distances_msa / distmat_from_host below.
+    A failed call returns None / False with lib.errno set."""
+
+    def __init__(self, lib, handle, states=0):
+        self.lib, self.L, self.h, self.S = lib, lib.lib, handle, states
+        self.T = self.L.pllhip_distmat_size(handle)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.h:
+            self.L.pllhip_distmat_destroy(self.h)
+            self.h = None
+
+    def matrix(self):
+        out = np.zeros((self.T, self.T))
+        return out if self.L.pllhip_distmat_get(self.h, out.ctypes.data_as(c_double_p)) else None
+
+    def compared(self):
+        out = np.zeros((self.T, self.T), np.uint32)
+        return out if self.L.pllhip_distmat_compared(self.h, out.ctypes.data_as(c_uint_p)) else None
+
+    def counts(self, i, j):
+        """N_ij [S][S] int32, or None (needs DIST_KEEP_COUNTS)"""
+        out = np.zeros((self.S, self.S), np.int32)
+        return out if self.L.pllhip_distmat_counts(self.h, i, j, out.ctypes.data_as(C.POINTER(C.c_int))) else None
+
+    @property
+    def no_overlap(self):
+        return self.L.pllhip_distmat_no_overlap(self.h)
+
+    def nj_joins(self):
+        """(slots, lengths): T - 3 rounds of (i, j) / (l_i, l_j), then the last three slots and lengths; or None"""
+        n = 2 * (self.T - 3) + 3
+        slots, lengths = np.zeros(n, np.uint32), np.zeros(n)
+        ok = self.L.pllhip_distmat_nj_joins(self.h, slots.ctypes.data_as(c_uint_p), lengths.ctypes.data_as(c_double_p))
+        return (slots, lengths) if ok else None
+
+    def nj(self, labels=None):
+        """the neighbour-joining tree as POINTER(UTree) (the caller destroys it), or None"""
+        arr = None
+        if labels is not None:
+            arr = (C.c_char_p * len(labels))(*[l if isinstance(l, bytes) else l.encode() for l in labels])
+        t = self.L.pllhip_distmat_nj(self.h, arr)
+        return t if t else None
+
+    def last_times(self):
+        """(upload, codes, counts, estimate, nj) ms of this thread's last calls"""
+        v = [C.c_double(0) for _ in range(5)]
+        self.L.pllhip_distances_last_times(*[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
+
+def _dist_params(method, flags, min_dist, max_dist, budget_bytes, chunk_columns):
+    return DistParams(method, flags, min_dist, max_dist, budget_bytes, chunk_columns)
+
+
+def distances_partition(lib, partition, method=DIST_P, flags=0, min_dist=0.0, max_dist=0.0, budget_bytes=0,
+                        chunk_columns=0):
+    """pllhip_distances_partition as a DistMat, or None"""
+    params = _dist_params(method, flags, min_dist, max_dist, budget_bytes, chunk_columns)
+    lib.errno = 0
+    h = lib.lib.pllhip_distances_partition(partition, C.byref(params))
+    return DistMat(lib, h, partition.contents.states) if h else None
+
+
+def distances_msa(lib, rows, states, charmap, weights=None, method=DIST_P, flags=0, min_dist=0.0, max_dist=0.0,
+                  budget_bytes=0, chunk_columns=0):
+    """pllhip_distances_msa on rows ([T][L] bytes) as a DistMat, or None"""
+    rows = [bytes(r) for r in rows]
+    T, L = len(rows), len(rows[0])
+    bufs = [C.create_string_buffer(r, len(r) + 1) for r in rows]
+    seqs = (C.c_void_p * T)(*[C.addressof(b) for b in bufs])
+    msa = Msa(T, L, seqs, None)
+    cmap = (C.c_ulonglong * 256)(*[int(x) for x in charmap])
+    w = None if weights is None else _u32(weights)
+    params = _dist_params(method, flags, min_dist, max_dist, budget_bytes, chunk_columns)
+    lib.errno = 0
+    h = lib.lib.pllhip_distances_msa(C.byref(msa), states, cmap, None if w is None else w.ctypes.data_as(c_uint_p),
+                                     C.byref(params))
+    return DistMat(lib, h, states) if h else None
+
+
+def distmat_from_host(lib, matrix):
+    """pllhip_distmat_from_host as a DistMat, or None"""
+    m = _f64(matrix)
+    lib.errno = 0
+    h = lib.lib.pllhip_distmat_from_host(m.shape[0], m.ctypes.data_as(c_double_p))
+    return DistMat(lib, h) if h else None
 
 
 def bootstrap_weights(lib, weights, patterns, seed, first, count):
