@@ -1,0 +1,182 @@
+// device_job.hpp -- the host plumbing the device modules share (pll_*_dev.hip, and pll_core.hip for the allocator):
+// owned device and pinned buffers, the calling thread's device put back on every path, the check of the device a
+// call runs on, and DeviceJob: the device, stream, buffers and events of one call, gone when it returns.
+#pragma once
+
+#include "engine.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+namespace pllhip {
+
+// count elements of T on the current device (0: one element); a failure leaves no sticky error behind
+template <typename T>
+bool dev_alloc(T ** ptr, size_t count, const char * what)
+{
+  const size_t bytes = (count ? count : 1) * sizeof(T);
+  *ptr = nullptr;
+  const hipError_t err = hipMalloc(reinterpret_cast<void **>(ptr), bytes);
+  if (err == hipSuccess) return true;
+  *ptr = nullptr;
+  (void)hipGetLastError();
+  set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(err));
+  return false;
+}
+
+template <typename T>
+bool pinned_alloc(T ** ptr, size_t count)
+{
+  *ptr = nullptr;
+  const hipError_t err = hipHostMalloc(reinterpret_cast<void **>(ptr), count * sizeof(T));
+  if (err == hipSuccess) return true;
+  *ptr = nullptr;
+  (void)hipGetLastError();
+  set_error(PLL_ERROR_MEM_ALLOC, "hipHostMalloc of the staging buffer (%zu bytes) failed: %s", count * sizeof(T),
+            hipGetErrorString(err));
+  return false;
+}
+
+// one device allocation, freed with the scope unless release() has handed it on
+template <typename T> struct DevBuf
+{
+  T * p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf & operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  bool alloc(size_t count, const char * what) { return dev_alloc(&p, count, what); }
+  T * release() { T * q = p; p = nullptr; return q; }
+};
+
+// ... and one pinned host allocation
+template <typename T> struct PinnedBuf
+{
+  T * p = nullptr;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf & operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+  bool alloc(size_t count) { return pinned_alloc(&p, count); }
+};
+
+// the calling thread's device, put back when the scope ends
+struct DeviceScope
+{
+  int saved = -1;
+  DeviceScope() = default;
+  DeviceScope(const DeviceScope &) = delete;
+  DeviceScope & operator=(const DeviceScope &) = delete;
+  ~DeviceScope() { if (saved >= 0) (void)hipSetDevice(saved); }
+  bool save() { return hip_ok(hipGetDevice(&saved), "hipGetDevice"); }      // (the caller switches devices itself)
+  bool enter(int device) { return save() && hip_ok(hipSetDevice(device), "hipSetDevice"); }
+};
+
+// the device pllhip_get_device() names, if it is visible
+inline bool caller_device(const char * who, int * device)
+{
+  *device = pllhip_get_device();
+  if (*device >= 0 && *device < pllhip_device_count()) return true;
+  set_error(PLL_ERROR_HIP_NODEVICE, "%s runs on HIP device %d; %d visible", who, *device, pllhip_device_count());
+  return false;
+}
+
+// the device tables of an engine's tip pointers (vectors; codes, null without coded tips), uploaded on the engine's
+// stream and complete on return (pll_core.hip)
+bool tip_pointer_tables(Engine * e, DevBuf<const double *> & clv, DevBuf<const uint8_t *> & codes);
+
+inline unsigned grid_for(size_t items, unsigned per_block)
+{
+  return (unsigned)std::max<size_t>(1, std::min<size_t>((items + per_block - 1) / per_block, 4096));
+}
+
+// <env>=<0..64>: only that many bits of a hash are used (a test knob: with few bits the full compare and the probing
+// carry the result)
+inline unsigned long long hash_keep_mask(const char * env)
+{
+  const char * v = getenv(env);
+  if (!v || !*v) return ~0ULL;
+  const long bits = std::max(0L, std::min(64L, atol(v)));
+  return bits >= 64 ? ~0ULL : ((1ULL << bits) - 1ULL);
+}
+
+// everything one call owns on a device: when it goes, the stream is idle, the buffers, the pinned memory and the
+// events are gone, a stream of its own is destroyed and the caller's device is current again
+struct DeviceJob
+{
+  hipStream_t stream = nullptr;
+
+  DeviceJob() = default;
+  DeviceJob(const DeviceJob &) = delete;
+  DeviceJob & operator=(const DeviceJob &) = delete;
+  ~DeviceJob()
+  {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (void * p : bufs) (void)hipFree(p);
+    for (void * p : pins) (void)hipHostFree(p);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }                                                             // (then `scope` puts the device back)
+
+  // no borrowed stream: a non-blocking stream of the job's own
+  bool enter(int device, hipStream_t borrowed = nullptr)
+  {
+    if (!scope.enter(device)) return false;
+    if (borrowed) { stream = borrowed; return true; }
+    own_stream = true;
+    return hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate");
+  }
+
+  // nullptr on failure
+  template <typename T> T * alloc(size_t count, const char * what)
+  {
+    T * p = nullptr;
+    if (dev_alloc(&p, count, what)) bufs.push_back(const_cast<void *>(static_cast<const void *>(p)));
+    return p;
+  }
+  // (a buffer the result keeps)
+  void keep(const void * p) { bufs.erase(std::remove(bufs.begin(), bufs.end(), p), bufs.end()); }
+
+  template <typename T> T * pinned(size_t count)
+  {
+    T * p = nullptr;
+    if (pinned_alloc(&p, count)) pins.push_back(p);
+    return p;
+  }
+
+  hipEvent_t event(unsigned flags = hipEventDefault)
+  {
+    hipEvent_t e = nullptr;
+    if (!hip_ok(hipEventCreateWithFlags(&e, flags), "hipEventCreate")) return nullptr;
+    events.push_back(e);
+    return e;
+  }
+  // a new event, recorded on the stream
+  hipEvent_t mark()
+  {
+    hipEvent_t e = event();
+    return e && hip_ok(hipEventRecord(e, stream), "hipEventRecord") ? e : nullptr;
+  }
+  bool elapsed(hipEvent_t a, hipEvent_t b, float * ms)
+  {
+    return hip_ok(hipEventElapsedTime(ms, a, b), "hipEventElapsedTime");
+  }
+
+  template <typename T> bool upload(T * dst, const T * src, size_t count, const char * what)
+  {
+    return hip_ok(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, stream), what);
+  }
+  template <typename T> bool download(T * dst, const T * src, size_t count, const char * what)
+  {
+    return hip_ok(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, stream), what);
+  }
+
+private:
+  DeviceScope scope;
+  bool own_stream = false;
+  std::vector<void *> bufs, pins;
+  std::vector<hipEvent_t> events;
+};
+
+} // namespace pllhip

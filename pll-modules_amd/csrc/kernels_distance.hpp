@@ -21,26 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "tip_view.hpp"
+
 namespace pllhip {
-
-// where the characters come from, as MstTips of kernels_msa_stats.hpp views them: a table of per-tip pointers (a
-// partition) or rows at a fixed stride (an alignment); codes, else vectors in the API layout or the 32-site blocked
-// layout (brows != 0)
-struct DstTips
-{
-  const uint8_t * const * code_rows;
-  const uint8_t * code_base;
-  unsigned long long code_stride;
-  const double * const * clv_rows;
-  unsigned R, Sp, brows;
-};
-
-// entry k of rate 0 of site n
-__device__ inline double dst_clv(const DstTips & tp, unsigned t, unsigned long long n, unsigned k)
-{
-  return tp.brows ? tp.clv_rows[t][(((n >> 5) * tp.R) * tp.brows + k) * 32 + (n & 31)]
-                  : tp.clv_rows[t][n * tp.R * tp.Sp + k];
-}
 
 constexpr unsigned DST_WG = 256;
 constexpr uint8_t DST_NONE = 0xFF;
@@ -58,7 +41,7 @@ constexpr unsigned NJ_MAX_GRID = 256;
 using dst_v4i = __attribute__((ext_vector_type(4))) int;
 
 template <bool CODED>
-__global__ __launch_bounds__(DST_WG) void k_dst_codes(DstTips tp, const unsigned long long * __restrict__ tipmap,
+__global__ __launch_bounds__(DST_WG) void k_dst_codes(TipView tp, const unsigned long long * __restrict__ tipmap,
                                                       const unsigned * __restrict__ col_site, unsigned T, unsigned N,
                                                       unsigned S, unsigned C, unsigned long long Cpad,
                                                       uint8_t * __restrict__ codes,
@@ -87,7 +70,7 @@ __global__ __launch_bounds__(DST_WG) void k_dst_codes(DstTips tp, const unsigned
         bool other = false;
         for (unsigned k = 0; k < S; ++k)
         {
-          const double x = dst_clv(tp, t, n, k);
+          const double x = tip_clv(tp, t, n, k);
           if (x == 1.0) { ++ones; which = k; }
           else if (x != 0.0) other = true;
         }

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "tip_view.hpp"
+
 namespace pllhip {
 
 constexpr unsigned MST_WG = 256;
@@ -36,17 +38,6 @@ constexpr unsigned long long MST_NO_BAD = ~0ULL;
 constexpr uint8_t MST_FLAG_GAPCOL = 1;   // every character of the column is a gap
 constexpr uint8_t MST_FLAG_ONE = 2;      // the AND of the column's masks has exactly one bit
 
-// where the characters come from: a table of per-tip pointers (a partition) or rows at a fixed stride (an
-// alignment); codes for CODED, else vectors in the API layout or the 32-site blocked layout (brows != 0)
-struct MstTips
-{
-  const uint8_t * const * code_rows;
-  const uint8_t * code_base;
-  unsigned long long code_stride;
-  const double * const * clv_rows;
-  unsigned R, Sp, brows;
-};
-
 template <int SMAX> struct MstShape
 {
   static constexpr unsigned TASKS = SMAX * (SMAX - 1) / 2 + SMAX;             // pairs, then the diagonal
@@ -61,14 +52,8 @@ __device__ inline unsigned long long mst_wave_sum(unsigned long long v)
   return v;
 }
 
-__device__ inline double mst_clv(const MstTips & tp, unsigned t, unsigned long long n, unsigned k)
-{
-  return tp.brows ? tp.clv_rows[t][(((n >> 5) * tp.R) * tp.brows + k) * 32 + (n & 31)]
-                  : tp.clv_rows[t][n * tp.R * tp.Sp + k];
-}
-
 template <int SMAX, int VPL, bool CODED>
-__global__ __launch_bounds__(MST_WG) void k_mst_tables(MstTips tp, const unsigned long long * __restrict__ tipmap,
+__global__ __launch_bounds__(MST_WG) void k_mst_tables(TipView tp, const unsigned long long * __restrict__ tipmap,
                                                        const unsigned * __restrict__ weights, unsigned T, unsigned N,
                                                        unsigned S, unsigned long long * __restrict__ out,
                                                        uint8_t * __restrict__ flags,
@@ -161,7 +146,7 @@ __global__ __launch_bounds__(MST_WG) void k_mst_tables(MstTips tp, const unsigne
           if (live[v])
             for (unsigned k = 0; k < S; ++k)            // (no per-lane array here: the bits go into one register pair)
             {
-              const double x = mst_clv(tp, t, n0 + v, k);
+              const double x = tip_clv(tp, t, n0 + v, k);
               if (x > 0.0) m[v] |= 1ULL << k;
               if (x < 1e-7) all_set = false;
               if (x != 0.0 && x != 1.0) other = true;
@@ -266,7 +251,7 @@ __global__ __launch_bounds__(MST_WG) void k_mst_tables(MstTips tp, const unsigne
 // site: KP (a power of two >= S, <= 64) neighbouring lanes hold a character, sum(v) is a butterfly over them, a lane
 // adds its sites in ascending order (tips inside), and the lanes of a block that own the same state are added in a
 // fixed tree.  The same grid gives the same bits.
-__global__ __launch_bounds__(MST_WG) void k_mst_vecfreq(MstTips tp, const unsigned * __restrict__ weights, unsigned T,
+__global__ __launch_bounds__(MST_WG) void k_mst_vecfreq(TipView tp, const unsigned * __restrict__ weights, unsigned T,
                                                         unsigned N, unsigned S, unsigned KP,
                                                         double * __restrict__ partial)
 {
@@ -279,7 +264,7 @@ __global__ __launch_bounds__(MST_WG) void k_mst_vecfreq(MstTips tp, const unsign
     const double w = (double)weights[n];
     for (unsigned t = 0; t < T; ++t)
     {
-      const double x = k < S ? mst_clv(tp, t, n, k) : 0.0;
+      const double x = k < S ? tip_clv(tp, t, n, k) : 0.0;
       double sum = x;
       for (unsigned off = KP >> 1; off > 0; off >>= 1) sum += __shfl_xor(sum, (int)off, 64);
       f += w * x / sum;

@@ -17,7 +17,7 @@
 // Operation lists are level-scheduled: ops of one dependency level share one
 // launch (grid.y = op), their descriptors travel by value in the kernel
 // arguments, so no host->device copy sits on the critical path.
-#include "engine.h"
+#include "device_job.hpp"
 #include "kernels_common.hpp"
 #include "kernels_generic.hpp"
 #include "kernels_s4.hpp"
@@ -117,22 +117,6 @@ static ModelView model_view(const Engine * e)
   mv.S = e->S;
   mv.Sp = e->Sp;
   return mv;
-}
-
-template <typename T>
-static bool dev_alloc(T ** ptr, size_t count, const char * what)
-{
-  *ptr = nullptr;
-  if (!count) count = 1;
-  hipError_t err = hipMalloc(reinterpret_cast<void **>(ptr), count * sizeof(T));
-  if (err != hipSuccess)
-  {
-    set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s",
-              count * sizeof(T), what, hipGetErrorString(err));
-    *ptr = nullptr;
-    return false;
-  }
-  return true;
 }
 
 // Kernel arguments in device memory (the ROCm runtime's HIP_FORCE_DEV_KERNARG): by default they sit in
@@ -4445,6 +4429,20 @@ static int newton_finish(Engine * lead, const std::vector<Engine *> & all, unsig
   }
 }
 
+// device_job.hpp (the host arrays are local, hence the synchronise)
+bool tip_pointer_tables(Engine * e, DevBuf<const double *> & clv, DevBuf<const uint8_t *> & codes)
+{
+  std::vector<const double *> h_clv(e->tips ? e->tips : 1, nullptr);
+  std::vector<const uint8_t *> h_codes(e->tips ? e->tips : 1, nullptr);
+  for (unsigned t = 0; t < e->tips; ++t) { h_clv[t] = e->d_clv[t]; h_codes[t] = e->coded_tips ? e->d_codes[t] : nullptr; }
+  return clv.alloc(h_clv.size(), "tip table") && codes.alloc(h_codes.size(), "tip table") &&
+         hip_ok(hipMemcpyAsync(clv.p, h_clv.data(), sizeof(void *) * h_clv.size(), hipMemcpyHostToDevice, e->stream),
+                "upload tip table") &&
+         hip_ok(hipMemcpyAsync(codes.p, h_codes.data(), sizeof(void *) * h_codes.size(), hipMemcpyHostToDevice, e->stream),
+                "upload tip table") &&
+         hip_ok(hipStreamSynchronize(e->stream), "upload tip table");
+}
+
 } // namespace pllhip
 
 extern "C" {
@@ -4741,24 +4739,15 @@ int pll_update_invariant_sites(pll_partition_t * p)
   }
   if (!e->d_invariant)
     if (!dev_alloc(&e->d_invariant, (size_t)e->N, "invariant sites")) return PLL_FAILURE;
-  // device tables of tip pointers
-  std::vector<const double *> h_clv(e->tips ? e->tips : 1, nullptr);
-  std::vector<const uint8_t *> h_codes(e->tips ? e->tips : 1, nullptr);
-  for (unsigned t = 0; t < e->tips; ++t) { h_clv[t] = e->d_clv[t]; h_codes[t] = e->coded_tips ? e->d_codes[t] : nullptr; }
-  const double ** d_tc = nullptr;
-  const uint8_t ** d_tk = nullptr;
-  if (!dev_alloc(&d_tc, h_clv.size(), "tip table") || !dev_alloc(&d_tk, h_codes.size(), "tip table"))
-    return PLL_FAILURE;
-  PLLHIP_TRY(hipMemcpyAsync(d_tc, h_clv.data(), sizeof(void *) * h_clv.size(), hipMemcpyHostToDevice, e->stream));
-  PLLHIP_TRY(hipMemcpyAsync(d_tk, h_codes.data(), sizeof(void *) * h_codes.size(), hipMemcpyHostToDevice, e->stream));
+  DevBuf<const double *> d_tc;
+  DevBuf<const uint8_t *> d_tk;
+  if (!tip_pointer_tables(e, d_tc, d_tk)) return PLL_FAILURE;
   hipLaunchKernelGGL(k_invariant, dim3(reduce_grid(e)), dim3(256), 0, e->stream,
-                     d_tc, d_tk, e->d_tipmap, e->tips, e->N, e->R, e->S, e->Sp, e->rows, e->d_invariant);
+                     d_tc.p, d_tk.p, e->d_tipmap, e->tips, e->N, e->R, e->S, e->Sp, e->rows, e->d_invariant);
   PLLHIP_TRY(hipGetLastError());
   if (e->N)
     PLLHIP_TRY(hipMemcpyAsync(p->invariant, e->d_invariant, sizeof(int) * e->N, hipMemcpyDeviceToHost, e->stream));
   PLLHIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipFree(d_tc);
-  (void)hipFree(d_tk);
   e->invariant_uploaded = true;
   return PLL_SUCCESS;
 }
@@ -4794,18 +4783,17 @@ int pll_compute_node_ancestral(pll_partition_t * p, unsigned int node_clv_index,
   if (!e->N) return PLL_SUCCESS;
   if (!need_clv(e, node_clv_index) || !need_clv(e, other_clv_index)) return PLL_FAILURE;
   // the result is normalised per site, so scaler counts cancel
-  double * d_out = nullptr;
-  if (!dev_alloc(&d_out, (size_t)e->N * e->S, "ancestral states")) return PLL_FAILURE;
+  DevBuf<double> d_out;
+  if (!d_out.alloc((size_t)e->N * e->S, "ancestral states")) return PLL_FAILURE;
   const unsigned gx = (unsigned)std::min<unsigned long long>(((unsigned long long)e->N + 255) / 256, 4096);
   hipLaunchKernelGGL(k_node_ancestral, dim3(gx), dim3(256), 0, e->stream,
                      model_view(e), make_params(p, freqs_indices), node_ref(e, node_clv_index),
                      node_ref(e, other_clv_index),
                      e->d_pmat + (size_t)matrix_index * e->R * e->S * e->Sp, e->d_tipmap, e->rows,
-                     e->N, e->R, d_out);
+                     e->N, e->R, d_out.p);
   PLLHIP_TRY(hipGetLastError());
-  PLLHIP_TRY(hipMemcpyAsync(ancestral, d_out, sizeof(double) * e->N * e->S, hipMemcpyDeviceToHost, e->stream));
+  PLLHIP_TRY(hipMemcpyAsync(ancestral, d_out.p, sizeof(double) * e->N * e->S, hipMemcpyDeviceToHost, e->stream));
   PLLHIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipFree(d_out);
   return PLL_SUCCESS;
 }
 

@@ -6,7 +6,7 @@
 // character into a one-byte code, and walks the taxa in bands whose rows of the count table fit the budget: the
 // integer product fills the band's rows, the distance kernel reads them.  The partition form runs on the partition's
 // stream, the alignment form and neighbour joining on a stream of their own on the device pllhip_get_device() names.
-#include "engine.h"
+#include "device_job.hpp"
 #include "kernels_distance.hpp"
 #include "msa_upload.hpp"
 #include "nj_tree.h"
@@ -43,77 +43,6 @@ constexpr u64 DIST_DEFAULT_BUDGET = 1ULL << 30;
 constexpr unsigned DIST_TARGET_WAVES = 4096;                  // waves the product aims for when it splits the columns
 
 thread_local double g_last_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // upload, codes, counts, estimate, nj
-
-// device buffers, events and the stream of one call, gone when it returns
-struct DistJob
-{
-  int saved_device = -1;
-  bool own_stream = false;
-  hipStream_t stream = nullptr;
-  std::vector<void *> bufs;
-  std::vector<hipEvent_t> events;
-  // msa_upload.hpp
-  uint8_t * d_in = nullptr, * h_stage = nullptr;
-  hipEvent_t half_free[2] = {nullptr, nullptr};
-
-  ~DistJob()
-  {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (void * p : bufs) (void)hipFree(p);
-    if (h_stage) (void)hipHostFree(h_stage);
-    for (hipEvent_t e : events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : half_free) if (e) (void)hipEventDestroy(e);
-    if (own_stream && stream) (void)hipStreamDestroy(stream);
-    if (saved_device >= 0) (void)hipSetDevice(saved_device);
-  }
-
-  bool enter(int device, hipStream_t use)
-  {
-    if (!hip_ok(hipGetDevice(&saved_device), "hipGetDevice") || !hip_ok(hipSetDevice(device), "hipSetDevice")) return false;
-    if (use) { stream = use; return true; }
-    own_stream = true;
-    return hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate");
-  }
-
-  template <typename T> T * alloc(size_t count, const char * what)
-  {
-    void * p = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    const hipError_t err = hipMalloc(&p, bytes);
-    if (err != hipSuccess)
-    {
-      (void)hipGetLastError();
-      set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s", bytes, what, hipGetErrorString(err));
-      return nullptr;
-    }
-    bufs.push_back(p);
-    return static_cast<T *>(p);
-  }
-
-  // (a buffer the result keeps)
-  void release(void * p) { bufs.erase(std::find(bufs.begin(), bufs.end(), p)); }
-
-  hipEvent_t event()
-  {
-    hipEvent_t e = nullptr;
-    if (!hip_ok(hipEventCreate(&e), "hipEventCreate")) return nullptr;
-    events.push_back(e);
-    return e;
-  }
-
-  template <typename T> bool upload(T * dst, const T * src, size_t count, const char * what)
-  {
-    return hip_ok(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, stream), what);
-  }
-};
-
-bool pick_device(int & device, const char * who)
-{
-  device = pllhip_get_device();
-  if (device >= 0 && device < pllhip_device_count()) return true;
-  set_error(PLL_ERROR_HIP_NODEVICE, "%s runs on HIP device %d; %d visible", who, device, pllhip_device_count());
-  return false;
-}
 
 struct Settings
 {
@@ -158,7 +87,7 @@ bool read_params(const pllhip_dist_params_t * params, bool partition_form, Setti
 // where the characters come from, and what the ML distance needs of the model (host pointers; R = 0: no model)
 struct Source
 {
-  DstTips view = {};
+  TipView view = {};
   bool coded = false;
   const u64 * d_tipmap = nullptr;
   unsigned T = 0, N = 0, S = 0;
@@ -189,7 +118,7 @@ bool stage_columns(const Source & src, std::vector<unsigned> & col_site, std::ve
 
 // codes, counts and distances of `src` on the job's stream.  *bad = tip * sites + site of an unmapped character
 // (DST_NO_BAD: none; the caller words the error).
-pllhip_distmat * compute(DistJob & j, const Source & src, const Settings & st, int device, double upload_ms, u64 * bad,
+pllhip_distmat * compute(DeviceJob & j, const Source & src, const Settings & st, int device, double upload_ms, u64 * bad,
                          const char * who)
 {
   const unsigned T = src.T, S = src.S;
@@ -327,7 +256,7 @@ pllhip_distmat * compute(DistJob & j, const Source & src, const Settings & st, i
     delete dm;
     return nullptr;
   }
-  if (keep) { dm->d_counts = d_counts; j.release(d_counts); }
+  if (keep) { dm->d_counts = d_counts; j.keep(d_counts); }
   g_last_ms[0] = upload_ms + up;
   g_last_ms[1] = codes;
   g_last_ms[2] = counts_ms;
@@ -347,8 +276,8 @@ bool run_nj(pllhip_distmat * dm)
 {
   const unsigned T = dm->T, rounds = T - 3, entries = 2 * rounds + 3;
   const auto t_begin = std::chrono::steady_clock::now();
-  DistJob j;
-  if (!j.enter(dm->device, nullptr)) return false;
+  DeviceJob j;
+  if (!j.enter(dm->device)) return false;
   double * d_D = j.alloc<double>((size_t)T * T, "the distance matrix");
   double * d_r = j.alloc<double>(T, "row sums");
   unsigned * d_alive = j.alloc<unsigned>(T, "active slots");
@@ -423,21 +352,14 @@ PLL_EXPORT pllhip_distmat_t * pllhip_distances_partition(pll_partition_t * parti
     }
     if (!partition->eigen_decomp_valid[0] && !pll_update_eigen(partition, 0)) return nullptr;
   }
-  DistJob j;
-  if (!j.enter(e->device, e->stream) || !upload_tipmap(partition)) return nullptr;
-  // device tables of tip pointers, as the statistics build them
-  std::vector<const double *> h_clv(e->tips, nullptr);
-  std::vector<const uint8_t *> h_codes(e->tips, nullptr);
-  for (unsigned t = 0; t < e->tips; ++t) { h_clv[t] = e->d_clv[t]; h_codes[t] = e->coded_tips ? e->d_codes[t] : nullptr; }
-  const double ** d_clv = j.alloc<const double *>(e->tips, "tip table");
-  const uint8_t ** d_rows = j.alloc<const uint8_t *>(e->tips, "tip table");
-  if (!d_clv || !d_rows || !j.upload(d_clv, h_clv.data(), (size_t)e->tips, "upload tip table") ||
-      !j.upload(d_rows, h_codes.data(), (size_t)e->tips, "upload tip table") ||
-      !hip_ok(hipStreamSynchronize(e->stream), "upload tip table"))
+  DeviceJob j;
+  DevBuf<const double *> d_clv;
+  DevBuf<const uint8_t *> d_rows;
+  if (!j.enter(e->device, e->stream) || !upload_tipmap(partition) || !tip_pointer_tables(e, d_clv, d_rows))
     return nullptr;
   Source src;
-  src.view.code_rows = d_rows;
-  src.view.clv_rows = d_clv;
+  src.view.code_rows = d_rows.p;
+  src.view.clv_rows = d_clv.p;
   src.view.R = e->R;
   src.view.Sp = e->Sp;
   src.view.brows = e->rows;
@@ -479,35 +401,25 @@ PLL_EXPORT pllhip_distmat_t * pllhip_distances_msa(const pll_msa_t * msa, unsign
       return nullptr;
     }
   int device = 0;
-  if (!pick_device(device, who)) return nullptr;
+  if (!caller_device(who, &device)) return nullptr;
   const unsigned T = (unsigned)msa->count, L = (unsigned)msa->length;
   const size_t Lp = ((size_t)L + 255u) & ~(size_t)255u;
   const size_t half = std::min(DIST_STAGE_BYTES, (size_t)T * Lp);
-  DistJob j;
-  if (!j.enter(device, nullptr)) return nullptr;
-  for (hipEvent_t & e : j.half_free)
-    if (!hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) return nullptr;
+  DeviceJob j;
+  MsaStager stager;
+  if (!j.enter(device)) return nullptr;
   hipEvent_t e0 = j.event(), e1 = j.event();
-  j.d_in = j.alloc<uint8_t>((size_t)T * Lp, "the alignment");
+  uint8_t * d_in = j.alloc<uint8_t>((size_t)T * Lp, "the alignment");
   u64 * d_map = j.alloc<u64>(256, "the character map");
-  if (!e0 || !e1 || !j.d_in || !d_map) return nullptr;
-  const hipError_t herr = hipHostMalloc(reinterpret_cast<void **>(&j.h_stage), 2u * half);
-  if (herr != hipSuccess)
-  {
-    (void)hipGetLastError();
-    j.h_stage = nullptr;
-    set_error(PLL_ERROR_MEM_ALLOC, "hipHostMalloc of the staging buffer (%zu bytes) failed: %s", 2u * half,
-              hipGetErrorString(herr));
-    return nullptr;
-  }
+  if (!e0 || !e1 || !d_in || !d_map || !stager.open(half)) return nullptr;
   float up = 0.f;
-  if (!hip_ok(hipEventRecord(e0, j.stream), "hipEventRecord") || !upload_rows(j, msa->sequence, T, L, Lp, half) ||
+  if (!hip_ok(hipEventRecord(e0, j.stream), "hipEventRecord") ||
+      !stager.rows(j.stream, d_in, msa->sequence, T, L, Lp, half) ||
       !j.upload(d_map, (const u64 *)tipmap, 256, "upload map") || !hip_ok(hipEventRecord(e1, j.stream), "hipEventRecord") ||
-      !hip_ok(hipStreamSynchronize(j.stream), "upload alignment") ||
-      !hip_ok(hipEventElapsedTime(&up, e0, e1), "hipEventElapsedTime"))
+      !hip_ok(hipStreamSynchronize(j.stream), "upload alignment") || !j.elapsed(e0, e1, &up))
     return nullptr;
   Source src;
-  src.view.code_base = j.d_in;
+  src.view.code_base = d_in;
   src.view.code_stride = Lp;
   src.coded = true;
   src.d_tipmap = d_map;
@@ -542,7 +454,7 @@ PLL_EXPORT pllhip_distmat_t * pllhip_distmat_from_host(unsigned int T, const dou
       return nullptr;
     }
   int device = 0;
-  if (!pick_device(device, who)) return nullptr;
+  if (!caller_device(who, &device)) return nullptr;
   pllhip_distmat * dm = new pllhip_distmat;
   dm->T = T;
   dm->device = device;
@@ -556,11 +468,9 @@ PLL_EXPORT void pllhip_distmat_destroy(pllhip_distmat_t * dm)
   if (!dm) return;
   if (dm->d_counts)
   {
-    int saved = -1;
-    (void)hipGetDevice(&saved);
-    (void)hipSetDevice(dm->device);
+    DeviceScope scope;
+    (void)scope.enter(dm->device);
     (void)hipFree(dm->d_counts);
-    if (saved >= 0) (void)hipSetDevice(saved);
   }
   delete dm;
 }
@@ -605,13 +515,10 @@ PLL_EXPORT int pllhip_distmat_counts(const pllhip_distmat_t * dm, unsigned int i
   const unsigned S = dm->S, lo = std::min(i, j), hi = std::max(i, j);
   const size_t M = (size_t)dm->T * S;
   std::vector<int> blk((size_t)S * S);
-  int saved = -1;
-  PLLHIP_TRY(hipGetDevice(&saved));
-  PLLHIP_TRY(hipSetDevice(dm->device));
-  const hipError_t err = hipMemcpy2D(blk.data(), S * sizeof(int), dm->d_counts + (size_t)lo * S * M + (size_t)hi * S,
-                                     M * sizeof(int), S * sizeof(int), S, hipMemcpyDeviceToHost);
-  (void)hipSetDevice(saved);
-  PLLHIP_TRY(err);
+  DeviceScope scope;
+  if (!scope.enter(dm->device)) return PLL_FAILURE;
+  PLLHIP_TRY(hipMemcpy2D(blk.data(), S * sizeof(int), dm->d_counts + (size_t)lo * S * M + (size_t)hi * S, M * sizeof(int),
+                         S * sizeof(int), S, hipMemcpyDeviceToHost));
   for (unsigned a = 0; a < S; ++a)
     for (unsigned b = 0; b < S; ++b)
     {

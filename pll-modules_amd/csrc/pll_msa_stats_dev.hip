@@ -6,7 +6,7 @@
 // partition forms run on the partition's stream (per shard on the shard's device, tables added here); the alignment
 // form runs on a stream of its own on the device pllhip_get_device() names.  Everything a call allocates is gone
 // when it returns, and nothing of the caller's is written.
-#include "engine.h"
+#include "device_job.hpp"
 #include "kernels_msa_stats.hpp"
 #include "msa_upload.hpp"
 #include "pllhip.h"
@@ -31,29 +31,6 @@ constexpr unsigned VECFREQ_MAX_GRID = 1024;
 
 thread_local double g_last_ms[2] = {0.0, 0.0};                // upload, kernels of the last call
 
-template <typename T> struct DevBuf
-{
-  T * p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  bool alloc(size_t count, const char * what)
-  {
-    const hipError_t err = hipMalloc(reinterpret_cast<void **>(&p), (count ? count : 1) * sizeof(T));
-    if (err == hipSuccess) return true;
-    p = nullptr;
-    (void)hipGetLastError();
-    set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s", (count ? count : 1) * sizeof(T), what,
-              hipGetErrorString(err));
-    return false;
-  }
-};
-
-struct EventPair
-{
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  bool create() { return hip_ok(hipEventCreate(&a), "hipEventCreate") && hip_ok(hipEventCreate(&b), "hipEventCreate"); }
-};
-
 unsigned tables_grid(unsigned N, unsigned vpl)
 {
   const unsigned tile = MST_WG * vpl;
@@ -62,7 +39,7 @@ unsigned tables_grid(unsigned N, unsigned vpl)
 
 // the tier of the state loop: <= 4, <= 32, <= 64 states; coded tips of the first tier take 4 sites per lane
 template <bool CODED>
-void launch_tables(hipStream_t stream, const MstTips & tp, const u64 * d_tipmap, const unsigned * d_weights, unsigned T,
+void launch_tables(hipStream_t stream, const TipView & tp, const u64 * d_tipmap, const unsigned * d_weights, unsigned T,
                    unsigned N, unsigned S, u64 * d_tab, uint8_t * d_flags, u64 * d_seq_gap)
 {
   if (S <= 4)
@@ -100,22 +77,12 @@ struct TipTables
 {
   DevBuf<const double *> clv;
   DevBuf<const uint8_t *> codes;
-  MstTips view = {};
+  TipView view = {};
 };
 
-// device tables of tip pointers, as pll_update_invariant_sites builds them
 bool tip_tables(Engine * e, TipTables & tt)
 {
-  std::vector<const double *> h_clv(e->tips ? e->tips : 1, nullptr);
-  std::vector<const uint8_t *> h_codes(e->tips ? e->tips : 1, nullptr);
-  for (unsigned t = 0; t < e->tips; ++t) { h_clv[t] = e->d_clv[t]; h_codes[t] = e->coded_tips ? e->d_codes[t] : nullptr; }
-  if (!tt.clv.alloc(h_clv.size(), "tip table") || !tt.codes.alloc(h_codes.size(), "tip table")) return false;
-  if (!hip_ok(hipMemcpyAsync(tt.clv.p, h_clv.data(), sizeof(void *) * h_clv.size(), hipMemcpyHostToDevice, e->stream),
-              "upload tip table") ||
-      !hip_ok(hipMemcpyAsync(tt.codes.p, h_codes.data(), sizeof(void *) * h_codes.size(), hipMemcpyHostToDevice, e->stream),
-              "upload tip table") ||
-      !hip_ok(hipStreamSynchronize(e->stream), "upload tip table"))      // (the sources are local)
-    return false;
+  if (!tip_pointer_tables(e, tt.clv, tt.codes)) return false;
   tt.view.code_rows = tt.codes.p;
   tt.view.code_base = nullptr;
   tt.view.code_stride = 0;
@@ -130,26 +97,24 @@ bool tip_tables(Engine * e, TipTables & tt)
 int add_tables(pll_partition_t * p, std::vector<u64> & tab, double & kernel_ms)
 {
   Engine * e = engine_of(p);
-  PLLHIP_TRY(hipSetDevice(e->device));
-  if (!upload_tipmap(p)) return PLL_FAILURE;
+  DeviceJob j;
+  if (!j.enter(e->device, e->stream) || !upload_tipmap(p)) return PLL_FAILURE;
   TipTables tt;
-  DevBuf<u64> d_tab;
-  EventPair ev;
+  u64 * d_tab = j.alloc<u64>(MST_WORDS, "statistics tables");
+  hipEvent_t a = j.event(), b = j.event();
   std::vector<u64> h_tab(MST_WORDS);
-  if (!tip_tables(e, tt) || !d_tab.alloc(MST_WORDS, "statistics tables") || !ev.create() ||
-      !clear_tables(d_tab.p, e->stream))
-    return PLL_FAILURE;
-  PLLHIP_TRY(hipEventRecord(ev.a, e->stream));
+  if (!tip_tables(e, tt) || !d_tab || !a || !b || !clear_tables(d_tab, e->stream)) return PLL_FAILURE;
+  PLLHIP_TRY(hipEventRecord(a, e->stream));
   if (e->coded_tips)
-    launch_tables<true>(e->stream, tt.view, e->d_tipmap, e->d_weights, e->tips, e->Nreal, e->S, d_tab.p, nullptr, nullptr);
+    launch_tables<true>(e->stream, tt.view, e->d_tipmap, e->d_weights, e->tips, e->Nreal, e->S, d_tab, nullptr, nullptr);
   else
-    launch_tables<false>(e->stream, tt.view, nullptr, e->d_weights, e->tips, e->Nreal, e->S, d_tab.p, nullptr, nullptr);
+    launch_tables<false>(e->stream, tt.view, nullptr, e->d_weights, e->tips, e->Nreal, e->S, d_tab, nullptr, nullptr);
   PLLHIP_TRY(hipGetLastError());
-  PLLHIP_TRY(hipEventRecord(ev.b, e->stream));
-  PLLHIP_TRY(hipMemcpyAsync(h_tab.data(), d_tab.p, MST_WORDS * sizeof(u64), hipMemcpyDeviceToHost, e->stream));
-  PLLHIP_TRY(hipStreamSynchronize(e->stream));
+  PLLHIP_TRY(hipEventRecord(b, e->stream));
   float ms = 0.f;
-  PLLHIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+  if (!j.download(h_tab.data(), d_tab, MST_WORDS, "download tables") ||
+      !hip_ok(hipStreamSynchronize(e->stream), "statistics kernel") || !j.elapsed(a, b, &ms))
+    return PLL_FAILURE;
   kernel_ms += ms;
   for (unsigned i = 1; i < MST_WORDS; ++i) tab[i] += h_tab[i];
   return PLL_SUCCESS;
@@ -159,24 +124,24 @@ int add_tables(pll_partition_t * p, std::vector<u64> & tab, double & kernel_ms)
 int add_vecfreq(pll_partition_t * p, std::vector<double> & fsum, double & kernel_ms)
 {
   Engine * e = engine_of(p);
-  PLLHIP_TRY(hipSetDevice(e->device));
   const unsigned kp = vecfreq_lanes(e->S), per_block = MST_WG / kp;
   const unsigned grid = std::max(1u, std::min((e->Nreal + per_block - 1) / per_block, VECFREQ_MAX_GRID));
+  DeviceJob j;
+  if (!j.enter(e->device, e->stream)) return PLL_FAILURE;
   TipTables tt;
-  DevBuf<double> d_partial;
-  EventPair ev;
   std::vector<double> h_partial((size_t)grid * e->S);
-  if (!tip_tables(e, tt) || !d_partial.alloc(h_partial.size(), "frequency partials") || !ev.create()) return PLL_FAILURE;
-  PLLHIP_TRY(hipEventRecord(ev.a, e->stream));
+  double * d_partial = j.alloc<double>(h_partial.size(), "frequency partials");
+  hipEvent_t a = j.event(), b = j.event();
+  if (!tip_tables(e, tt) || !d_partial || !a || !b) return PLL_FAILURE;
+  PLLHIP_TRY(hipEventRecord(a, e->stream));
   hipLaunchKernelGGL(k_mst_vecfreq, dim3(grid), dim3(MST_WG), 0, e->stream, tt.view, (const unsigned *)e->d_weights,
-                     e->tips, e->Nreal, e->S, kp, d_partial.p);
+                     e->tips, e->Nreal, e->S, kp, d_partial);
   PLLHIP_TRY(hipGetLastError());
-  PLLHIP_TRY(hipEventRecord(ev.b, e->stream));
-  PLLHIP_TRY(hipMemcpyAsync(h_partial.data(), d_partial.p, h_partial.size() * sizeof(double), hipMemcpyDeviceToHost,
-                            e->stream));
-  PLLHIP_TRY(hipStreamSynchronize(e->stream));
+  PLLHIP_TRY(hipEventRecord(b, e->stream));
   float ms = 0.f;
-  PLLHIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+  if (!j.download(h_partial.data(), d_partial, h_partial.size(), "download partials") ||
+      !hip_ok(hipStreamSynchronize(e->stream), "frequency kernel") || !j.elapsed(a, b, &ms))
+    return PLL_FAILURE;
   kernel_ms += ms;
   for (unsigned b = 0; b < grid; ++b)
     for (unsigned k = 0; k < e->S; ++k) fsum[k] += h_partial[(size_t)b * e->S + k];
@@ -202,14 +167,11 @@ bool check_partition(const pll_partition_t * p, const char * who)
 int partition_tables(pll_partition_t * p, std::vector<u64> & tab)
 {
   Engine * e = engine_of(p);
-  int saved = -1;
-  PLLHIP_TRY(hipGetDevice(&saved));
   double ms = 0.0;
   int rc = PLL_SUCCESS;
   if (e->shards.empty()) rc = add_tables(p, tab, ms);
   else
     for (size_t k = 0; rc && k < e->shards.size(); ++k) rc = add_tables(e->shards[k], tab, ms);
-  (void)hipSetDevice(saved);
   if (rc) { g_last_ms[0] = 0.0; g_last_ms[1] = ms; }
   return rc;
 }
@@ -217,14 +179,11 @@ int partition_tables(pll_partition_t * p, std::vector<u64> & tab)
 int partition_vecfreq(pll_partition_t * p, std::vector<double> & fsum)
 {
   Engine * e = engine_of(p);
-  int saved = -1;
-  PLLHIP_TRY(hipGetDevice(&saved));
   double ms = 0.0;
   int rc = PLL_SUCCESS;
   if (e->shards.empty()) rc = add_vecfreq(p, fsum, ms);
   else
     for (size_t k = 0; rc && k < e->shards.size(); ++k) rc = add_vecfreq(e->shards[k], fsum, ms);
-  (void)hipSetDevice(saved);
   if (rc) g_last_ms[1] += ms;
   return rc;
 }
@@ -295,108 +254,49 @@ bool find_duplicates(char ** strings, size_t count, size_t length, unsigned long
   return true;
 }
 
-struct StatsJob
-{
-  int saved_device = -1;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};             // start, uploaded, computed
-  hipEvent_t half_free[2] = {nullptr, nullptr};
-  uint8_t * h_stage = nullptr;
-  uint8_t * d_in = nullptr, * d_flags = nullptr;
-  u64 * d_map = nullptr, * d_tab = nullptr, * d_seq_gap = nullptr;
-  unsigned * d_weights = nullptr;
-
-  ~StatsJob()
-  {
-    if (stream) (void)hipStreamSynchronize(stream);
-    (void)hipFree(d_in); (void)hipFree(d_flags); (void)hipFree(d_map); (void)hipFree(d_tab); (void)hipFree(d_seq_gap);
-    (void)hipFree(d_weights);
-    if (h_stage) (void)hipHostFree(h_stage);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : half_free) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (saved_device >= 0) (void)hipSetDevice(saved_device);
-  }
-};
-
-template <typename T>
-bool job_alloc(T ** ptr, size_t count, const char * what)
-{
-  *ptr = nullptr;
-  const hipError_t err = hipMalloc(reinterpret_cast<void **>(ptr), (count ? count : 1) * sizeof(T));
-  if (err == hipSuccess) return true;
-  *ptr = nullptr;
-  (void)hipGetLastError();
-  set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s", (count ? count : 1) * sizeof(T), what,
-            hipGetErrorString(err));
-  return false;
-}
-
 // the device part of the alignment form: tab[MST_WORDS], flags[L], seq_gap[T]
 // (want_flags / want_seq_gap: only a mask that asks for them pays for the per-site flags and the per-sequence sums)
 bool alignment_tables(const pll_msa_t * msa, unsigned states, const pll_state_t * tipmap, const unsigned * weights,
                       bool want_flags, bool want_seq_gap, std::vector<u64> & tab, std::vector<uint8_t> & flags,
                       std::vector<u64> & seq_gap)
 {
-  const int device = pllhip_get_device();
-  if (device < 0 || device >= pllhip_device_count())
-  {
-    set_error(PLL_ERROR_HIP_NODEVICE, "pllhip_msa_compute_stats runs on HIP device %d; %d visible", device,
-              pllhip_device_count());
-    return false;
-  }
+  int device = -1;
+  if (!caller_device("pllhip_msa_compute_stats", &device)) return false;
   const unsigned T = (unsigned)msa->count, L = (unsigned)msa->length;
   const size_t Lp = ((size_t)L + 255u) & ~(size_t)255u;
   const size_t half = std::min(STATS_STAGE_BYTES, (size_t)T * Lp);
-  StatsJob j;
-  if (!hip_ok(hipGetDevice(&j.saved_device), "hipGetDevice") || !hip_ok(hipSetDevice(device), "hipSetDevice") ||
-      !hip_ok(hipStreamCreateWithFlags(&j.stream, hipStreamNonBlocking), "hipStreamCreate"))
+  DeviceJob j;
+  MsaStager stager;
+  if (!j.enter(device)) return false;
+  hipEvent_t ev[3];                                           // start, uploaded, computed
+  for (hipEvent_t & e : ev) if (!(e = j.event())) return false;
+  uint8_t * d_in = j.alloc<uint8_t>((size_t)T * Lp, "the alignment");
+  uint8_t * d_flags = j.alloc<uint8_t>((size_t)L, "column flags");
+  u64 * d_map = j.alloc<u64>(256, "the character map");
+  u64 * d_tab = j.alloc<u64>(MST_WORDS, "statistics tables");
+  u64 * d_seq_gap = j.alloc<u64>((size_t)T, "sequence gap weights");
+  unsigned * d_weights = weights ? j.alloc<unsigned>((size_t)L, "column weights") : nullptr;
+  if (!d_in || !d_flags || !d_map || !d_tab || !d_seq_gap || (weights && !d_weights) || !stager.open(half)) return false;
+  if (!hip_ok(hipEventRecord(ev[0], j.stream), "hipEventRecord") ||
+      !stager.rows(j.stream, d_in, msa->sequence, T, L, Lp, half) ||
+      !j.upload(d_map, (const u64 *)tipmap, 256, "upload map") ||
+      (weights && !j.upload(d_weights, weights, (size_t)L, "upload weights")) || !clear_tables(d_tab, j.stream) ||
+      !hip_ok(hipMemsetAsync(d_seq_gap, 0, (size_t)T * sizeof(u64), j.stream), "memset gap weights") ||
+      !hip_ok(hipEventRecord(ev[1], j.stream), "hipEventRecord"))
     return false;
-  for (hipEvent_t & e : j.ev) if (!hip_ok(hipEventCreate(&e), "hipEventCreate")) return false;
-  for (hipEvent_t & e : j.half_free)
-    if (!hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) return false;
-  if (!job_alloc(&j.d_in, (size_t)T * Lp, "the alignment") || !job_alloc(&j.d_flags, (size_t)L, "column flags") ||
-      !job_alloc(&j.d_map, 256, "the character map") || !job_alloc(&j.d_tab, MST_WORDS, "statistics tables") ||
-      !job_alloc(&j.d_seq_gap, (size_t)T, "sequence gap weights") ||
-      (weights && !job_alloc(&j.d_weights, (size_t)L, "column weights")))
-    return false;
-  const hipError_t herr = hipHostMalloc(reinterpret_cast<void **>(&j.h_stage), 2u * half);
-  if (herr != hipSuccess)
-  {
-    (void)hipGetLastError();
-    j.h_stage = nullptr;
-    set_error(PLL_ERROR_MEM_ALLOC, "hipHostMalloc of the staging buffer (%zu bytes) failed: %s", 2u * half,
-              hipGetErrorString(herr));
-    return false;
-  }
-  if (!hip_ok(hipEventRecord(j.ev[0], j.stream), "hipEventRecord") ||
-      !upload_rows(j, msa->sequence, T, L, Lp, half) ||
-      !hip_ok(hipMemcpyAsync(j.d_map, tipmap, 256 * sizeof(u64), hipMemcpyHostToDevice, j.stream), "upload map") ||
-      (weights && !hip_ok(hipMemcpyAsync(j.d_weights, weights, (size_t)L * sizeof(unsigned), hipMemcpyHostToDevice,
-                                         j.stream), "upload weights")) ||
-      !clear_tables(j.d_tab, j.stream) ||
-      !hip_ok(hipMemsetAsync(j.d_seq_gap, 0, (size_t)T * sizeof(u64), j.stream), "memset gap weights") ||
-      !hip_ok(hipEventRecord(j.ev[1], j.stream), "hipEventRecord"))
-    return false;
-  MstTips tp = {};
-  tp.code_base = j.d_in;
+  TipView tp = {};
+  tp.code_base = d_in;
   tp.code_stride = Lp;
-  launch_tables<true>(j.stream, tp, j.d_map, j.d_weights, T, L, states, j.d_tab, want_flags ? j.d_flags : nullptr,
-                      want_seq_gap ? j.d_seq_gap : nullptr);
-  if (!hip_ok(hipGetLastError(), "statistics kernel") || !hip_ok(hipEventRecord(j.ev[2], j.stream), "hipEventRecord") ||
-      !hip_ok(hipMemcpyAsync(tab.data(), j.d_tab, MST_WORDS * sizeof(u64), hipMemcpyDeviceToHost, j.stream),
-              "download tables") ||
-      (want_flags &&
-       !hip_ok(hipMemcpyAsync(flags.data(), j.d_flags, (size_t)L, hipMemcpyDeviceToHost, j.stream), "download flags")) ||
-      (want_seq_gap &&
-       !hip_ok(hipMemcpyAsync(seq_gap.data(), j.d_seq_gap, (size_t)T * sizeof(u64), hipMemcpyDeviceToHost, j.stream),
-               "download gap weights")) ||
+  launch_tables<true>(j.stream, tp, d_map, d_weights, T, L, states, d_tab, want_flags ? d_flags : nullptr,
+                      want_seq_gap ? d_seq_gap : nullptr);
+  if (!hip_ok(hipGetLastError(), "statistics kernel") || !hip_ok(hipEventRecord(ev[2], j.stream), "hipEventRecord") ||
+      !j.download(tab.data(), d_tab, MST_WORDS, "download tables") ||
+      (want_flags && !j.download(flags.data(), d_flags, (size_t)L, "download flags")) ||
+      (want_seq_gap && !j.download(seq_gap.data(), d_seq_gap, (size_t)T, "download gap weights")) ||
       !hip_ok(hipStreamSynchronize(j.stream), "statistics kernel"))
     return false;
   float up = 0.f, kern = 0.f;
-  if (!hip_ok(hipEventElapsedTime(&up, j.ev[0], j.ev[1]), "hipEventElapsedTime") ||
-      !hip_ok(hipEventElapsedTime(&kern, j.ev[1], j.ev[2]), "hipEventElapsedTime"))
-    return false;
+  if (!j.elapsed(ev[0], ev[1], &up) || !j.elapsed(ev[1], ev[2], &kern)) return false;
   g_last_ms[0] = up;
   g_last_ms[1] = kern;
   return true;

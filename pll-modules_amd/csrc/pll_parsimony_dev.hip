@@ -3,7 +3,7 @@
 //
 // A partition is one unit (its device, a stream of the object's own); a partition spread over devices by
 // pllhip_set_sharding is one unit per shard.  Shards hold disjoint sites, so their counts add up exactly.
-#include "engine.h"
+#include "device_job.hpp"
 #include "kernels_parsimony.hpp"
 #include "parsimony_dev.h"
 
@@ -61,18 +61,6 @@ static void unit_free(ParsUnit & u)
   u = ParsUnit();
 }
 
-template <typename T>
-static bool pars_alloc(T ** ptr, size_t count, const char * what)
-{
-  *ptr = nullptr;
-  const hipError_t err = hipMalloc(reinterpret_cast<void **>(ptr), (count ? count : 1) * sizeof(T));
-  if (err == hipSuccess) return true;
-  *ptr = nullptr;
-  set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s", (count ? count : 1) * sizeof(T), what,
-            hipGetErrorString(err));
-  return false;
-}
-
 // one ordinary (non-router) partition: sites [0, p->sites) of it, weights from `weights`
 static bool unit_create(pllhip_pars_dev_t * d, ParsUnit & u, const pll_partition_t * p, const unsigned * weights)
 {
@@ -88,11 +76,11 @@ static bool unit_create(pllhip_pars_dev_t * d, ParsUnit & u, const pll_partition
   u.nplanes = 0;
   while (u.nplanes < 32 && (maxw >> u.nplanes)) ++u.nplanes;
   const size_t vec = vec_words(d, u);
-  if (!pars_alloc(&u.d_sets, (size_t)d->nodes * vec, "parsimony sets") ||
-      !pars_alloc(&u.d_up, (size_t)d->nodes * vec, "parsimony up-sets") ||
-      !pars_alloc(&u.d_planes, (size_t)std::max(1u, u.nplanes) * u.nw, "parsimony weights") ||
-      !pars_alloc(&u.d_ops, d->ops_cap, "parsimony schedule") ||
-      !pars_alloc(&u.d_out, d->out_cap, "parsimony costs"))
+  if (!dev_alloc(&u.d_sets, (size_t)d->nodes * vec, "parsimony sets") ||
+      !dev_alloc(&u.d_up, (size_t)d->nodes * vec, "parsimony up-sets") ||
+      !dev_alloc(&u.d_planes, (size_t)std::max(1u, u.nplanes) * u.nw, "parsimony weights") ||
+      !dev_alloc(&u.d_ops, d->ops_cap, "parsimony schedule") ||
+      !dev_alloc(&u.d_out, d->out_cap, "parsimony costs"))
     return false;
   if (!hip_ok(hipHostMalloc(reinterpret_cast<void **>(&u.h_out), d->out_cap * sizeof(unsigned long long)),
                "hipHostMalloc costs") ||
@@ -109,29 +97,22 @@ static bool unit_create(pllhip_pars_dev_t * d, ParsUnit & u, const pll_partition
     return false;
 
   // the tips, from the engine's device data (after whatever the engine's stream still has to upload)
-  unsigned long long * d_tipmap = nullptr;
-  if (e->coded_tips)
-  {
-    if (!pars_alloc(&d_tipmap, PLL_ASCII_SIZE, "parsimony code table")) return false;
-    if (!hip_ok(hipMemcpyAsync(d_tipmap, p->tipmap, PLL_ASCII_SIZE * sizeof(unsigned long long),
-                                hipMemcpyHostToDevice, u.stream), "upload code table"))
-    {
-      (void)hipFree(d_tipmap);
-      return false;
-    }
-  }
+  DevBuf<unsigned long long> d_tipmap;
+  if (e->coded_tips &&
+      (!d_tipmap.alloc(PLL_ASCII_SIZE, "parsimony code table") ||
+       !hip_ok(hipMemcpyAsync(d_tipmap.p, p->tipmap, PLL_ASCII_SIZE * sizeof(unsigned long long), hipMemcpyHostToDevice,
+                              u.stream), "upload code table")))
+    return false;
   bool ok = hip_ok(hipStreamSynchronize(e->stream), "engine stream");
   for (unsigned t = 0; ok && t < d->tips; ++t)
   {
     const bool coded = e->coded_tips;
     hipLaunchKernelGGL(k_pars_pack, dim3(u.nw / 2u), dim3(PARS_WG), 0, u.stream,
-                       coded ? nullptr : e->d_clv[t], coded ? e->d_codes[t] : nullptr, d_tipmap,
+                       coded ? nullptr : e->d_clv[t], coded ? e->d_codes[t] : nullptr, d_tipmap.p,
                        e->blocked ? 1u : 0u, e->R, e->Sp, e->rows, d->S, nreal, u.nw, u.d_sets + (size_t)t * vec);
     ok = hip_ok(hipGetLastError(), "k_pars_pack");
   }
-  ok = ok && hip_ok(hipStreamSynchronize(u.stream), "pack tips");
-  (void)hipFree(d_tipmap);
-  return ok;
+  return ok && hip_ok(hipStreamSynchronize(u.stream), "pack tips");
 }
 
 extern "C" pllhip_pars_dev_t * pllhip_pars_dev_create(const pll_partition_t * p)
@@ -153,8 +134,8 @@ extern "C" pllhip_pars_dev_t * pllhip_pars_dev_create(const pll_partition_t * p)
     set_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate parsimony state");
     return nullptr;
   }
-  int saved = 0;
-  (void)hipGetDevice(&saved);
+  DeviceScope scope;
+  (void)scope.save();
   d->S = p->states;
   d->tips = p->tips;
   d->nodes = std::max(p->tips, 2u * p->tips - 2u);
@@ -172,7 +153,6 @@ extern "C" pllhip_pars_dev_t * pllhip_pars_dev_create(const pll_partition_t * p)
       d->units.emplace_back();
       ok = unit_create(d, d->units.back(), e->shards[k], p->pattern_weights + e->shard_first[k]);
     }
-  (void)hipSetDevice(saved);
   if (!ok)
   {
     pllhip_pars_dev_destroy(d);
@@ -184,10 +164,9 @@ extern "C" pllhip_pars_dev_t * pllhip_pars_dev_create(const pll_partition_t * p)
 extern "C" void pllhip_pars_dev_destroy(pllhip_pars_dev_t * d)
 {
   if (!d) return;
-  int saved = 0;
-  (void)hipGetDevice(&saved);
+  DeviceScope scope;
+  (void)scope.save();
   for (ParsUnit & u : d->units) unit_free(u);
-  (void)hipSetDevice(saved);
   delete d;
 }
 
@@ -206,8 +185,8 @@ extern "C" int pllhip_pars_dev_launch(pllhip_pars_dev_t * d, const int * ops, un
       set_error(PLL_ERROR_PARAM_INVALID, "Parsimony schedule names node %d of %u", ops[i], d->nodes);
       return PLL_FAILURE;
     }
-  int saved = 0;
-  (void)hipGetDevice(&saved);
+  DeviceScope scope;
+  (void)scope.save();
   for (ParsUnit & u : d->units)
   {
     PLLHIP_TRY(hipSetDevice(u.device));
@@ -226,15 +205,14 @@ extern "C" int pllhip_pars_dev_launch(pllhip_pars_dev_t * d, const int * ops, un
                               u.stream));
     u.npre = npre;
   }
-  (void)hipSetDevice(saved);
   return PLL_SUCCESS;
 }
 
 extern "C" int pllhip_pars_dev_collect(pllhip_pars_dev_t * d, unsigned long long * edge_acc,
                                        unsigned long long * score_acc)
 {
-  int saved = 0;
-  (void)hipGetDevice(&saved);
+  DeviceScope scope;
+  (void)scope.save();
   for (ParsUnit & u : d->units)
   {
     PLLHIP_TRY(hipSetDevice(u.device));
@@ -243,7 +221,6 @@ extern "C" int pllhip_pars_dev_collect(pllhip_pars_dev_t * d, unsigned long long
       for (unsigned i = 0; i < u.npre; ++i) edge_acc[i] += u.h_out[i];
     if (score_acc) *score_acc += u.h_out[u.npre];
   }
-  (void)hipSetDevice(saved);
   return PLL_SUCCESS;
 }
 
@@ -259,8 +236,8 @@ static bool unit_grow_io(pllhip_pars_dev_t * d, ParsUnit & u)
   if (u.h_out) (void)hipHostFree(u.h_out);
   if (u.h_ops) (void)hipHostFree(u.h_ops);
   u.d_ops = nullptr; u.d_out = nullptr; u.h_out = nullptr; u.h_ops = nullptr;
-  return pars_alloc(&u.d_ops, d->ops_cap, "parsimony schedule") &&
-         pars_alloc(&u.d_out, d->out_cap, "parsimony costs") &&
+  return dev_alloc(&u.d_ops, d->ops_cap, "parsimony schedule") &&
+         dev_alloc(&u.d_out, d->out_cap, "parsimony costs") &&
          hip_ok(hipHostMalloc(reinterpret_cast<void **>(&u.h_out), d->out_cap * sizeof(unsigned long long)),
                 "hipHostMalloc costs") &&
          hip_ok(hipHostMalloc(reinterpret_cast<void **>(&u.h_ops), d->ops_cap * sizeof(int)), "hipHostMalloc schedule");
@@ -276,8 +253,8 @@ extern "C" unsigned pllhip_pars_dev_spr_hint(const pllhip_pars_dev_t * d)
 extern "C" unsigned pllhip_pars_dev_spr_reserve(pllhip_pars_dev_t * d, unsigned want)
 {
   want = std::max(1u, std::min(want, PARS_SPR_MAX_BATCH));
-  int saved = 0;
-  (void)hipGetDevice(&saved);
+  DeviceScope scope;
+  (void)scope.save();
   unsigned batch = want;
   bool ok = true;
   for (ParsUnit & u : d->units)
@@ -293,7 +270,7 @@ extern "C" unsigned pllhip_pars_dev_spr_reserve(pllhip_pars_dev_t * d, unsigned 
     (void)hipFree(u.d_scr);
     u.d_scr = nullptr;
     u.spr_batch = 0;
-    ok = pars_alloc(&u.d_scr, (size_t)b * d->nodes * vec_words(d, u), "parsimony SPR scratch");
+    ok = dev_alloc(&u.d_scr, (size_t)b * d->nodes * vec_words(d, u), "parsimony SPR scratch");
     if (!ok) break;
     u.spr_batch = b;
     batch = std::min(batch, b);
@@ -312,7 +289,6 @@ extern "C" unsigned pllhip_pars_dev_spr_reserve(pllhip_pars_dev_t * d, unsigned 
       if (!ok) break;
     }
   }
-  (void)hipSetDevice(saved);
   return ok ? batch : 0u;
 }
 
@@ -353,8 +329,8 @@ extern "C" int pllhip_pars_dev_spr_launch(pllhip_pars_dev_t * d, const int * ops
     set_error(PLL_ERROR_PARAM_INVALID, "Parsimony SPR schedule out of range");
     return PLL_FAILURE;
   }
-  int saved = 0;
-  (void)hipGetDevice(&saved);
+  DeviceScope scope;
+  (void)scope.save();
   for (ParsUnit & u : d->units)
   {
     PLLHIP_TRY(hipSetDevice(u.device));
@@ -373,20 +349,18 @@ extern "C" int pllhip_pars_dev_spr_launch(pllhip_pars_dev_t * d, const int * ops
                               hipMemcpyDeviceToHost, u.stream));
     u.nout = nout;
   }
-  (void)hipSetDevice(saved);
   return PLL_SUCCESS;
 }
 
 extern "C" int pllhip_pars_dev_spr_collect(pllhip_pars_dev_t * d, unsigned long long * acc)
 {
-  int saved = 0;
-  (void)hipGetDevice(&saved);
+  DeviceScope scope;
+  (void)scope.save();
   for (ParsUnit & u : d->units)
   {
     PLLHIP_TRY(hipSetDevice(u.device));
     PLLHIP_TRY(hipStreamSynchronize(u.stream));
     for (unsigned i = 0; i < u.nout; ++i) acc[i] += u.h_out[i];
   }
-  (void)hipSetDevice(saved);
   return PLL_SUCCESS;
 }

@@ -6,7 +6,7 @@
 // per-site buffer of an edge log-likelihood (loglikelihood_impl, persite_dev): that copy runs on the engine's stream
 // and the set's stream is ordered after it with an event.  pllhip_sitelh_rell works through the replicates in batches
 // that bound the memory of the counts; nothing it computes depends on the batch.
-#include "engine.h"
+#include "device_job.hpp"
 #include "kernels_rell.hpp"
 #include "pllhip.h"
 
@@ -32,55 +32,6 @@ constexpr size_t WEIGHTS_STAGE_BYTES = (size_t)256 << 20;
 thread_local double g_last_ms[3] = {0.0, 0.0, 0.0};      // draw, product, statistics of the last call
 
 size_t pad16(size_t n) { return (n + RELL_TILE - 1) / RELL_TILE * RELL_TILE; }
-
-template <typename T> struct DevBuf
-{
-  T * p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  bool alloc(size_t count, const char * what)
-  {
-    const hipError_t err = hipMalloc(reinterpret_cast<void **>(&p), (count ? count : 1) * sizeof(T));
-    if (err == hipSuccess) return true;
-    p = nullptr;
-    (void)hipGetLastError();
-    set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s", (count ? count : 1) * sizeof(T), what,
-              hipGetErrorString(err));
-    return false;
-  }
-};
-
-// the calling thread's device, put back when the call returns
-struct DeviceScope
-{
-  int saved = -1;
-  bool enter(int device)
-  {
-    return hip_ok(hipGetDevice(&saved), "hipGetDevice") && hip_ok(hipSetDevice(device), "hipSetDevice");
-  }
-  ~DeviceScope() { if (saved >= 0) (void)hipSetDevice(saved); }
-};
-
-struct Events
-{
-  std::vector<hipEvent_t> ev;
-  ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-  // a new event, recorded on `stream`; nullptr on failure
-  hipEvent_t mark(hipStream_t stream)
-  {
-    hipEvent_t e = nullptr;
-    if (!hip_ok(hipEventCreate(&e), "hipEventCreate")) return nullptr;
-    ev.push_back(e);
-    return hip_ok(hipEventRecord(e, stream), "hipEventRecord") ? e : nullptr;
-  }
-};
-
-bool current_device(const char * who, int * device)
-{
-  *device = pllhip_get_device();
-  if (*device >= 0 && *device < pllhip_device_count()) return true;
-  set_error(PLL_ERROR_HIP_NODEVICE, "%s runs on HIP device %d; %d visible", who, *device, pllhip_device_count());
-  return false;
-}
 
 // what the draw kernel searches; all empty for unit weights, where a site is its pattern
 struct DrawTable
@@ -174,26 +125,17 @@ bool ensure_rows(pllhip_sitelh_t * set, unsigned rows)
 {
   if (rows <= set->cap) return true;
   const unsigned cap = (unsigned)pad16(std::max(rows, 2 * set->cap));
-  double * d_new = nullptr;
+  DevBuf<double> d_new;
   const size_t bytes = (size_t)cap * set->Sp * sizeof(double);
-  const hipError_t err = hipMalloc(reinterpret_cast<void **>(&d_new), bytes);
-  if (err != hipSuccess)
-  {
-    (void)hipGetLastError();
-    set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for site likelihoods failed: %s", bytes, hipGetErrorString(err));
-    return false;
-  }
+  if (!d_new.alloc((size_t)cap * set->Sp, "site likelihoods")) return false;
   const size_t used = (size_t)set->cap * set->Sp * sizeof(double);
   // (every device-to-device row copy so far precedes this on the set's stream: pllhip_sitelh_add_edge)
-  if (!hip_ok(hipMemsetAsync(reinterpret_cast<char *>(d_new) + used, 0, bytes - used, set->stream), "memset rows") ||
-      (used && !hip_ok(hipMemcpyAsync(d_new, set->d_L, used, hipMemcpyDeviceToDevice, set->stream), "copy rows")) ||
+  if (!hip_ok(hipMemsetAsync(reinterpret_cast<char *>(d_new.p) + used, 0, bytes - used, set->stream), "memset rows") ||
+      (used && !hip_ok(hipMemcpyAsync(d_new.p, set->d_L, used, hipMemcpyDeviceToDevice, set->stream), "copy rows")) ||
       !hip_ok(hipStreamSynchronize(set->stream), "copy rows"))
-  {
-    (void)hipFree(d_new);
     return false;
-  }
   (void)hipFree(set->d_L);
-  set->d_L = d_new;
+  set->d_L = d_new.release();
   set->cap = cap;
   return true;
 }
@@ -254,7 +196,8 @@ bool rell_run(pllhip_sitelh_t * set, const pllhip_rell_params_t * params, pllhip
   const unsigned T = set->count, B = params->replicates, S = set->S;
   const size_t Sp = set->Sp;
   hipStream_t st = set->stream;
-  if (!scan_rows(set)) return false;
+  DeviceJob j;                                   // the set's device and stream; the events of the clocks
+  if (!j.enter(set->device, st) || !scan_rows(set)) return false;
   unsigned batch = params->batch ? (unsigned)std::min<size_t>({pad16(params->batch), RELL_MAX_BATCH, pad16(B)})
                                  : default_batch(set, B);
   res->batch = batch;
@@ -279,17 +222,16 @@ bool rell_run(pllhip_sitelh_t * set, const pllhip_rell_params_t * params, pllhip
   for (unsigned t = 1; t < T; ++t) if (res->lnl[t] > res->lnl[best]) best = t;
   res->best = best;
 
-  Events ev;
   std::vector<hipEvent_t> marks;
   for (unsigned first = 0; first < B; first += batch)
   {
     const unsigned nb = std::min(batch, B - first);
-    marks.push_back(ev.mark(st));
+    marks.push_back(j.mark());
     if (!marks.back() || !draw_batch(st, set->d_cum, set->d_first, set->shift, Sp, set->N, params->seed, first, nb, d_C.p)) return false;
-    marks.push_back(ev.mark(st));
+    marks.push_back(j.mark());
     if (!marks.back() || !replicate_sums(set, d_C.p, nb, d_P.p, d_R.p + (size_t)first * T)) return false;
   }
-  hipEvent_t stats_begin = ev.mark(st);
+  hipEvent_t stats_begin = j.mark();
   if (!stats_begin || !hip_ok(hipMemsetAsync(d_cnt.p, 0, (size_t)3 * T * sizeof(unsigned), st), "memset counts")) return false;
   hipLaunchKernelGGL(k_rell_colmean, dim3(T), dim3(RELL_WG), 0, st, (const double *)d_R.p, B, T, -1, d_meanR);
   hipLaunchKernelGGL(k_rell_colmean, dim3(T), dim3(RELL_WG), 0, st, (const double *)d_R.p, B, T, (int)best, d_meanD);
@@ -298,7 +240,7 @@ bool rell_run(pllhip_sitelh_t * set, const pllhip_rell_params_t * params, pllhip
                      (const double *)d_meanD, d_cnt.p, d_cnt.p + T, d_cnt.p + 2 * T, d_E.p);
   hipLaunchKernelGGL(k_rell_colmean, dim3(T), dim3(RELL_WG), 0, st, (const double *)d_E.p, B, T, -1, d_elw);
   if (!hip_ok(hipGetLastError(), "statistics kernels")) return false;
-  hipEvent_t stats_end = ev.mark(st);
+  hipEvent_t stats_end = j.mark();
   if (!stats_end ||
       !hip_ok(hipMemcpyAsync(res->bp_count, d_cnt.p, T * sizeof(unsigned), hipMemcpyDeviceToHost, st), "download counts") ||
       !hip_ok(hipMemcpyAsync(res->kh_count, d_cnt.p + T, T * sizeof(unsigned), hipMemcpyDeviceToHost, st), "download counts") ||
@@ -314,10 +256,10 @@ bool rell_run(pllhip_sitelh_t * set, const pllhip_rell_params_t * params, pllhip
   for (size_t k = 0; k < marks.size(); ++k)
   {
     hipEvent_t next = k + 1 < marks.size() ? marks[k + 1] : stats_begin;
-    if (!hip_ok(hipEventElapsedTime(&f, marks[k], next), "hipEventElapsedTime")) return false;
+    if (!j.elapsed(marks[k], next, &f)) return false;
     ms[k & 1] += f;
   }
-  if (!hip_ok(hipEventElapsedTime(&f, stats_begin, stats_end), "hipEventElapsedTime")) return false;
+  if (!j.elapsed(stats_begin, stats_end, &f)) return false;
   ms[2] = f;
   for (int k = 0; k < 3; ++k) g_last_ms[k] = ms[k];
   return true;
@@ -338,7 +280,7 @@ PLL_EXPORT pllhip_sitelh_t * pllhip_sitelh_create(unsigned int patterns, const u
   const std::vector<u64> & cum = table.cum;
   u64 N = 0;
   int device = -1;
-  if (!prefix_sums("pllhip_sitelh_create", weights, patterns, table, &N) || !current_device("pllhip_sitelh_create", &device))
+  if (!prefix_sums("pllhip_sitelh_create", weights, patterns, table, &N) || !caller_device("pllhip_sitelh_create", &device))
     return nullptr;
   DeviceScope scope;
   if (!scope.enter(device)) return nullptr;
@@ -368,13 +310,10 @@ PLL_EXPORT pllhip_sitelh_t * pllhip_sitelh_create(unsigned int patterns, const u
     pllhip_sitelh_destroy(set);
     return nullptr;
   }
-  set->d_w = d_w.p;
-  set->d_cum = d_cum.p;
-  set->d_first = d_first.p;
+  set->d_w = d_w.release();
+  set->d_cum = d_cum.release();
+  set->d_first = d_first.release();
   set->shift = table.shift;
-  d_w.p = nullptr;
-  d_cum.p = nullptr;
-  d_first.p = nullptr;
   return set;
 }
 
@@ -533,8 +472,7 @@ PLL_EXPORT pllhip_rell_result_t * pllhip_sitelh_rell(pllhip_sitelh_t * set, cons
     set_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate memory for the resampling result");
     return nullptr;
   }
-  DeviceScope scope;
-  if (!scope.enter(set->device) || !rell_run(set, params, res))
+  if (!rell_run(set, params, res))
   {
     pllhip_rell_destroy(res);
     return nullptr;
@@ -562,39 +500,32 @@ PLL_EXPORT int pllhip_bootstrap_weights(const unsigned int * weights, unsigned i
   u64 N = 0;
   int device = -1;
   if (!prefix_sums("pllhip_bootstrap_weights", weights, patterns, table, &N) ||
-      !current_device("pllhip_bootstrap_weights", &device))
+      !caller_device("pllhip_bootstrap_weights", &device))
     return PLL_FAILURE;
   if (!count) return PLL_SUCCESS;
-  DeviceScope scope;
-  if (!scope.enter(device)) return PLL_FAILURE;
   const size_t Sp = pad16(patterns);
   const unsigned batch = (unsigned)std::max<size_t>(
       1, std::min<size_t>({count, RELL_MAX_BATCH, WEIGHTS_STAGE_BYTES / (Sp * sizeof(unsigned))}));
-  struct Stream
-  {
-    hipStream_t s = nullptr;
-    ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
-  } stream;
+  DeviceJob j;
   DevBuf<unsigned> d_C, d_first;
   DevBuf<u64> d_cum;
-  PLLHIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
-  if (!d_C.alloc(pad16(batch) * Sp, "replicate counts") ||
+  if (!j.enter(device) || !d_C.alloc(pad16(batch) * Sp, "replicate counts") ||
       (!cum.empty() && (!d_cum.alloc(patterns, "weight prefix sums") || !d_first.alloc(table.first.size(), "draw buckets"))))
     return PLL_FAILURE;
   if (!cum.empty())
   {
-    PLLHIP_TRY(hipMemcpyAsync(d_cum.p, cum.data(), (size_t)patterns * sizeof(u64), hipMemcpyHostToDevice, stream.s));
+    PLLHIP_TRY(hipMemcpyAsync(d_cum.p, cum.data(), (size_t)patterns * sizeof(u64), hipMemcpyHostToDevice, j.stream));
     PLLHIP_TRY(hipMemcpyAsync(d_first.p, table.first.data(), table.first.size() * sizeof(unsigned), hipMemcpyHostToDevice,
-                              stream.s));
+                              j.stream));
   }
   for (unsigned done = 0; done < count; done += batch)
   {
     const unsigned nb = std::min(batch, count - done);
-    if (!draw_batch(stream.s, d_cum.p, d_first.p, table.shift, Sp, N, seed, first + done, nb, d_C.p)) return PLL_FAILURE;
+    if (!draw_batch(j.stream, d_cum.p, d_first.p, table.shift, Sp, N, seed, first + done, nb, d_C.p)) return PLL_FAILURE;
     PLLHIP_TRY(hipMemcpy2DAsync(out + (size_t)done * patterns, (size_t)patterns * sizeof(unsigned), d_C.p,
                                 Sp * sizeof(unsigned), (size_t)patterns * sizeof(unsigned), nb, hipMemcpyDeviceToHost,
-                                stream.s));
-    PLLHIP_TRY(hipStreamSynchronize(stream.s));
+                                j.stream));
+    PLLHIP_TRY(hipStreamSynchronize(j.stream));
   }
   return PLL_SUCCESS;
 }

@@ -7,7 +7,7 @@
 // device holds a cache of them: the programs, the distinct splits' bit vectors, the hash table over those and every
 // tree's sorted split ids.  A query first brings the cache up to date, batch by batch, on a stream of its own; a
 // query that fails drops the cache, so the set is as it was and the next query builds it again.
-#include "engine.h"
+#include "device_job.hpp"
 #include "kernels_treeset.hpp"
 #include "pllhip.h"
 
@@ -53,44 +53,17 @@ void drop_cache(pllhip_treeset * ts)
 {
   if (ts->device >= 0)
   {
-    int saved = -1;
-    (void)hipGetDevice(&saved);
-    (void)hipSetDevice(ts->device);
+    DeviceScope scope;
+    (void)scope.enter(ts->device);
     (void)hipFree(ts->d_program); (void)hipFree(ts->d_ids); (void)hipFree(ts->d_table); (void)hipFree(ts->d_store);
     (void)hipFree(ts->d_trees_with); (void)hipFree(ts->d_scalars);
-    if (saved >= 0) (void)hipSetDevice(saved);
   }
   ts->d_program = nullptr; ts->d_ids = nullptr; ts->d_table = nullptr; ts->d_store = nullptr;
   ts->d_trees_with = nullptr; ts->d_scalars = nullptr;
   ts->device = -1; ts->ingested = ts->capacity = ts->ndistinct = 0; ts->slots = ts->store_cap = 0;
 }
 
-template <typename T>
-bool dev_alloc(T ** ptr, size_t count, const char * what)
-{
-  *ptr = nullptr;
-  const hipError_t err = hipMalloc(reinterpret_cast<void **>(ptr), (count ? count : 1) * sizeof(T));
-  if (err == hipSuccess) return true;
-  *ptr = nullptr;
-  (void)hipGetLastError();
-  set_error(PLL_ERROR_MEM_ALLOC, "hipMalloc of %zu bytes for %s failed: %s", (count ? count : 1) * sizeof(T), what,
-            hipGetErrorString(err));
-  return false;
-}
-
-unsigned grid_for(size_t items, unsigned per_block)
-{
-  return (unsigned)std::max<size_t>(1, std::min<size_t>((items + per_block - 1) / per_block, 4096));
-}
-
-// PLLHIP_SPLIT_HASH_BITS=<0..64>: only that many bits of the hash are used (a test knob)
-unsigned long long hash_keep_mask()
-{
-  const char * env = getenv("PLLHIP_SPLIT_HASH_BITS");
-  if (!env || !*env) return ~0ULL;
-  const long bits = std::max(0L, std::min(64L, atol(env)));
-  return bits >= 64 ? ~0ULL : ((1ULL << bits) - 1ULL);
-}
+constexpr const char * SPLIT_HASH_BITS = "PLLHIP_SPLIT_HASH_BITS";      // hash_keep_mask: a test knob
 
 unsigned long long all_keys(unsigned T)
 {
@@ -100,42 +73,26 @@ unsigned long long all_keys(unsigned T)
 }
 
 // one query: the device, a stream, and the three clocks
-struct Job
+struct Job : DeviceJob
 {
-  int saved_device = -1;
-  hipStream_t stream = nullptr;
   hipEvent_t a = nullptr, b = nullptr;
   double ms[3] = {0.0, 0.0, 0.0};
-  std::vector<void *> temps;
 
   bool open(pllhip_treeset * ts)
   {
-    const int device = pllhip_get_device();
-    if (device < 0 || device >= pllhip_device_count())
-    {
-      set_error(PLL_ERROR_HIP_NODEVICE, "the tree set runs on HIP device %d; %d visible", device, pllhip_device_count());
-      return false;
-    }
+    int device = -1;
+    if (!caller_device("the tree set", &device)) return false;
     if (ts->device >= 0 && ts->device != device) drop_cache(ts);
-    if (!hip_ok(hipGetDevice(&saved_device), "hipGetDevice") || !hip_ok(hipSetDevice(device), "hipSetDevice") ||
-        !hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate") ||
-        !hip_ok(hipEventCreate(&a), "hipEventCreate") || !hip_ok(hipEventCreate(&b), "hipEventCreate"))
-      return false;
+    if (!enter(device) || !(a = event()) || !(b = event())) return false;
     ts->device = device;
     return true;
   }
-  template <typename T>
-  bool temp(T ** ptr, size_t count, const char * what)
-  {
-    if (!dev_alloc(ptr, count, what)) return false;
-    temps.push_back(*ptr);
-    return true;
-  }
+  // frees a buffer before the query ends
   void release(void * p)
   {
     if (stream) (void)hipStreamSynchronize(stream);
     (void)hipFree(p);
-    temps.erase(std::remove(temps.begin(), temps.end(), p), temps.end());
+    keep(p);
   }
   bool start() { return hip_ok(hipEventRecord(a, stream), "hipEventRecord"); }
   // ends a segment: the stream is idle afterwards
@@ -143,31 +100,26 @@ struct Job
   {
     float t = 0.f;
     if (!hip_ok(hipGetLastError(), what) || !hip_ok(hipEventRecord(b, stream), "hipEventRecord") ||
-        !hip_ok(hipEventSynchronize(b), what) || !hip_ok(hipEventElapsedTime(&t, a, b), "hipEventElapsedTime"))
+        !hip_ok(hipEventSynchronize(b), what) || !elapsed(a, b, &t))
       return false;
     ms[which] += t;
     return true;
   }
+  template <typename T> bool temp(T ** ptr, size_t count, const char * what)
+  {
+    return (*ptr = alloc<T>(count, what)) != nullptr;
+  }
   bool up(void * dst, const void * src, size_t bytes)
   {
-    return hip_ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream), "upload");
+    return upload(static_cast<char *>(dst), static_cast<const char *>(src), bytes, "upload");
   }
   bool down(void * dst, const void * src, size_t bytes)
   {
-    return hip_ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream), "download");
+    return download(static_cast<char *>(dst), static_cast<const char *>(src), bytes, "download");
   }
   void commit()
   {
     for (int k = 0; k < 3; ++k) g_last_ms[k] = ms[k];
-  }
-  ~Job()
-  {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (void * p : temps) (void)hipFree(p);
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (saved_device >= 0) (void)hipSetDevice(saved_device);
   }
 };
 
@@ -238,7 +190,7 @@ bool sync_cache(pllhip_treeset * ts, Job & j)
         !hip_ok(hipMemsetAsync(ts->d_scalars, 0, 3 * sizeof(unsigned long long), j.stream), "memset scalars"))
       return false;
   }
-  const unsigned long long keep = hash_keep_mask(), keys = all_keys(ts->T);
+  const unsigned long long keep = hash_keep_mask(SPLIT_HASH_BITS), keys = all_keys(ts->T);
   const unsigned slot_mask = (unsigned)(ts->slots - 1u);
   const unsigned batch = batch_size(ts, B - ts->ingested);
   const size_t nmax = (size_t)batch * R;
@@ -334,8 +286,9 @@ bool lookup_reference(pllhip_treeset * ts, Job & j, const Reference & ref, unsig
     return false;
   if (!j.start()) return false;
   hipLaunchKernelGGL(k_ts_lookup, dim3(grid_for(ts->R, TS_WG)), dim3(TS_WG), 0, j.stream, (const uint32_t *)d_vec,
-                     (const unsigned long long *)d_hash, (const uint32_t *)ts->d_store, ts->len, ts->R, hash_keep_mask(),
-                     (const unsigned long long *)ts->d_table, (unsigned)(ts->slots - 1u), *d_ref_id);
+                     (const unsigned long long *)d_hash, (const uint32_t *)ts->d_store, ts->len, ts->R,
+                     hash_keep_mask(SPLIT_HASH_BITS), (const unsigned long long *)ts->d_table, (unsigned)(ts->slots - 1u),
+                     *d_ref_id);
   return j.stop(1, "reference lookup");
 }
 
