@@ -684,6 +684,48 @@ PLL_EXPORT void pllhip_rell_last_times(double * draw_ms, double * product_ms, do
 PLL_EXPORT int pllhip_bootstrap_weights(const unsigned int * weights, unsigned int patterns, unsigned long long seed,
                                         unsigned int first, unsigned int count, unsigned int * out);
 
+/* The approximately unbiased (AU) test from multiscale bootstrap replicates ("Multiscale replicates
+   and the AU test").  Scale k draws n_k = floor(r_k N + 0.5) sites per replicate from a stream
+   of its own; bp_count[k][t] counts the replicates of scale k that tree t wins; per tree, z_k = -Phi^-1(bp_count / B)
+   is fitted by d sqrt(n_k / N) + c / sqrt(n_k / N) with weighted least squares over the scales with
+   0 < bp_count < B, and p_au = 1 - Phi(d - c).  With fewer than two such scales no fit is made: d = c = se = rss = 0
+   and p_au is the proportion of the scale whose n_k is nearest to N.  Every field is bit-identical across runs and
+   across `batch`. */
+#define PLLHIP_AU_REPLICATES (1u << 0)   /* also return R[scales][replicates][trees] */
+
+typedef struct pllhip_au_params
+{
+  unsigned int replicates;        /* B per scale, 1 .. 2^24 - 1 */
+  unsigned int scales;            /* K, 2 .. 64; ignored when scale == NULL (then 10) */
+  const double * scale;           /* r_k, or NULL: 0.5, 0.6, ... 1.4 */
+  unsigned long long seed;
+  unsigned int flags;
+  unsigned int batch;             /* rows (scale, replicate) per pass, as in pllhip_rell_params_t */
+} pllhip_au_params_t;
+
+typedef struct pllhip_au_result
+{
+  unsigned int trees, replicates, scales, best, batch;
+  double * lnl;                   /* [trees] */
+  unsigned long long * draws;     /* [scales]  n_k */
+  unsigned int * bp_count;        /* [scales][trees] */
+  double * p_au, * d, * c, * se, * rss;   /* [trees] */
+  unsigned int * used;            /* [trees]  scales with 0 < bp_count < B */
+  double * replicate_lnl;         /* [scales][replicates][trees] with PLLHIP_AU_REPLICATES, else NULL */
+} pllhip_au_result_t;
+
+PLL_EXPORT pllhip_au_result_t * pllhip_sitelh_au(pllhip_sitelh_t * set, const pllhip_au_params_t * params);
+PLL_EXPORT void pllhip_au_destroy(pllhip_au_result_t * result);
+/* the last pllhip_sitelh_au of this thread: device time of its stages in ms between HIP events (stats = proportions
+   and fit) */
+PLL_EXPORT void pllhip_au_last_times(double * draw_ms, double * product_ms, double * stats_ms);
+
+/* the count vectors of replicates first .. first + count - 1 of scale `scale_index` (< 64) with `draws` = n_k draws each,
+   for (weights, seed) -- the very vectors pllhip_sitelh_au uses -- as out[count][patterns] */
+PLL_EXPORT int pllhip_multiscale_weights(const unsigned int * weights, unsigned int patterns, unsigned long long seed,
+                                         unsigned int scale_index, unsigned long long draws,
+                                         unsigned int first, unsigned int count, unsigned int * out);
+
 /* ---- pairwise distances and neighbour joining ("Pairwise distances and neighbour joining";
  *      DESIGN.md section 23) ----
  * Every character becomes a code: its state where its mask has exactly one bit, "nothing" otherwise (gaps and

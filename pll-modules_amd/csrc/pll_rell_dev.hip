@@ -1,12 +1,13 @@
-// pll_rell_dev.hip -- site-likelihood sets, RELL resampling with the KH, SH and ELW statistics, and bootstrap
-// replicate weights (kernels_rell.hpp; contract: INTEGRATION.md, "Topology tests and bootstrap weights"; design:
-// DESIGN.md section 20).
+// pll_rell_dev.hip -- site-likelihood sets, RELL resampling with the KH, SH and ELW statistics, bootstrap replicate
+// weights (kernels_rell.hpp), and the AU test from multiscale replicates (kernels_au.hpp); contract: INTEGRATION.md,
+// "Topology tests and bootstrap weights"; design: DESIGN.md sections 20 and 25.
 //
 // A set lives on one device, with a stream of its own.  Rows arrive from the host or, device to device, from the
 // per-site buffer of an edge log-likelihood (loglikelihood_impl, persite_dev): that copy runs on the engine's stream
 // and the set's stream is ordered after it with an event.  pllhip_sitelh_rell works through the replicates in batches
 // that bound the memory of the counts; nothing it computes depends on the batch.
 #include "device_job.hpp"
+#include "kernels_au.hpp"
 #include "kernels_rell.hpp"
 #include "pllhip.h"
 
@@ -155,7 +156,7 @@ bool replicate_sums(const pllhip_sitelh_t * set, const unsigned * d_C, unsigned 
 }
 
 // a non-finite value in a row the device wrote: PLL_FAILURE, naming row and pattern
-bool scan_rows(pllhip_sitelh_t * set)
+bool scan_rows(pllhip_sitelh_t * set, const char * who)
 {
   if (!set->unscanned) return true;
   DevBuf<u64> d_bad;
@@ -171,11 +172,28 @@ bool scan_rows(pllhip_sitelh_t * set)
       !hip_ok(hipStreamSynchronize(set->stream), "scan kernel")) return false;
   if (bad != ~0ULL)
   {
-    set_error(PLL_ERROR_PARAM_INVALID, "pllhip_sitelh_rell: non-finite site log-likelihood in row %llu at pattern %llu",
+    set_error(PLL_ERROR_PARAM_INVALID, "%s: non-finite site log-likelihood in row %llu at pattern %llu", who,
               bad / set->S, bad % set->S);
     return false;
   }
   set->unscanned = false;
+  return true;
+}
+
+// the observed log-likelihoods, on the device and the host, and the best tree: the weights as the only replicate of a
+// batch of their own (d_C holds at least 16 rows)
+bool observed_lnl(const pllhip_sitelh_t * set, unsigned * d_C, double * d_P, double * d_lnl, double * lnl, unsigned * best)
+{
+  const size_t Sp = set->Sp;
+  hipStream_t st = set->stream;
+  if (!hip_ok(hipMemsetAsync(d_C, 0, RELL_TILE * Sp * sizeof(unsigned), st), "memset counts") ||
+      !hip_ok(hipMemcpyAsync(d_C, set->d_w, Sp * sizeof(unsigned), hipMemcpyDeviceToDevice, st), "copy weights") ||
+      !replicate_sums(set, d_C, 1, d_P, d_lnl) ||
+      !hip_ok(hipMemcpyAsync(lnl, d_lnl, set->count * sizeof(double), hipMemcpyDeviceToHost, st), "download lnl") ||
+      !hip_ok(hipStreamSynchronize(st), "observed log-likelihoods"))
+    return false;
+  *best = 0;
+  for (unsigned t = 1; t < set->count; ++t) if (lnl[t] > lnl[*best]) *best = t;
   return true;
 }
 
@@ -197,7 +215,7 @@ bool rell_run(pllhip_sitelh_t * set, const pllhip_rell_params_t * params, pllhip
   const size_t Sp = set->Sp;
   hipStream_t st = set->stream;
   DeviceJob j;                                   // the set's device and stream; the events of the clocks
-  if (!j.enter(set->device, st) || !scan_rows(set)) return false;
+  if (!j.enter(set->device, st) || !scan_rows(set, "pllhip_sitelh_rell")) return false;
   unsigned batch = params->batch ? (unsigned)std::min<size_t>({pad16(params->batch), RELL_MAX_BATCH, pad16(B)})
                                  : default_batch(set, B);
   res->batch = batch;
@@ -211,15 +229,8 @@ bool rell_run(pllhip_sitelh_t * set, const pllhip_rell_params_t * params, pllhip
     return false;
   double * d_lnl = d_vec.p, * d_meanR = d_vec.p + T, * d_meanD = d_vec.p + 2 * T, * d_elw = d_vec.p + 3 * T;
 
-  // the observed log-likelihoods: the weights as the only replicate of a batch of their own
-  if (!hip_ok(hipMemsetAsync(d_C.p, 0, RELL_TILE * Sp * sizeof(unsigned), st), "memset counts") ||
-      !hip_ok(hipMemcpyAsync(d_C.p, set->d_w, Sp * sizeof(unsigned), hipMemcpyDeviceToDevice, st), "copy weights") ||
-      !replicate_sums(set, d_C.p, 1, d_P.p, d_lnl) ||
-      !hip_ok(hipMemcpyAsync(res->lnl, d_lnl, T * sizeof(double), hipMemcpyDeviceToHost, st), "download lnl") ||
-      !hip_ok(hipStreamSynchronize(st), "observed log-likelihoods"))
-    return false;
   unsigned best = 0;
-  for (unsigned t = 1; t < T; ++t) if (res->lnl[t] > res->lnl[best]) best = t;
+  if (!observed_lnl(set, d_C.p, d_P.p, d_lnl, res->lnl, &best)) return false;
   res->best = best;
 
   std::vector<hipEvent_t> marks;
@@ -262,6 +273,156 @@ bool rell_run(pllhip_sitelh_t * set, const pllhip_rell_params_t * params, pllhip
   if (!j.elapsed(stats_begin, stats_end, &f)) return false;
   ms[2] = f;
   for (int k = 0; k < 3; ++k) g_last_ms[k] = ms[k];
+  return true;
+}
+
+// ---- the AU test: multiscale replicates (kernels_au.hpp) ----
+
+constexpr unsigned AU_MAX_SCALES = 64;
+const double AU_DEFAULT_SCALES[10] = {5 / 10.0, 6 / 10.0, 7 / 10.0, 8 / 10.0, 9 / 10.0, 10 / 10.0, 11 / 10.0, 12 / 10.0,
+                                      13 / 10.0, 14 / 10.0};
+
+thread_local double g_au_last_ms[3] = {0.0, 0.0, 0.0};   // draw, product, counts + fit of the last call
+
+// n_k = floor(r_k N + 0.5) of every scale; false with the error set: a scale that is not finite and positive, an n_k
+// outside 1 .. 2^40 - 1, or two scales of the same n_k
+bool au_draw_counts(const double * scale, unsigned K, u64 N, std::vector<u64> & n)
+{
+  n.assign(K, 0);
+  for (unsigned k = 0; k < K; ++k)
+  {
+    const double r = scale[k];
+    if (!std::isfinite(r) || r <= 0.0)
+    {
+      set_error(PLL_ERROR_PARAM_INVALID, "pllhip_sitelh_au: scale %u is %g (finite and positive values are supported)", k, r);
+      return false;
+    }
+    const double x = std::floor(r * (double)N + 0.5);
+    if (x < 1.0 || x >= (double)RELL_MAX_DRAWS)
+    {
+      set_error(PLL_ERROR_PARAM_INVALID, "pllhip_sitelh_au: scale %u (%g) of %llu sites draws %.0f (1 to 2^40 - 1 are supported)",
+                k, r, N, x);
+      return false;
+    }
+    n[k] = (u64)x;
+    for (unsigned i = 0; i < k; ++i)
+      if (n[i] == n[k])
+      {
+        set_error(PLL_ERROR_PARAM_INVALID, "pllhip_sitelh_au: scales %u and %u both draw %llu sites", i, k, n[k]);
+        return false;
+      }
+  }
+  return true;
+}
+
+// rows first .. first + nb - 1 of the K x B rows (scale-major) into rows[0 .. nb - 1]; returns the largest n among them
+u64 au_fill_rows(au_row * rows, u64 first, unsigned nb, unsigned B, const std::vector<u64> & seeds,
+                 const std::vector<u64> & n)
+{
+  u64 longest = 0;
+  for (unsigned i = 0; i < nb; ++i)
+  {
+    const unsigned k = (unsigned)((first + i) / B);
+    rows[i] = au_row{seeds[k], n[k], (unsigned)((first + i) % B), k};
+    longest = std::max(longest, n[k]);
+  }
+  return longest;
+}
+
+// counts of the nb rows the table describes into rows 0 .. nb - 1 of C (cleared here, pad16(nb) rows)
+bool au_draw_batch(hipStream_t stream, const u64 * d_cum, const unsigned * d_first, unsigned shift, size_t Sp, u64 N,
+                   const au_row * d_rows, unsigned nb, u64 longest, unsigned * d_C)
+{
+  if (!hip_ok(hipMemsetAsync(d_C, 0, pad16(nb) * Sp * sizeof(unsigned), stream), "memset counts")) return false;
+  const unsigned gx = (unsigned)std::min<u64>((longest + RELL_WG - 1) / RELL_WG, RELL_DRAW_MAX_GRID);
+  hipLaunchKernelGGL(k_au_draw, dim3(gx, nb), dim3(RELL_WG), 0, stream, d_cum, d_first, shift, Sp, N, d_rows, d_C);
+  return hip_ok(hipGetLastError(), "multiscale draw kernel");
+}
+
+bool au_run(pllhip_sitelh_t * set, const pllhip_au_params_t * params, const std::vector<u64> & n, pllhip_au_result_t * res)
+{
+  const unsigned T = set->count, B = params->replicates, K = res->scales, S = set->S;
+  const size_t Sp = set->Sp;
+  const u64 total = (u64)K * B;                  // rows of R, scale-major (< 2^30)
+  hipStream_t st = set->stream;
+  DeviceJob j;
+  if (!j.enter(set->device, st) || !scan_rows(set, "pllhip_sitelh_au")) return false;
+  const unsigned batch = params->batch ? (unsigned)std::min<u64>({pad16(params->batch), RELL_MAX_BATCH, pad16(total)})
+                                       : default_batch(set, (unsigned)total);
+  res->batch = batch;
+  const bool keep = params->flags & PLLHIP_AU_REPLICATES;
+  const unsigned chunk = rell_chunk_len(S), nchunks = (unsigned)((Sp + chunk - 1) / chunk);
+  unsigned * d_C = j.alloc<unsigned>((size_t)batch * Sp, "replicate counts");
+  double * d_P = j.alloc<double>((size_t)nchunks * batch * pad16(T), "chunk partials");
+  double * d_R = j.alloc<double>((keep ? total : batch) * T, "replicate log-likelihoods");
+  double * d_vec = j.alloc<double>((size_t)6 * T + K, "tree statistics");
+  unsigned * d_cnt = j.alloc<unsigned>((size_t)K * T + T, "proportion counts");
+  au_row * d_rows = j.alloc<au_row>(batch, "row table");
+  au_row * h_rows = j.pinned<au_row>(batch);
+  if (!d_C || !d_P || !d_R || !d_vec || !d_cnt || !d_rows || !h_rows) return false;
+  double * d_lnl = d_vec, * d_fit = d_vec + T, * d_rho = d_vec + 6 * T;
+  unsigned * d_bp = d_cnt, * d_used = d_cnt + (size_t)K * T;
+
+  if (!observed_lnl(set, d_C, d_P, d_lnl, res->lnl, &res->best)) return false;
+
+  std::vector<u64> seeds(K);
+  std::vector<double> rho(K);
+  unsigned kstar = 0;                            // the scale whose n_k is nearest to N, the lowest on ties
+  const u64 N = set->N;
+  auto gap = [N](u64 draws) { return draws > N ? draws - N : N - draws; };
+  for (unsigned k = 0; k < K; ++k)
+  {
+    seeds[k] = au_scale_seed(params->seed, k);
+    rho[k] = (double)n[k] / (double)N;
+    if (gap(n[k]) < gap(n[kstar])) kstar = k;
+  }
+  if (!j.upload(d_rho, rho.data(), K, "upload scales") ||
+      !hip_ok(hipMemsetAsync(d_bp, 0, (size_t)K * T * sizeof(unsigned), st), "memset proportions")) return false;
+
+  std::vector<hipEvent_t> marks;                 // per pass: draw, product, counts
+  for (u64 first = 0; first < total; first += batch)
+  {
+    const unsigned nb = (unsigned)std::min<u64>(batch, total - first);
+    // (the pinned table is free again: the pass before has read it)
+    if (first && !hip_ok(hipStreamSynchronize(st), "multiscale pass")) return false;
+    const u64 longest = au_fill_rows(h_rows, first, nb, B, seeds, n);
+    double * d_Rpass = keep ? d_R + first * T : d_R;
+    marks.push_back(j.mark());
+    if (!marks.back() || !j.upload(d_rows, h_rows, nb, "upload row table") ||
+        !au_draw_batch(st, set->d_cum, set->d_first, set->shift, Sp, set->N, d_rows, nb, longest, d_C)) return false;
+    marks.push_back(j.mark());
+    if (!marks.back() || !replicate_sums(set, d_C, nb, d_P, d_Rpass)) return false;
+    marks.push_back(j.mark());
+    if (!marks.back()) return false;
+    hipLaunchKernelGGL(k_au_counts, dim3((nb + RELL_WG - 1) / RELL_WG), dim3(RELL_WG), 0, st, (const double *)d_Rpass,
+                       (const au_row *)d_rows, nb, T, d_bp);
+    if (!hip_ok(hipGetLastError(), "proportion kernel")) return false;
+  }
+  hipEvent_t fit_begin = j.mark();
+  if (!fit_begin) return false;
+  hipLaunchKernelGGL(k_au_fit, dim3((T + RELL_WG - 1) / RELL_WG), dim3(RELL_WG), 0, st, (const unsigned *)d_bp,
+                     (const double *)d_rho, K, T, B, kstar, d_fit, d_fit + T, d_fit + 2 * T, d_fit + 3 * T, d_fit + 4 * T,
+                     d_used);
+  if (!hip_ok(hipGetLastError(), "fit kernel")) return false;
+  hipEvent_t fit_end = j.mark();
+  if (!fit_end || !j.download(res->bp_count, d_bp, (size_t)K * T, "download proportions") ||
+      !j.download(res->used, d_used, T, "download fit") || !j.download(res->p_au, d_fit, T, "download fit") ||
+      !j.download(res->d, d_fit + T, T, "download fit") || !j.download(res->c, d_fit + 2 * T, T, "download fit") ||
+      !j.download(res->se, d_fit + 3 * T, T, "download fit") || !j.download(res->rss, d_fit + 4 * T, T, "download fit") ||
+      (keep && !j.download(res->replicate_lnl, d_R, total * T, "download replicates")) ||
+      !hip_ok(hipStreamSynchronize(st), "multiscale kernels"))
+    return false;
+  double ms[3] = {0.0, 0.0, 0.0};
+  float f = 0.f;
+  for (size_t k = 0; k < marks.size(); ++k)
+  {
+    hipEvent_t next = k + 1 < marks.size() ? marks[k + 1] : fit_begin;
+    if (!j.elapsed(marks[k], next, &f)) return false;
+    ms[k % 3] += f;
+  }
+  if (!j.elapsed(fit_begin, fit_end, &f)) return false;
+  ms[2] += f;
+  for (int k = 0; k < 3; ++k) g_au_last_ms[k] = ms[k];
   return true;
 }
 
@@ -523,6 +684,135 @@ PLL_EXPORT int pllhip_bootstrap_weights(const unsigned int * weights, unsigned i
     const unsigned nb = std::min(batch, count - done);
     if (!draw_batch(j.stream, d_cum.p, d_first.p, table.shift, Sp, N, seed, first + done, nb, d_C.p)) return PLL_FAILURE;
     PLLHIP_TRY(hipMemcpy2DAsync(out + (size_t)done * patterns, (size_t)patterns * sizeof(unsigned), d_C.p,
+                                Sp * sizeof(unsigned), (size_t)patterns * sizeof(unsigned), nb, hipMemcpyDeviceToHost,
+                                j.stream));
+    PLLHIP_TRY(hipStreamSynchronize(j.stream));
+  }
+  return PLL_SUCCESS;
+}
+
+PLL_EXPORT void pllhip_au_destroy(pllhip_au_result_t * result)
+{
+  if (!result) return;
+  free(result->lnl);
+  free(result->draws);
+  free(result->bp_count);
+  free(result->p_au);
+  free(result->d);
+  free(result->c);
+  free(result->se);
+  free(result->rss);
+  free(result->used);
+  free(result->replicate_lnl);
+  free(result);
+}
+
+PLL_EXPORT pllhip_au_result_t * pllhip_sitelh_au(pllhip_sitelh_t * set, const pllhip_au_params_t * params)
+{
+  if (!check_set(set, "pllhip_sitelh_au")) return nullptr;
+  if (!params || !params->replicates || params->replicates >= RELL_MAX_REPLICATES)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "pllhip_sitelh_au: %u replicates per scale (1 to 2^24 - 1 are supported)",
+              params ? params->replicates : 0u);
+    return nullptr;
+  }
+  const unsigned K = params->scale ? params->scales : 10u;
+  if (K < 2 || K > AU_MAX_SCALES)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "pllhip_sitelh_au: %u scales (2 to %u are supported)", K, AU_MAX_SCALES);
+    return nullptr;
+  }
+  if (!set->count)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "pllhip_sitelh_au: the set holds no tree");
+    return nullptr;
+  }
+  std::vector<u64> n;
+  if (!au_draw_counts(params->scale ? params->scale : AU_DEFAULT_SCALES, K, set->N, n)) return nullptr;
+  const unsigned T = set->count, B = params->replicates;
+  const bool keep = params->flags & PLLHIP_AU_REPLICATES;
+  pllhip_au_result_t * res = (pllhip_au_result_t *)calloc(1, sizeof(pllhip_au_result_t));
+  if (res)
+  {
+    res->trees = T;
+    res->replicates = B;
+    res->scales = K;
+    res->lnl = (double *)calloc(T, sizeof(double));
+    res->draws = (u64 *)calloc(K, sizeof(u64));
+    res->bp_count = (unsigned *)calloc((size_t)K * T, sizeof(unsigned));
+    res->p_au = (double *)calloc(T, sizeof(double));
+    res->d = (double *)calloc(T, sizeof(double));
+    res->c = (double *)calloc(T, sizeof(double));
+    res->se = (double *)calloc(T, sizeof(double));
+    res->rss = (double *)calloc(T, sizeof(double));
+    res->used = (unsigned *)calloc(T, sizeof(unsigned));
+    if (keep) res->replicate_lnl = (double *)calloc((size_t)K * B * T, sizeof(double));
+  }
+  if (!res || !res->lnl || !res->draws || !res->bp_count || !res->p_au || !res->d || !res->c || !res->se || !res->rss ||
+      !res->used || (keep && !res->replicate_lnl))
+  {
+    pllhip_au_destroy(res);
+    set_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate memory for the AU test's result");
+    return nullptr;
+  }
+  std::copy(n.begin(), n.end(), res->draws);
+  if (!au_run(set, params, n, res))
+  {
+    pllhip_au_destroy(res);
+    return nullptr;
+  }
+  return res;
+}
+
+PLL_EXPORT void pllhip_au_last_times(double * draw_ms, double * product_ms, double * stats_ms)
+{
+  if (draw_ms) *draw_ms = g_au_last_ms[0];
+  if (product_ms) *product_ms = g_au_last_ms[1];
+  if (stats_ms) *stats_ms = g_au_last_ms[2];
+}
+
+PLL_EXPORT int pllhip_multiscale_weights(const unsigned int * weights, unsigned int patterns, unsigned long long seed,
+                                         unsigned int scale_index, unsigned long long draws, unsigned int first,
+                                         unsigned int count, unsigned int * out)
+{
+  if (!patterns || !out || (u64)first + count > RELL_MAX_REPLICATES - 1 || scale_index >= AU_MAX_SCALES || !draws ||
+      draws >= RELL_MAX_DRAWS)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "pllhip_multiscale_weights: no patterns, no output array, replicates beyond "
+              "2^24 - 2, a scale index beyond 63, or draws outside 1 .. 2^40 - 1");
+    return PLL_FAILURE;
+  }
+  DrawTable table;
+  const std::vector<u64> & cum = table.cum;
+  u64 N = 0;
+  int device = -1;
+  if (!prefix_sums("pllhip_multiscale_weights", weights, patterns, table, &N) ||
+      !caller_device("pllhip_multiscale_weights", &device))
+    return PLL_FAILURE;
+  if (!count) return PLL_SUCCESS;
+  const size_t Sp = pad16(patterns);
+  const unsigned batch = (unsigned)std::max<size_t>(
+      1, std::min<size_t>({count, RELL_MAX_BATCH, WEIGHTS_STAGE_BYTES / (Sp * sizeof(unsigned))}));
+  DeviceJob j;
+  if (!j.enter(device)) return PLL_FAILURE;
+  unsigned * d_C = j.alloc<unsigned>(pad16(batch) * Sp, "replicate counts");
+  au_row * d_rows = j.alloc<au_row>(batch, "row table");
+  au_row * h_rows = j.pinned<au_row>(batch);
+  u64 * d_cum = cum.empty() ? nullptr : j.alloc<u64>(patterns, "weight prefix sums");
+  unsigned * d_first = cum.empty() ? nullptr : j.alloc<unsigned>(table.first.size(), "draw buckets");
+  if (!d_C || !d_rows || !h_rows || (!cum.empty() && (!d_cum || !d_first))) return PLL_FAILURE;
+  if (!cum.empty() && (!j.upload(d_cum, cum.data(), patterns, "upload prefix sums") ||
+                       !j.upload(d_first, table.first.data(), table.first.size(), "upload draw buckets")))
+    return PLL_FAILURE;
+  const u64 stream_seed = au_scale_seed(seed, scale_index);
+  for (unsigned done = 0; done < count; done += batch)
+  {
+    const unsigned nb = std::min(batch, count - done);
+    for (unsigned i = 0; i < nb; ++i) h_rows[i] = au_row{stream_seed, draws, first + done + i, scale_index};
+    if (!j.upload(d_rows, h_rows, nb, "upload row table") ||
+        !au_draw_batch(j.stream, d_cum, d_first, table.shift, Sp, N, d_rows, nb, draws, d_C))
+      return PLL_FAILURE;
+    PLLHIP_TRY(hipMemcpy2DAsync(out + (size_t)done * patterns, (size_t)patterns * sizeof(unsigned), d_C,
                                 Sp * sizeof(unsigned), (size_t)patterns * sizeof(unsigned), nb, hipMemcpyDeviceToHost,
                                 j.stream));
     PLLHIP_TRY(hipStreamSynchronize(j.stream));

@@ -203,6 +203,7 @@ pllhip_node_ancestral_last_times
 pllhip_sitelh_create pllhip_sitelh_destroy pllhip_sitelh_count pllhip_sitelh_get pllhip_sitelh_add
 pllhip_sitelh_add_edge pllhip_sitelh_rell pllhip_rell_destroy pllhip_rell_last_times
 pllhip_bootstrap_weights
+pllhip_sitelh_au pllhip_au_destroy pllhip_au_last_times pllhip_multiscale_weights
 pllhip_distances_partition pllhip_distances_msa pllhip_distmat_from_host pllhip_distmat_destroy pllhip_distmat_size
 pllhip_distmat_get pllhip_distmat_compared pllhip_distmat_counts pllhip_distmat_no_overlap pllhip_distmat_nj
 pllhip_distmat_nj_joins pllhip_distances_last_times""".split()
@@ -270,6 +271,23 @@ class RellResult(C.Structure):
                 ("elw", c_double_p), ("replicate_lnl", c_double_p)]
 
 
+PLLHIP_AU_REPLICATES = 1
+
+
+class AuParams(C.Structure):
+    """pllhip_au_params_t"""
+    _fields_ = [("replicates", C.c_uint), ("scales", C.c_uint), ("scale", c_double_p), ("seed", C.c_ulonglong),
+                ("flags", C.c_uint), ("batch", C.c_uint)]
+
+
+class AuResult(C.Structure):
+    """pllhip_au_result_t"""
+    _fields_ = [("trees", C.c_uint), ("replicates", C.c_uint), ("scales", C.c_uint), ("best", C.c_uint),
+                ("batch", C.c_uint), ("lnl", c_double_p), ("draws", C.POINTER(C.c_ulonglong)), ("bp_count", c_uint_p),
+                ("p_au", c_double_p), ("d", c_double_p), ("c", c_double_p), ("se", c_double_p), ("rss", c_double_p),
+                ("used", c_uint_p), ("replicate_lnl", c_double_p)]
+
+
 DIST_P, DIST_JC, DIST_ML = 0, 1, 2
 DIST_KEEP_COUNTS = 1
 
@@ -283,6 +301,12 @@ class DistParams(C.Structure):
 class Rell:
     """numpy copy of a pllhip_rell_result_t: trees, replicates, best, batch, lnl, bp_count, kh_count, sh_count, elw,
     R [replicates][trees] or None, times = (draw, product, statistics) in ms"""
+
+
+class Au:
+    """numpy copy of a pllhip_au_result_t: trees, replicates, scales, best, batch, lnl [T], draws [K], bp_count [K][T],
+    p_au / d / c / se / rss [T], used [T], R [scales][replicates][trees] or None, times = (draw, product, statistics)
+    in ms"""
 
 
 class PllLib:
@@ -503,6 +527,15 @@ class PllLib:
             L.pllhip_rell_last_times.restype = None
             L.pllhip_rell_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
             L.pllhip_bootstrap_weights.argtypes = [c_uint_p, C.c_uint, C.c_ulonglong, C.c_uint, C.c_uint, c_uint_p]
+        if hasattr(L, "pllhip_sitelh_au"):
+            L.pllhip_sitelh_au.restype = C.POINTER(AuResult)
+            L.pllhip_sitelh_au.argtypes = [C.c_void_p, C.POINTER(AuParams)]
+            L.pllhip_au_destroy.restype = None
+            L.pllhip_au_destroy.argtypes = [C.POINTER(AuResult)]
+            L.pllhip_au_last_times.restype = None
+            L.pllhip_au_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
+            L.pllhip_multiscale_weights.argtypes = [c_uint_p, C.c_uint, C.c_ulonglong, C.c_uint, C.c_ulonglong,
+                                                    C.c_uint, C.c_uint, c_uint_p]
         if hasattr(L, "pllhip_distances_partition"):
             L.pllhip_distances_partition.restype = C.c_void_p
             L.pllhip_distances_partition.argtypes = [pp, C.POINTER(DistParams)]
@@ -1484,6 +1517,32 @@ class SiteLikelihoods:
         out.times = (a.value, b.value, c.value)
         return out
 
+    def au(self, replicates, seed, scale=None, flags=0, batch=0, scales=None):
+        """pllhip_sitelh_au as an Au, or None; scale = the r_k (None: the library's ten), scales = K where it is to
+        differ from len(scale)"""
+        r = None if scale is None else _f64(scale)
+        K = (0 if r is None else len(r)) if scales is None else scales
+        params = AuParams(replicates, K, None if r is None else r.ctypes.data_as(c_double_p), seed, flags, batch)
+        rp = self.L.pllhip_sitelh_au(self.h, C.byref(params))
+        if not rp:
+            return None
+        try:
+            a, out = rp.contents, Au()
+            T, B, K = a.trees, a.replicates, a.scales
+            out.trees, out.replicates, out.scales, out.best, out.batch = T, B, K, a.best, a.batch
+            out.lnl = np.ctypeslib.as_array(a.lnl, (T,)).copy()
+            out.draws = np.ctypeslib.as_array(a.draws, (K,)).copy()
+            out.bp_count = np.ctypeslib.as_array(a.bp_count, (K, T)).copy()
+            for name in ("p_au", "d", "c", "se", "rss", "used"):
+                setattr(out, name, np.ctypeslib.as_array(getattr(a, name), (T,)).copy())
+            out.R = np.ctypeslib.as_array(a.replicate_lnl, (K, B, T)).copy() if a.replicate_lnl else None
+        finally:
+            self.L.pllhip_au_destroy(rp)
+        x, y, z = C.c_double(0), C.c_double(0), C.c_double(0)
+        self.L.pllhip_au_last_times(C.byref(x), C.byref(y), C.byref(z))
+        out.times = (x.value, y.value, z.value)
+        return out
+
 
 class DistMat:
     """pllhip_distmat_t (include/pllhip.h): made by distances_partition / distances_msa / distmat_from_host below.
@@ -1587,6 +1646,15 @@ def bootstrap_weights(lib, weights, patterns, seed, first, count):
     out = np.zeros((count, patterns), np.uint32)
     ok = lib.lib.pllhip_bootstrap_weights(None if w is None else w.ctypes.data_as(c_uint_p), patterns, seed, first,
                                           count, out.ctypes.data_as(c_uint_p))
+    return out if ok else None
+
+
+def multiscale_weights(lib, weights, patterns, seed, scale_index, draws, first, count):
+    """pllhip_multiscale_weights: [count][patterns] uint32, or None"""
+    w = None if weights is None else _u32(weights)
+    out = np.zeros((count, patterns), np.uint32)
+    ok = lib.lib.pllhip_multiscale_weights(None if w is None else w.ctypes.data_as(c_uint_p), patterns, seed,
+                                           scale_index, draws, first, count, out.ctypes.data_as(c_uint_p))
     return out if ok else None
 
 
