@@ -224,9 +224,15 @@ PLL_EXPORT int pllhip_transient_stats(const pll_partition_t * partition, pllhip_
    evaluating without reading such vectors (two such lists in a row of which none was stored later; PLLHIP_DEFER=3: always),
    the tip-only run at the bottom of every operation chain -- the cherry a chain starts with and the "that vector x
    coded tip" operations above it whose result the next operation takes in registers (PLLHIP_DEFER_DEPTH=D: the
-   first D operations of a run).  Their scaler counts are stored as always.  Such a vector is kept as its operation, exactly like a vector the mode above left out, and is
-   stored for its first reader or before one of its inputs changes -- by a launch of its own (the members of a run at
-   the bottom of a chain: by one launch for the run; PLLHIP_DEFER_GROUP=0: one per reader), which costs two to three
+   first D operations of a run); and, once four such lists in a row have gone unread
+   (PLLHIP_DEFER=4: always), every vector inside a chain that the next operation of the chain takes in registers and
+   that no other operation of the list reads, whatever its children are: from the fifth
+   evaluation of a row on only the last vector of each chain and the vectors at the root edge are stored.  The first
+   deferred vector that is stored for a reader takes the following lists back to the first level.  Their scaler
+   counts are stored as always.  Such a vector is kept as its operation, exactly like a vector the mode above left
+   out, and is stored for its first reader or before one of its inputs -- a P-matrix, a tip, a child vector, a scaler
+   buffer -- changes, by a launch of its own (deferred vectors that stand next to each other in a chain: by one
+   launch for all of them from the reader's upwards; PLLHIP_DEFER_GROUP=0: one per reader), which costs two to three
    times what leaving the store out of the traversal saved.  A caller observes nothing but
    timing: whatever it reads is bit-identical to PLLHIP_DEFER=0 in the environment (which plans every store).
    pllhip_discard_transient leaves these vectors alone (the caller never asked for them to be left out);

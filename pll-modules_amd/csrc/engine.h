@@ -144,7 +144,8 @@ struct DevicePlan                                 // the schedule resident on th
   unsigned inner_reads = 0;                       // inner vectors that the chains read from memory
   unsigned nlookups = 0;                          // children read through their class tables (PlanOp::flags bit 5)
   unsigned ndeferred = 0;                         // stores a storing traversal leaves out (plan_defers; PlanOp::flags bit 0)
-  // of them, the runs at the bottom of chains: (vector, the vector above it in the same run), bottom-up
+  // of them, the runs at the bottom of chains (level 3) and the adjacent members inside chains (level 4): (vector, the
+  // vector above it in the same chain), bottom-up
   std::vector<std::pair<unsigned, unsigned>> defer_runs;
   double algo_bytes = 0.0, algo_flops = 0.0;      // algorithmic traffic / work of the traversal
   double min_bytes = 0.0;                         // traffic without the child vectors handed over in registers
@@ -262,9 +263,9 @@ struct Engine
   pllhip_transient_stats_t transient_stats = {};
   pllhip_deferred_stats_t deferred_stats = {};  // the same records, for the stores that storing traversals defer
   // how the caller has treated deferred vectors lately (run_resident; the default level of plan_defers goes by it):
-  // a list that left stores out has run; stored_later at its end; no deferred vector was stored between the two such
-  // lists before
-  bool defer_counted = false, defer_unread = false;
+  // the lists in a row that left stores out with no deferred vector stored since the end of the first of them (0: no
+  // such list has run yet); stored_later at the end of the last one
+  unsigned defer_row = 0;
   unsigned long long defer_stored_mark = 0;
   size_t sc_len = 0;                  // entries per scale buffer on the device
   KernelFamily family = KernelFamily::Generic;

@@ -1077,7 +1077,8 @@ struct ChainFamily
   unsigned (*look_classes)(const Engine * e, unsigned lut_used);
   // the family's storing schedules leave out the stores nobody reads (plan_defers; null: never; 0: not at this
   // partition's shape; bits 0 - 7: which -- 1, 2: those of folded cherries alone, 3: also the tip-only runs at the
-  // bottom of the chains --, bits 8 and up: the most operations of such a run, 0 = all)
+  // bottom of the chains, 4: also the vectors inside the chains --, bits 8 and up: the most operations of such a run,
+  // 0 = all)
   unsigned (*defer)(const Engine * e);
   const double * (*pair_pfrag)(const Engine * e, unsigned matrix);        // PairLutJob::pfrag of a branch
   bool (*fills_chip)(const Engine * e);                 // the site blocks alone keep the chip busy: one launch
@@ -1114,27 +1115,40 @@ static unsigned s20_look_classes(const Engine * e, unsigned lut_used)
 
 // 20 states: whether a storing schedule leaves out the stores nobody reads (plan_defers): 0 = no, 1 = those of folded
 // cherries and of looked-up children, 2 = those of folded cherries alone, 3 = level 1 and the tip-only runs at the
-// bottom of the chains; bits 8 and up: the most operations of such a run that are left out (0: the whole run).  A store
+// bottom of the chains, 4 = level 3 and the vectors inside the chains; bits 8 and up (level 3): the most operations of
+// such a run that are left out (0: the whole run).  A store
 // that is made up for later costs a launch of its own on top of its bytes, which a small partition never saved in the
 // traversal: a floor of S20_DEFER_MIN_BLOCKS site blocks, just under the smallest partition measured to gain (C3's
-// 125 k-site slice, 3 907 blocks: 4.07 -> 3.96 ms per evaluation).  PLLHIP_DEFER=1 / 3 defers at any size (the tests
-// do), PLLHIP_DEFER=0 at none (every vector is stored by the traversal that computes it: the reference of the A/B runs
-// and of the bitwise tests), PLLHIP_DEFER=2 defers the folded half alone, at any size (the A/B runs that weigh the two
-// halves separately).  PLLHIP_DEFER_DEPTH=D caps the runs of level 3 at D operations (0: no cap).
-// Without PLLHIP_DEFER the level follows what the caller does with the vectors that were left out (DESIGN.md section
-// 22): level 3 gains 11 % on an evaluation that is followed by another evaluation, and costs an evaluation that is
-// followed by a pass over all branches more than it saved, at any depth.  So level 1 is planned until two lists in a row
-// that left stores out have come and gone without one deferred vector being stored later (Engine::defer_unread, run_resident), level 3 from
-// then on, and level 1 again as soon as a reader asks for a deferred vector.
+// 125 k-site slice, 3 907 blocks: 4.07 -> 3.96 ms per evaluation).  PLLHIP_DEFER=1 / 3 / 4 defers at any size (the
+// tests do), PLLHIP_DEFER=0 at none (every vector is stored by the traversal that computes it: the reference of the A/B
+// runs and of the bitwise tests), PLLHIP_DEFER=2 defers the folded half alone, at any size (the A/B runs that weigh the
+// two halves separately).  PLLHIP_DEFER_DEPTH=D caps the runs of level 3 at D operations (0: no cap); level 4 = level 3
+// and every vector inside a chain that the next operation takes in registers and nobody reads from memory, without a cap.
+// Without PLLHIP_DEFER the level follows what the caller does with the vectors that were left out (DESIGN.md sections
+// 22 and 26): a higher level gains on an evaluation that is followed by another evaluation, and costs an evaluation that
+// is followed by a pass over all branches more than it saved.  So level 1 is planned until S20_DEFER_RUN_ROW lists in a
+// row that left stores out have come and gone without one deferred vector being stored later (Engine::defer_row,
+// run_resident), level 3 from then on, level 4 once S20_DEFER_CHAIN_ROW such lists have, and level 1 again as soon as a
+// reader asks for a deferred vector.  S20_DEFER_CHAIN_ROW = max(4, ceil(T / G)) at the size where T / G is largest: G is
+// what level 4 gains per evaluation over level 3, T what the turn "evaluation, then a pass over all branches" costs more
+// at level 4 than at level 3, plus G.  Measured on C3 (section 26; medians of three processes, ms):
+//   125 000 sites  G 0.61  T 1.50  T / G 2.5;  250 000 sites  G 0.92  T 2.72  T / G 3.0;  500 000 sites  G 1.91  T 5.56  T / G 2.9
+// so ceil(T / G) = 3 and the bound of 4 decides: a caller who reads after a row of evaluations has by then saved more
+// than the turn costs, and a row of fewer than five evaluations never reaches level 4.  The 125 k-site slice gains
+// (3.42 -> 2.81 ms per evaluation), so level 4 shares the floor.
 constexpr unsigned S20_DEFER_MIN_BLOCKS = 3840;         // 122 880 sites
 constexpr unsigned S20_DEFER_DEPTH = 0;                 // without PLLHIP_DEFER_DEPTH
+constexpr unsigned S20_DEFER_RUN_ROW = 2;               // unread lists in a row before level 3
+constexpr unsigned S20_DEFER_CHAIN_ROW = 4;             // ... before level 4
 static unsigned s20_defer(const Engine * e)
 {
   static const int use_defer = getenv("PLLHIP_DEFER") ? atoi(getenv("PLLHIP_DEFER")) : -1;
   static const int env_depth = getenv("PLLHIP_DEFER_DEPTH") ? atoi(getenv("PLLHIP_DEFER_DEPTH")) : -1;
   if (!use_defer || (use_defer < 0 && e->nblk < S20_DEFER_MIN_BLOCKS)) return 0u;
-  const bool unread = e->defer_unread && e->deferred_stats.stored_later == e->defer_stored_mark;
-  const unsigned level = use_defer < 0 ? (unread ? 3u : 1u) : use_defer == 2 ? 2u : use_defer >= 3 ? 3u : 1u;
+  // (the lists in a row that went unread so far; a vector stored since the last of them ends the row)
+  const unsigned row = e->deferred_stats.stored_later == e->defer_stored_mark ? e->defer_row : 0u;
+  const unsigned level = use_defer < 0 ? (row >= S20_DEFER_CHAIN_ROW ? 4u : row >= S20_DEFER_RUN_ROW ? 3u : 1u)
+                       : use_defer == 2 ? 2u : use_defer == 3 ? 3u : use_defer >= 4 ? 4u : 1u;
   const unsigned depth = env_depth < 0 ? S20_DEFER_DEPTH : (unsigned)std::min(env_depth, 1023);
   return level == 3 ? level | depth << 8 : level;
 }
@@ -1729,6 +1743,17 @@ static void plan_lookups(const Engine * e, const pll_operation_t * ops, unsigned
 //                                  run at the most (0: all of them): never the last operation of a chain, never a vector
 //                                  that an operation reads from memory.  plan.run_up links the marked operations of a
 //                                  run bottom-up (transient_materialize stores a run in one list).
+//   a vector inside a chain (level 4)
+//                               -- any operation whose vector the next operation of its chain (the one behind a folded
+//                                  cherry, if one stands between them) takes in registers, that operation being its only
+//                                  reader in the list: whatever its children are, however far up the chain.  The next
+//                                  evaluation overwrites it unread.  Never the last operation of a chain, never a vector
+//                                  that an operation reads from memory or that nobody in the list reads.  Everything
+//                                  level 3 marks is among them.  Such a vector is recomputed from stored child vectors,
+//                                  not from tip codes alone: the engine stores it before one of them is overwritten
+//                                  (transient_before_list).  plan.run_up links two marked operations that stand next to
+//                                  each other in a chain; across a folded cherry there is no link, and the reader of the
+//                                  lower one stores what it needs alone.
 // `plan`: after plan_folds and plan_lookups.
 // level 2: the looked-up children keep their stores (defer_stores)
 static void plan_defers(const Engine * e, const pll_operation_t * ops, unsigned count, unsigned level, unsigned depth, ChainPlan & plan)
@@ -1761,6 +1786,30 @@ static void plan_defers(const Engine * e, const pll_operation_t * ops, unsigned 
     if (!side) return 0u;
     return (side == 1 ? ops[o].child1_clv_index : ops[o].child2_clv_index) == ops[from].parent_clv_index ? side : 0u;
   };
+  if (level >= 4)
+  {
+    // every vector inside a chain that goes up in registers and nowhere else, whatever its children are
+    for (const std::vector<unsigned> & ch : plan.chains)
+    {
+      size_t below = ch.size();                        // position of the operation marked last
+      for (size_t i = 0; i + 1 < ch.size(); ++i)
+      {
+        const unsigned k = ch[i];
+        if (is_folded(k)) continue;
+        const size_t next = i + 1 + (is_folded(ch[i + 1]) ? 1 : 0);
+        if (next >= ch.size() || !taken_over(ch[next], k) || readers[ops[k].parent_clv_index] != 1) continue;
+        plan.deferred[k] = 1;
+        // (linked to the one below only where the two stand next to each other: no folded cherry between them)
+        if (below + 1 == i)
+        {
+          if (plan.run_up.empty()) plan.run_up.assign(count, -1);
+          plan.run_up[ch[below]] = (int)k;
+        }
+        below = i;
+      }
+    }
+    return;
+  }
   for (const std::vector<unsigned> & ch : plan.chains)
   {
     size_t i = 0;
@@ -2084,7 +2133,8 @@ static void transient_mark(Engine * e, const pll_operation_t & o, char kind)
 // store the vectors of `want` that exist as their operation only: the operations that made them run again (and,
 // below them, the ones of the children that were not stored either), as an ordinary list -- the same kernels on the
 // same inputs, so what is stored is what the traversal would have stored.
-// A member of a deferred chain-bottom run (plan_defers, level 3) brings the members above it along: one list, one
+// A member of a deferred chain-bottom run (plan_defers, level 3), or of a stretch of deferred vectors that stand next to
+// each other inside a chain (level 4), brings the members above it along: one list, one
 // chain, one launch for the run instead of a launch per member that re-reads what the one before just wrote
 // (PLLHIP_DEFER_GROUP=0: every reader stores what it reads and what lies below, as for every other vector).
 // going: [nodes] vectors that the caller is about to overwrite -- a run is not followed into them (null: none)
@@ -3118,13 +3168,13 @@ static int run_resident(Engine * e, const ChainFamily & f, const pll_operation_t
   if (!launch_resident(e, f, dp, view, 0, !e->cherries.empty(), transient)) return PLL_FAILURE;
   // (a storing schedule marks only the stores it deferred: plan_defers)
   if (transient || dp.ndeferred) transient_after_list(e, ops, count, dp, transient ? TRANSIENT_MODE : TRANSIENT_DEFERRED);
-  // what became of the vectors that the deferring lists before this one left out: all given up unread since the end of
-  // the last but one, or some stored for a reader (the family's default level goes by it: s20_defer; lists that leave
-  // nothing out -- the single operations of a smoothing pass -- say nothing about it)
+  // what became of the vectors that the deferring lists before this one left out: all given up unread -- the row of
+  // such lists grows by this one --, or some stored for a reader -- a new row starts here (the family's default level
+  // goes by its length: s20_defer; lists that leave nothing out -- the single operations of a smoothing pass -- say
+  // nothing about it)
   if (dp.ndeferred)
   {
-    e->defer_unread = e->defer_counted && e->deferred_stats.stored_later == e->defer_stored_mark;
-    e->defer_counted = true;
+    e->defer_row = e->defer_row && e->deferred_stats.stored_later == e->defer_stored_mark ? e->defer_row + 1u : 1u;
     e->defer_stored_mark = e->deferred_stats.stored_later;
   }
   count_list(e, count);
