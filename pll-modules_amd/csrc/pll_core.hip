@@ -17,6 +17,7 @@
 // Operation lists are level-scheduled: ops of one dependency level share one
 // launch (grid.y = op), their descriptors travel by value in the kernel
 // arguments, so no host->device copy sits on the critical path.
+#include "chain_plan.hpp"
 #include "device_job.hpp"
 #include "kernels_common.hpp"
 #include "kernels_generic.hpp"
@@ -38,6 +39,8 @@
 #include <time.h>
 
 namespace pllhip {
+
+using namespace chainplan;                       // the chain planner (chain_plan.hpp)
 
 static thread_local int g_device = -1;
 
@@ -1075,11 +1078,9 @@ struct ChainFamily
   // the family reads small light subtrees through class tables (plan_lookups): the most classes of such a child
   // (null: the family has no such reads; 0: none at this partition's shape)
   unsigned (*look_classes)(const Engine * e, unsigned lut_used);
-  // the family's storing schedules leave out the stores nobody reads (plan_defers; null: never; 0: not at this
-  // partition's shape; bits 0 - 7: which -- 1, 2: those of folded cherries alone, 3: also the tip-only runs at the
-  // bottom of the chains, 4: also the vectors inside the chains --, bits 8 and up: the most operations of such a run,
-  // 0 = all)
-  unsigned (*defer)(const Engine * e);
+  // the family's storing schedules leave out the stores nobody reads (plan_defers; null: never; level 0: not at this
+  // partition's shape; DeferPolicy, chain_plan.hpp)
+  DeferPolicy (*defer)(const Engine * e);
   const double * (*pair_pfrag)(const Engine * e, unsigned matrix);        // PairLutJob::pfrag of a branch
   bool (*fills_chip)(const Engine * e);                 // the site blocks alone keep the chip busy: one launch
   unsigned (*units)(const Engine * e);                  // workgroups a member of a batch can use side by side
@@ -1115,7 +1116,7 @@ static unsigned s20_look_classes(const Engine * e, unsigned lut_used)
 
 // 20 states: whether a storing schedule leaves out the stores nobody reads (plan_defers): 0 = no, 1 = those of folded
 // cherries and of looked-up children, 2 = those of folded cherries alone, 3 = level 1 and the tip-only runs at the
-// bottom of the chains, 4 = level 3 and the vectors inside the chains; bits 8 and up (level 3): the most operations of
+// bottom of the chains, 4 = level 3 and the vectors inside the chains; depth (level 3): the most operations of
 // such a run that are left out (0: the whole run).  A store
 // that is made up for later costs a launch of its own on top of its bytes, which a small partition never saved in the
 // traversal: a floor of S20_DEFER_MIN_BLOCKS site blocks, just under the smallest partition measured to gain (C3's
@@ -1140,17 +1141,17 @@ constexpr unsigned S20_DEFER_MIN_BLOCKS = 3840;         // 122 880 sites
 constexpr unsigned S20_DEFER_DEPTH = 0;                 // without PLLHIP_DEFER_DEPTH
 constexpr unsigned S20_DEFER_RUN_ROW = 2;               // unread lists in a row before level 3
 constexpr unsigned S20_DEFER_CHAIN_ROW = 4;             // ... before level 4
-static unsigned s20_defer(const Engine * e)
+static DeferPolicy s20_defer(const Engine * e)
 {
   static const int use_defer = getenv("PLLHIP_DEFER") ? atoi(getenv("PLLHIP_DEFER")) : -1;
   static const int env_depth = getenv("PLLHIP_DEFER_DEPTH") ? atoi(getenv("PLLHIP_DEFER_DEPTH")) : -1;
-  if (!use_defer || (use_defer < 0 && e->nblk < S20_DEFER_MIN_BLOCKS)) return 0u;
+  if (!use_defer || (use_defer < 0 && e->nblk < S20_DEFER_MIN_BLOCKS)) return {};
   // (the lists in a row that went unread so far; a vector stored since the last of them ends the row)
   const unsigned row = e->deferred_stats.stored_later == e->defer_stored_mark ? e->defer_row : 0u;
   const unsigned level = use_defer < 0 ? (row >= S20_DEFER_CHAIN_ROW ? 4u : row >= S20_DEFER_RUN_ROW ? 3u : 1u)
                        : use_defer == 2 ? 2u : use_defer == 3 ? 3u : use_defer >= 4 ? 4u : 1u;
   const unsigned depth = env_depth < 0 ? S20_DEFER_DEPTH : (unsigned)std::min(env_depth, 1023);
-  return level == 3 ? level | depth << 8 : level;
+  return {level, level == 3 ? depth : 0u};
 }
 
 static const ChainFamily CHAINS_S4 = {
@@ -1398,10 +1399,10 @@ static unsigned fold_table_lds(const Engine * e, const ChainFamily & f, unsigned
 
 // whether a storing schedule with folds leaves out the stores nobody reads (plan_defers; the family says which and
 // from what size on: ChainFamily::defer)
-static unsigned defer_stores(const Engine * e, const ChainFamily & f, bool transient)
+static DeferPolicy defer_stores(const Engine * e, const ChainFamily & f, bool transient)
 {
   // (an evaluate-only traversal leaves these vectors out already; the lists that store vectors later store them)
-  if (!f.defer || transient || e->transient_mode || e->transient_busy || e->site_repeats) return 0u;
+  if (!f.defer || transient || e->transient_mode || e->transient_busy || e->site_repeats) return {};
   return f.defer(e);
 }
 
@@ -1411,439 +1412,36 @@ static unsigned child_table_lds(const Engine * e, const ChainFamily & f, unsigne
   return wide ? f.wide_lds(e, e->cherries[idx].nclasses) : f.child_lds(e, coded_tip(e, idx), lut_used);
 }
 
-// Chain schedule of an operation list (see ChainBatch, engine.h).  Accepted only for
-// lists with the shape of a tree traversal -- every vector written once, read by at
-// most one later operation, nothing overwritten after it was read, child scalers
-// being the ones the producers wrote -- anything else keeps the level schedule.
-struct ChainPlan
+// An operation list as the chain planner takes it (chain_plan.hpp: the planner knows nothing of the engine), and what
+// its one pass over the list found.  accepted: the list has the shape of a tree traversal; anything else keeps the
+// level schedule.
+// f: the family whose tables count against the LDS cap (null: no tables, the shape alone)
+// wide: [2 * count] which children are read as wide tips (null or empty: none)
+struct PlannedList
 {
-  std::vector<std::vector<unsigned>> chains;     // op indices, bottom to top
-  std::vector<int> launch;                       // per chain: launch round
-  std::vector<unsigned> lds;                     // per chain: LDS doubles of its operations' tables
-  std::vector<unsigned char> carried;            // per op
-  // per op: 1 / 2 = a lone cherry that the next operation of its chain builds in registers as its child 1 / 2
-  // (plan_folds; empty: no folds).  Such an operation sits in front of its consumer in `chains`
-  std::vector<unsigned char> folded;
-  // children that their consumer reads through a class table instead of the stored vector (plan_lookups), and per op
-  // which child that is (1 / 2; empty: none)
-  struct Lookup
+  std::vector<unsigned> costs;                   // per child: child_table_lds
+  ChainList list;
+  ListFacts facts;
+  bool accepted;
+  PlannedList(const Engine * e, const ChainFamily * f, const pll_operation_t * ops, unsigned count, unsigned lut_used,
+              const std::vector<unsigned char> * wide = nullptr)
   {
-    unsigned consumer, top;                      // the operation that reads the child; the one that makes it
-    int cherry;                                  // top is cherry x tip: the cherry's operation (-1: top is the cherry)
-    unsigned nclasses;
-    size_t off_table[2], off_flags[2], off_counts[2], off_rows[2];   // bytes in Engine::d_looktab: [0] top, [1] the cherry below it
-  };
-  std::vector<Lookup> lookups;
-  std::vector<unsigned char> looked;
-  // per op: the traversal does not store the parent vector (plan_defers; empty: every vector is stored)
-  std::vector<unsigned char> deferred;
-  // per op: the operation above it in the same deferred chain-bottom run (-1: none; empty: no such runs)
-  std::vector<int> run_up;
-  int rounds = 0;
+    const bool w = wide && !wide->empty();
+    costs.resize(f ? 2 * (size_t)count : 0);
+    for (size_t i = 0; i < costs.size(); ++i)
+      costs[i] = child_table_lds(e, *f, i & 1 ? ops[i / 2].child2_clv_index : ops[i / 2].child1_clv_index, lut_used, w && (*wide)[i]);
+    list = {ops, count, e->nodes, e->nscalers, e->coded_tips ? e->tips : 0u, f ? costs.data() : nullptr};
+    accepted = analyse_list(list, facts);
+  }
+  PlannedList(const PlannedList &) = delete;
 };
 
-// f: the family whose tables count against lds_cap (null: no tables, the shape alone)
-// wide: [2 * count] which children are read as wide tips (null: none)
-static bool plan_chains(const Engine * e, const ChainFamily * f, const pll_operation_t * ops, unsigned count, unsigned max_len,
-                        unsigned lds_cap, unsigned lut_used, ChainPlan & plan, const std::vector<unsigned char> * wide = nullptr)
+// bytes in Engine::d_looktab of the tables of one looked-up child (ChainPlan::lookups, reserve_lookup_tables): [0] top,
+// [1] the cherry below it
+struct LookupRoom
 {
-  std::vector<int> producer(e->nodes, -1), sc_writer(e->nscalers, -1), chain_of(count, -1);
-  std::vector<char> read_ext(e->nodes, 0), sc_read_ext(e->nscalers, 0);
-  std::vector<unsigned> size(count, 1), consumers(count, 0);
-  plan.carried.assign(count, 0);
-  for (unsigned k = 0; k < count; ++k)
-  {
-    const pll_operation_t & op = ops[k];
-    const unsigned child[2] = {op.child1_clv_index, op.child2_clv_index};
-    const int child_sc[2] = {op.child1_scaler_index, op.child2_scaler_index};
-    if (child[0] == child[1] || op.parent_clv_index == child[0] || op.parent_clv_index == child[1]) return false;
-    int pr[2];
-    for (int c = 0; c < 2; ++c)
-    {
-      pr[c] = producer[child[c]];
-      if (pr[c] < 0)
-      {
-        read_ext[child[c]] = 1;
-        if (child_sc[c] >= 0)
-        {
-          if (sc_writer[child_sc[c]] >= 0) return false;
-          sc_read_ext[child_sc[c]] = 1;
-        }
-      }
-      else
-      {
-        if (++consumers[pr[c]] > 1) return false;
-        if (child_sc[c] != ops[pr[c]].parent_scaler_index) return false;
-      }
-    }
-    if (producer[op.parent_clv_index] >= 0 || read_ext[op.parent_clv_index]) return false;
-    producer[op.parent_clv_index] = (int)k;
-    if (op.parent_scaler_index >= 0)
-    {
-      if (sc_writer[op.parent_scaler_index] >= 0 || sc_read_ext[op.parent_scaler_index]) return false;
-      sc_writer[op.parent_scaler_index] = (int)k;
-    }
-
-    size[k] = 1 + (pr[0] >= 0 ? size[pr[0]] : 0) + (pr[1] >= 0 ? size[pr[1]] : 0);
-    int heavy = -1;                               // which child (0 / 1) continues a chain
-    if (pr[0] >= 0 && (pr[1] < 0 || size[pr[0]] >= size[pr[1]])) heavy = 0;
-    else if (pr[1] >= 0) heavy = 1;
-    const bool w = wide && !wide->empty();
-    const unsigned cost = !f ? 0u : child_table_lds(e, *f, op.child1_clv_index, lut_used, w && (*wide)[2 * k]) +
-                                    child_table_lds(e, *f, op.child2_clv_index, lut_used, w && (*wide)[2 * k + 1]);
-    if (heavy >= 0 && (plan.chains[chain_of[pr[heavy]]].size() >= max_len ||
-                       plan.lds[chain_of[pr[heavy]]] + cost > lds_cap)) heavy = -1;
-    int round = 0;
-    for (int c = 0; c < 2; ++c)
-      if (pr[c] >= 0 && c != heavy) round = std::max(round, plan.launch[chain_of[pr[c]]] + 1);
-    if (heavy >= 0)
-    {
-      const int ch = chain_of[pr[heavy]];
-      plan.chains[ch].push_back(k);
-      plan.lds[ch] += cost;
-      plan.launch[ch] = std::max(plan.launch[ch], round);
-      plan.carried[k] = (unsigned char)(heavy + 1);
-      chain_of[k] = ch;
-    }
-    else
-    {
-      chain_of[k] = (int)plan.chains.size();
-      plan.chains.push_back(std::vector<unsigned>(1, k));
-      plan.lds.push_back(cost);
-      plan.launch.push_back(round);
-    }
-    plan.rounds = std::max(plan.rounds, plan.launch[chain_of[k]] + 1);
-  }
-  return true;
-}
-
-// Folded cherries.  The vector that an operation reads next to the handed-over one comes back from memory -- unless it
-// is a lone cherry (a tip x tip operation that is a chain of its own): that one the consumer can build in registers
-// from the two tip tables, at the price of fold_lds doubles of the chain's LDS.  LDS is what ends chains, and a cut
-// costs a read as well (the handed-over vector comes back from memory), so cuts and folds are chosen together: per
-// heavy path (the operations linked by their larger child, which is what plan_chains' chains are pieces of) a dynamic
-// programme picks the cut points that minimise
-//     vectors read from memory = cuts + foldable cherries that are not folded
-// under the caps (max_len operations per chain, not counting the folded ones; lds_cap doubles including the folds'
-// tables); within a piece as many cherries are folded as fit.  Ties go to fewer cuts.  Without a foldable cherry, or
-// when the optimum folds nothing, `plan` stays what plan_chains made it -- whose greedy cuts are the fewest possible --,
-// so the result never reads more than the plan without folds.
-// `plan`: plan_chains' result for the same arguments (the list has the shape of a tree traversal).
-static void plan_folds(const Engine * e, const ChainFamily & f, const pll_operation_t * ops, unsigned count, unsigned max_len,
-                       unsigned lds_cap, unsigned lut_used, unsigned fold_lds, ChainPlan & plan)
-{
-  if (!fold_lds || count < 2) return;
-  std::vector<int> producer(e->nodes, -1), hprod(count, -1), up(count, -1), cherry(count, -1);
-  std::vector<unsigned> size(count, 1), cost(count, 0);
-  std::vector<unsigned char> hside(count, 0);
-  bool any = false;
-  for (unsigned k = 0; k < count; ++k)
-  {
-    const pll_operation_t & op = ops[k];
-    const int pr[2] = {producer[op.child1_clv_index], producer[op.child2_clv_index]};
-    producer[op.parent_clv_index] = (int)k;
-    size[k] = 1 + (pr[0] >= 0 ? size[pr[0]] : 0) + (pr[1] >= 0 ? size[pr[1]] : 0);
-    cost[k] = child_table_lds(e, f, op.child1_clv_index, lut_used, false) + child_table_lds(e, f, op.child2_clv_index, lut_used, false);
-    int heavy = -1;                               // (plan_chains' choice)
-    if (pr[0] >= 0 && (pr[1] < 0 || size[pr[0]] >= size[pr[1]])) heavy = 0;
-    else if (pr[1] >= 0) heavy = 1;
-    if (heavy < 0) continue;
-    hprod[k] = pr[heavy];
-    hside[k] = (unsigned char)(heavy + 1);
-    up[pr[heavy]] = (int)k;
-    const int light = pr[1 - heavy];
-    if (light < 0) continue;
-    const pll_operation_t & c = ops[light];
-    if (coded_tip(e, c.child1_clv_index) && coded_tip(e, c.child2_clv_index) &&
-        c.child1_scaler_index == PLL_SCALE_BUFFER_NONE && c.child2_scaler_index == PLL_SCALE_BUFFER_NONE)
-    {
-      cherry[k] = light;
-      any = true;
-    }
-  }
-  if (!any) return;
-
-  // per path: the pieces [a, b] and how many cherries each folds
-  struct Piece { unsigned a, b, folds; };
-  std::vector<std::vector<unsigned>> paths;
-  std::vector<std::vector<Piece>> pieces;
-  unsigned nfolds = 0;
-  for (unsigned k = 0; k < count; ++k)
-  {
-    if (hprod[k] >= 0) continue;                  // not the bottom of a path
-    std::vector<unsigned> path;
-    for (int x = (int)k; x >= 0; x = up[x]) path.push_back((unsigned)x);
-    const unsigned n = (unsigned)path.size();
-    // best[i]: the first i operations of the path; value = (pieces - folds, pieces), smallest first
-    const long INF = 1L << 40;
-    std::vector<long> best(n + 1, INF);
-    std::vector<unsigned> from(n + 1, 0), nf(n + 1, 0);
-    best[0] = 0;
-    for (unsigned b = 0; b < n; ++b)
-    {
-      unsigned lds = 0, foldable = 0;
-      for (unsigned a = b + 1; a-- > 0 && b - a < max_len; )
-      {
-        lds += cost[path[a]];
-        if (lds > lds_cap) break;
-        if (cherry[path[a]] >= 0) ++foldable;
-        if (best[a] >= INF) continue;
-        const unsigned folds = std::min(foldable, (lds_cap - lds) / fold_lds);
-        const long v = best[a] + (1L - (long)folds) * 4096L + 1L;
-        if (v < best[b + 1]) { best[b + 1] = v; from[b + 1] = a; nf[b + 1] = folds; }
-      }
-    }
-    if (best[n] >= INF) return;                   // (an operation whose own tables exceed the cap: plan_chains' plan stands)
-    std::vector<Piece> pc;
-    for (unsigned i = n; i > 0; i = from[i]) pc.push_back({from[i], i - 1, nf[i]});
-    std::reverse(pc.begin(), pc.end());
-    for (const Piece & x : pc) nfolds += x.folds;
-    paths.push_back(std::move(path));
-    pieces.push_back(std::move(pc));
-  }
-  if (!nfolds) return;
-
-  // the chains: the pieces of the paths, numbered by their first operation as plan_chains numbers them; a folded
-  // cherry (a path of one operation) goes in front of its consumer instead of forming a chain
-  std::vector<char> is_folded(count, 0);
-  std::vector<std::pair<unsigned, std::vector<unsigned>>> made;     // (first operation, chain)
-  std::vector<unsigned> made_lds;
-  ChainPlan out;
-  out.carried.assign(count, 0);
-  out.folded.assign(count, 0);
-  for (size_t p = 0; p < paths.size(); ++p)
-    for (const Piece & x : pieces[p])
-    {
-      unsigned left = x.folds;
-      for (unsigned j = x.a; j <= x.b && left; ++j)
-        if (cherry[paths[p][j]] >= 0) { is_folded[cherry[paths[p][j]]] = 1; --left; }
-    }
-  for (size_t p = 0; p < paths.size(); ++p)
-  {
-    if (paths[p].size() == 1 && is_folded[paths[p][0]]) continue;
-    for (const Piece & x : pieces[p])
-    {
-      std::vector<unsigned> ch;
-      unsigned lds = 0;
-      for (unsigned j = x.a; j <= x.b; ++j)
-      {
-        const unsigned k = paths[p][j];
-        if (cherry[k] >= 0 && is_folded[cherry[k]])
-        {
-          ch.push_back((unsigned)cherry[k]);
-          out.folded[cherry[k]] = (unsigned char)(3 - hside[k]);      // the child that is not the heavy one
-          lds += fold_lds;
-        }
-        ch.push_back(k);
-        lds += cost[k];
-        out.carried[k] = j > x.a ? hside[k] : 0;
-      }
-      made.emplace_back(paths[p][x.a], std::move(ch));
-      made_lds.push_back(lds);
-    }
-  }
-  std::vector<size_t> idx(made.size());
-  for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
-  std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return made[a].first < made[b].first; });
-  std::vector<int> chain_of(count, -1);
-  for (size_t i : idx)
-  {
-    for (unsigned k : made[i].second) chain_of[k] = (int)out.chains.size();
-    out.chains.push_back(std::move(made[i].second));
-    out.lds.push_back(made_lds[i]);
-  }
-  // rounds: a chain runs after the chains whose last vector it reads from memory (a folded cherry is no chain)
-  out.launch.assign(out.chains.size(), 0);
-  std::fill(producer.begin(), producer.end(), -1);
-  for (unsigned k = 0; k < count; ++k)
-  {
-    const unsigned child[2] = {ops[k].child1_clv_index, ops[k].child2_clv_index};
-    for (int c = 0; c < 2; ++c)
-    {
-      const int pk = producer[child[c]];
-      if (pk >= 0 && chain_of[pk] != chain_of[k])
-        out.launch[chain_of[k]] = std::max(out.launch[chain_of[k]], out.launch[chain_of[pk]] + 1);
-    }
-    producer[ops[k].parent_clv_index] = (int)k;
-    out.rounds = std::max(out.rounds, out.launch[chain_of[k]] + 1);
-  }
-  plan = std::move(out);
-}
-
-// Children read through class tables.  The vector of a cherry depends on the pair of tip codes of a site alone, the one
-// of a cherry x tip operation on three codes: at most U^2 / U^3 different columns for U codes in use, however long the
-// alignment.  Where a chain meets such a child as its light child -- the vector that comes back from memory next to the
-// handed-over one --, the consumer gathers rows of P . vector(class) from a table of all classes instead (built per
-// traversal by the class kernels of site repeats, emit_lookup_tables; the class code is arithmetic on the tip codes).
-// Nothing else changes: the child's own chain runs and stores vector and counts as before, no chain, cut or fold moves.
-// Marked: an operation's inner child that is neither handed over nor folded, made by an operation of the list that is
-// a cherry of coded tips or such a cherry x a coded tip, with at most max_classes classes; one child per operation
-// (it becomes child 2, as a folded cherry does), none next to a fold.
-static void plan_lookups(const Engine * e, const pll_operation_t * ops, unsigned count, unsigned lut_used, unsigned max_classes,
-                         ChainPlan & plan)
-{
-  plan.lookups.clear();
-  plan.looked.clear();
-  if (!max_classes || count < 2) return;
-  std::vector<int> producer(e->nodes, -1);
-  std::vector<char> fold_consumer(count, 0);
-  if (!plan.folded.empty())
-    for (const std::vector<unsigned> & ch : plan.chains)
-      for (size_t i = 0; i + 1 < ch.size(); ++i)
-        if (plan.folded[ch[i]]) fold_consumer[ch[i + 1]] = 1;
-  auto plain_tip = [&](unsigned idx, int scaler) { return coded_tip(e, idx) && scaler == PLL_SCALE_BUFFER_NONE; };
-  auto is_cherry = [&](const pll_operation_t & o)
-  { return plain_tip(o.child1_clv_index, o.child1_scaler_index) && plain_tip(o.child2_clv_index, o.child2_scaler_index); };
-  const unsigned long long u = lut_used;
-  for (unsigned k = 0; k < count; ++k)
-  {
-    const pll_operation_t & op = ops[k];
-    const unsigned child[2] = {op.child1_clv_index, op.child2_clv_index};
-    for (unsigned x = 0; x < 2 && !fold_consumer[k]; ++x)
-    {
-      const int top = child[x] < e->nodes ? producer[child[x]] : -1;
-      if (top < 0 || plan.carried[k] == x + 1 || (!plan.folded.empty() && plan.folded[top])) continue;
-      const pll_operation_t & t = ops[top];
-      int cherry = -1;
-      unsigned long long classes = u * u;
-      if (!is_cherry(t))
-      {
-        const bool tip1 = plain_tip(t.child1_clv_index, t.child1_scaler_index), tip2 = plain_tip(t.child2_clv_index, t.child2_scaler_index);
-        if (tip1 == tip2) continue;
-        cherry = producer[tip1 ? t.child2_clv_index : t.child1_clv_index];
-        if (cherry < 0 || !is_cherry(ops[cherry])) continue;
-        classes *= u;
-      }
-      if (classes > max_classes) continue;
-      if (plan.looked.empty()) plan.looked.assign(count, 0);
-      plan.looked[k] = (unsigned char)(x + 1);
-      ChainPlan::Lookup l = {};
-      l.consumer = k; l.top = (unsigned)top; l.cherry = cherry; l.nclasses = (unsigned)classes;
-      plan.lookups.push_back(l);
-      break;
-    }
-    producer[op.parent_clv_index] = (int)k;
-  }
-}
-
-// Deferred stores.  Folds and class tables took the READS of small tip-only subtrees out of the traversal; their
-// vectors were still written, 8 * S * R bytes per site each, although no operation of the list reads them from memory:
-//   a folded cherry             -- its consumer builds the block in registers;
-//   a looked-up child           -- its consumer gathers rows of the class table; the child's own chain (the cherry, or
-//                                  the cherry handed over in registers to the cherry x tip operation) feeds nobody else.
-// Such an operation is marked "parent vector not stored" (PlanOp::flags bit 0).  Coded tips and P-matrices alone
-// recompute it, so the engine keeps it as its operation (transient_mark, as for an evaluate-only traversal) and stores it
-// for the first reader or before an input changes.  Scaler counts are written as always.  The cherry below a looked-up
-// cherry x tip is marked only where that operation takes it over in registers.
-//   a tip-only run at the bottom of a chain (level 3)
-//                               -- a chain that starts with a cherry of coded tips hands its vector to the next operation
-//                                  in registers; where that one is "handed-over child x coded tip" its result depends on
-//                                  tip codes alone again, and so on up the chain.  An operation of such a run whose vector
-//                                  the next operation of the chain takes in registers is marked, the first `depth` of a
-//                                  run at the most (0: all of them): never the last operation of a chain, never a vector
-//                                  that an operation reads from memory.  plan.run_up links the marked operations of a
-//                                  run bottom-up (transient_materialize stores a run in one list).
-//   a vector inside a chain (level 4)
-//                               -- any operation whose vector the next operation of its chain (the one behind a folded
-//                                  cherry, if one stands between them) takes in registers, that operation being its only
-//                                  reader in the list: whatever its children are, however far up the chain.  The next
-//                                  evaluation overwrites it unread.  Never the last operation of a chain, never a vector
-//                                  that an operation reads from memory or that nobody in the list reads.  Everything
-//                                  level 3 marks is among them.  Such a vector is recomputed from stored child vectors,
-//                                  not from tip codes alone: the engine stores it before one of them is overwritten
-//                                  (transient_before_list).  plan.run_up links two marked operations that stand next to
-//                                  each other in a chain; across a folded cherry there is no link, and the reader of the
-//                                  lower one stores what it needs alone.
-// `plan`: after plan_folds and plan_lookups.
-// level 2: the looked-up children keep their stores (defer_stores)
-static void plan_defers(const Engine * e, const pll_operation_t * ops, unsigned count, unsigned level, unsigned depth, ChainPlan & plan)
-{
-  plan.deferred.clear();
-  plan.run_up.clear();
-  const bool folds_only = level == 2;
-  if ((level < 3 || count < 2) && plan.folded.empty() && (folds_only || plan.lookups.empty())) return;
-  plan.deferred.assign(count, 0);
-  for (unsigned k = 0; k < count && !plan.folded.empty(); ++k)
-    if (plan.folded[k]) plan.deferred[k] = 1;
-  if (folds_only) return;
-  for (const ChainPlan::Lookup & l : plan.lookups)
-  {
-    plan.deferred[l.top] = 1;
-    if (l.cherry < 0) continue;
-    const pll_operation_t & t = ops[l.top];
-    const unsigned side = t.child1_clv_index == ops[l.cherry].parent_clv_index ? 1u : 2u;
-    if (plan.carried[l.top] == side) plan.deferred[l.cherry] = 1;
-  }
-  if (level < 3 || count < 2) return;
-  std::vector<unsigned> readers(e->nodes, 0);
-  for (unsigned k = 0; k < count; ++k) { ++readers[ops[k].child1_clv_index]; ++readers[ops[k].child2_clv_index]; }
-  auto plain_tip = [&](unsigned idx, int scaler) { return coded_tip(e, idx) && scaler == PLL_SCALE_BUFFER_NONE; };
-  auto is_folded = [&](unsigned k) { return !plan.folded.empty() && plan.folded[k]; };
-  // the child of `o` that comes from operation `from` in registers (0: none)
-  auto taken_over = [&](unsigned o, unsigned from) -> unsigned
-  {
-    const unsigned side = plan.carried[o];
-    if (!side) return 0u;
-    return (side == 1 ? ops[o].child1_clv_index : ops[o].child2_clv_index) == ops[from].parent_clv_index ? side : 0u;
-  };
-  if (level >= 4)
-  {
-    // every vector inside a chain that goes up in registers and nowhere else, whatever its children are
-    for (const std::vector<unsigned> & ch : plan.chains)
-    {
-      size_t below = ch.size();                        // position of the operation marked last
-      for (size_t i = 0; i + 1 < ch.size(); ++i)
-      {
-        const unsigned k = ch[i];
-        if (is_folded(k)) continue;
-        const size_t next = i + 1 + (is_folded(ch[i + 1]) ? 1 : 0);
-        if (next >= ch.size() || !taken_over(ch[next], k) || readers[ops[k].parent_clv_index] != 1) continue;
-        plan.deferred[k] = 1;
-        // (linked to the one below only where the two stand next to each other: no folded cherry between them)
-        if (below + 1 == i)
-        {
-          if (plan.run_up.empty()) plan.run_up.assign(count, -1);
-          plan.run_up[ch[below]] = (int)k;
-        }
-        below = i;
-      }
-    }
-    return;
-  }
-  for (const std::vector<unsigned> & ch : plan.chains)
-  {
-    size_t i = 0;
-    while (i < ch.size() && is_folded(ch[i])) ++i;
-    if (i >= ch.size()) continue;
-    const pll_operation_t & c = ops[ch[i]];
-    if (!plain_tip(c.child1_clv_index, c.child1_scaler_index) || !plain_tip(c.child2_clv_index, c.child2_scaler_index)) continue;
-    int below = -1;                                  // the marked operation of the run under ch[i]
-    for (unsigned len = 1; i + 1 < ch.size() && (!depth || len <= depth); ++i, ++len)
-    {
-      const unsigned k = ch[i];
-      if (len > 1)
-      {
-        // handed-over child x coded tip
-        const unsigned side = taken_over(k, ch[i - 1]);
-        if (!side) break;
-        const pll_operation_t & o = ops[k];
-        if (!(side == 1 ? plain_tip(o.child2_clv_index, o.child2_scaler_index) : plain_tip(o.child1_clv_index, o.child1_scaler_index))) break;
-      }
-      // its vector goes up in registers and nowhere else (the next entry may be a cherry folded into the operation
-      // behind it: that operation is the one that takes the vector, and the run ends under it)
-      const size_t next = i + 1 + (is_folded(ch[i + 1]) ? 1 : 0);
-      if (next >= ch.size() || !taken_over(ch[next], k) || readers[ops[k].parent_clv_index] != 1) break;
-      plan.deferred[k] = 1;
-      if (below >= 0)
-      {
-        if (plan.run_up.empty()) plan.run_up.assign(count, -1);
-        plan.run_up[below] = (int)k;
-      }
-      below = (int)k;
-      if (next != i + 1) break;
-    }
-  }
-}
+  size_t off_table[2], off_flags[2], off_counts[2], off_rows[2];
+};
 
 // make DevicePlan::bytes resident on the device (stream-ordered; nothing is copied when the
 // device already holds exactly these bytes) and point `view` at it
@@ -2309,7 +1907,7 @@ static void fill_desc(const Engine * e, const pll_operation_t & op, OpDesc & d, 
 // The device-resident schedule of an operation list (chains in dependency order, DevicePlan) in e->plan:
 // built unless the cached one was made from the same list and settings.  mode 1: the whole traversal in
 // one launch (chains depth first); mode 0: one launch per round of chains.  false: the list does not have
-// the shape of a tree traversal (plan_chains).
+// the shape of a tree traversal (analyse_list, chain_plan.hpp).
 static std::atomic<unsigned long long> plan_generation{0};
 
 struct ScheduleRequest
@@ -2371,19 +1969,18 @@ static bool mark_wide_tips(Engine * e, const pll_operation_t * ops, unsigned cou
 // in use, the mode, the wide tips, and which operations are kept per class (the same list can meet other class nodes
 // of earlier calls)
 static std::vector<unsigned char> schedule_key(const ScheduleRequest & rq, unsigned lut_used, const std::vector<unsigned char> & wide,
-                                               bool fold, unsigned look_classes, unsigned defer)
+                                               bool fold, unsigned look_classes, DeferPolicy defer)
 {
   std::vector<unsigned char> tracked(rq.rp ? rq.count : 0, 0);
   if (rq.rp) for (unsigned k : rq.rp->cherry_ops) tracked[k] = 1;
   const size_t list_bytes = (size_t)rq.count * sizeof(pll_operation_t);
-  std::vector<unsigned char> key(4 * sizeof(unsigned) + list_bytes + wide.size() + tracked.size());
-  const unsigned mode_key = rq.mode | (rq.transient ? 0x100u : 0u) | (fold ? 0x200u : 0u) | (defer << 10);
-  memcpy(key.data(), &rq.count, sizeof(unsigned));
-  memcpy(key.data() + sizeof(unsigned), &lut_used, sizeof(unsigned));
-  memcpy(key.data() + 2 * sizeof(unsigned), &mode_key, sizeof(unsigned));
-  memcpy(key.data() + 3 * sizeof(unsigned), &look_classes, sizeof(unsigned));      // (the class limit of plan_lookups)
-  memcpy(key.data() + 4 * sizeof(unsigned), rq.ops, list_bytes);
-  if (!wide.empty()) memcpy(key.data() + 4 * sizeof(unsigned) + list_bytes, wide.data(), wide.size());
+  const unsigned mode_key = rq.mode | (rq.transient ? 0x100u : 0u) | (fold ? 0x200u : 0u);
+  // (look_classes: the class limit of plan_lookups; defer: the policy of plan_defers)
+  const unsigned head[] = {rq.count, lut_used, mode_key, look_classes, defer.level, defer.depth};
+  std::vector<unsigned char> key(sizeof(head) + list_bytes + wide.size() + tracked.size());
+  memcpy(key.data(), head, sizeof(head));
+  memcpy(key.data() + sizeof(head), rq.ops, list_bytes);
+  if (!wide.empty()) memcpy(key.data() + sizeof(head) + list_bytes, wide.data(), wide.size());
   if (!tracked.empty()) memcpy(key.data() + key.size() - tracked.size(), tracked.data(), tracked.size());
   return key;
 }
@@ -2419,19 +2016,21 @@ static bool reserve_pair_tables(Engine * e, const ScheduleRequest & rq, const pl
 // room in e->d_looktab for the tables of the children read by tip codes (plan_lookups): per child, and per cherry below
 // a cherry x tip child, the class table (blocked like a vector over the classes), its scaling flags and scaler counts
 // per class, and its rows through the branch above it.  Allocated here, with the schedule: a traversal allocates nothing
-static bool reserve_lookup_tables(Engine * e, ChainPlan & plan, unsigned lut_used)
+// room: per entry of plan.lookups, where its tables are
+static bool reserve_lookup_tables(Engine * e, const ChainPlan & plan, unsigned lut_used, std::vector<LookupRoom> & room)
 {
+  room.assign(plan.lookups.size(), LookupRoom());
   if (plan.lookups.empty()) return true;
   size_t need = 0;
   auto take = [&](size_t bytes) { const size_t at = need; need += (bytes + 255) & ~(size_t)255; return at; };
-  for (ChainPlan::Lookup & l : plan.lookups)
-    for (int x = 0; x < (l.cherry >= 0 ? 2 : 1); ++x)
+  for (size_t i = 0; i < plan.lookups.size(); ++i)
+    for (int x = 0; x < (plan.lookups[i].cherry >= 0 ? 2 : 1); ++x)
     {
-      const size_t classes = x ? (size_t)lut_used * lut_used : l.nclasses, npblk = (classes + S20_BS - 1) / S20_BS;
-      l.off_table[x] = take(npblk * e->R * S20_UNIT * sizeof(double));
-      l.off_flags[x] = take(npblk * S20_BS);
-      l.off_counts[x] = take(npblk * S20_BS * sizeof(unsigned));
-      l.off_rows[x] = take(classes * e->R * e->S * sizeof(double));
+      const size_t classes = x ? (size_t)lut_used * lut_used : plan.lookups[i].nclasses, npblk = (classes + S20_BS - 1) / S20_BS;
+      room[i].off_table[x] = take(npblk * e->R * S20_UNIT * sizeof(double));
+      room[i].off_flags[x] = take(npblk * S20_BS);
+      room[i].off_counts[x] = take(npblk * S20_BS * sizeof(unsigned));
+      room[i].off_rows[x] = take(classes * e->R * e->S * sizeof(double));
     }
   if (need <= e->looktab_cap) return true;
   if (hipStreamSynchronize(e->stream) != hipSuccess) return false;      // a running traversal may still read the old tables
@@ -2441,66 +2040,6 @@ static bool reserve_lookup_tables(Engine * e, ChainPlan & plan, unsigned lut_use
   if (!dev_alloc(&e->d_looktab, need, "class tables of looked-up children")) return false;
   e->looktab_cap = need;
   return true;
-}
-
-// Order of the chains.  By rounds: round by round, longest chains first within a round (their workgroups are
-// dispatched first).  Otherwise depth first, so that a vector is consumed soon after it was written (the kernel
-// walks slabs of sites through ALL chains: what a slab wrote a few chains ago is still in L2 / the memory-side
-// cache).  The chains form a tree -- chain c feeds the chain that reads c's last vector as a child from memory --
-// and the larger feeder goes first, which keeps the number of results waiting for their consumer small.
-static std::vector<size_t> chain_order(const Engine * e, const pll_operation_t * ops, unsigned count, const ChainPlan & plan,
-                                       bool by_rounds)
-{
-  const size_t nch = plan.chains.size();
-  std::vector<size_t> order;
-  order.reserve(nch);
-  if (by_rounds)
-  {
-    for (size_t c = 0; c < nch; ++c) order.push_back(c);
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b)
-    {
-      if (plan.launch[a] != plan.launch[b]) return plan.launch[a] < plan.launch[b];
-      return plan.chains[a].size() > plan.chains[b].size();
-    });
-    return order;
-  }
-  std::vector<int> chain_at(count, -1), producer_op(e->nodes, -1);
-  std::vector<unsigned> weight(nch, 0);
-  std::vector<std::vector<size_t>> feeders(nch);
-  std::vector<char> is_feeder(nch, 0);
-  for (size_t c = 0; c < nch; ++c)
-    for (unsigned k : plan.chains[c]) { chain_at[k] = (int)c; producer_op[ops[k].parent_clv_index] = (int)k; }
-  for (size_t c = 0; c < nch; ++c)                  // chains are numbered in creation order: feeders first
-  {
-    weight[c] += (unsigned)plan.chains[c].size();
-    for (unsigned k : plan.chains[c])
-    {
-      const unsigned child[2] = {ops[k].child1_clv_index, ops[k].child2_clv_index};
-      for (int x = 0; x < 2; ++x)
-      {
-        const int pk = producer_op[child[x]];
-        if (pk < 0 || pk >= (int)k || chain_at[pk] == (int)c) continue;
-        feeders[c].push_back((size_t)chain_at[pk]);
-        is_feeder[chain_at[pk]] = 1;
-        weight[c] += weight[chain_at[pk]];
-      }
-    }
-  }
-  std::vector<std::pair<size_t, size_t>> stack;   // (chain, next feeder)
-  for (size_t root = 0; root < nch; ++root)
-  {
-    if (is_feeder[root]) continue;
-    stack.emplace_back(root, 0);
-    while (!stack.empty())
-    {
-      const size_t c = stack.back().first;
-      if (stack.back().second == 0)
-        std::stable_sort(feeders[c].begin(), feeders[c].end(), [&](size_t a, size_t b) { return weight[a] > weight[b]; });
-      if (stack.back().second < feeders[c].size()) { const size_t f = feeders[c][stack.back().second++]; stack.emplace_back(f, 0); }
-      else { order.push_back(c); stack.pop_back(); }
-    }
-  }
-  return order;
 }
 
 // the row table of class node `c` through matrix `matrix` (the branch above it): its job, and where it will be
@@ -2722,16 +2261,17 @@ static void emit_repeat_levels(const Engine * e, const ChainFamily & f, const Sc
 //   the rows of those through the branch above them (pack_schedule's last level).
 // The consumers' entries get the tip code arrays, the rows and the counts (PlanOp::flags bit 5).
 static void emit_lookup_tables(const Engine * e, const ChainFamily & f, const pll_operation_t * ops, const ChainPlan & plan,
-                               unsigned lut_used, DevicePlan & dp, ScheduleBuild & sb)
+                               const std::vector<LookupRoom> & room, unsigned lut_used, DevicePlan & dp, ScheduleBuild & sb)
 {
   if (plan.lookups.empty()) return;
   const size_t lut_stride = (size_t)e->R * e->lut_codes * e->S;
   const unsigned pairs = lut_used * lut_used;
   std::vector<int> entry_of(e->nodes, -1);
   for (unsigned i = 0; i < sb.nops; ++i) entry_of[sb.pops[i].d.parent_index] = (int)i;
-  auto table = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<double *>(e->d_looktab + l.off_table[x]); };
-  auto counts = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<unsigned *>(e->d_looktab + l.off_counts[x]); };
-  auto rows = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<double *>(e->d_looktab + l.off_rows[x]); };
+  auto room_of = [&](const ChainPlan::Lookup & l) -> const LookupRoom & { return room[&l - plan.lookups.data()]; };
+  auto table = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<double *>(e->d_looktab + room_of(l).off_table[x]); };
+  auto counts = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<unsigned *>(e->d_looktab + room_of(l).off_counts[x]); };
+  auto rows = [&](const ChainPlan::Lookup & l, int x) { return reinterpret_cast<double *>(e->d_looktab + room_of(l).off_rows[x]); };
   // the matrix of the branch above `child` in operation o
   auto matrix_above = [&](const pll_operation_t & o, unsigned child)
   { return o.child1_clv_index == child ? o.child1_matrix_index : o.child2_matrix_index; };
@@ -2746,7 +2286,7 @@ static void emit_lookup_tables(const Engine * e, const ChainFamily & f, const pl
     j.lut2 = e->d_lut + lut_stride * c.child2_matrix_index; j.rows2 = e->lut_codes;
     j.nclasses = pairs;
     j.table = table(l, x);
-    j.flags = e->d_looktab + l.off_flags[x];
+    j.flags = e->d_looktab + room_of(l).off_flags[x];
     j.counts = c.parent_scaler_index >= 0 ? counts(l, x) : nullptr;
     sb.cherry_jobs.push_back(j);
   }
@@ -2775,7 +2315,7 @@ static void emit_lookup_tables(const Engine * e, const ChainFamily & f, const pl
     j.cnt1 = (cherry_first ? t.child1_scaler_index : t.child2_scaler_index) >= 0 ? counts(l, 1) : nullptr;
     j.nclasses = l.nclasses;
     j.table = table(l, 0);
-    j.flags = e->d_looktab + l.off_flags[0];
+    j.flags = e->d_looktab + room_of(l).off_flags[0];
     j.counts = t.parent_scaler_index >= 0 ? counts(l, 0) : nullptr;
     sb.cherry_jobs.push_back(j);
     L1.max_classes = std::max(L1.max_classes, l.nclasses);
@@ -2873,21 +2413,24 @@ static bool prepare_schedule(Engine * e, const pll_partition_t * p, const ChainF
   // (children read through class tables: where folds are planned, in storing traversals)
   const unsigned look_classes = fold_lds && f.look_classes && !rq.transient && !e->transient_mode ? f.look_classes(e, lut_used) : 0u;
   // (deferred stores: where folds are planned, in storing traversals)
-  const unsigned defer = fold_lds ? defer_stores(e, f, rq.transient) : 0u;
+  const DeferPolicy defer = fold_lds ? defer_stores(e, f, rq.transient) : DeferPolicy();
   std::vector<unsigned char> key = schedule_key(rq, lut_used, wide, fold_lds != 0, look_classes, defer);
   if (!dp.key.empty() && dp.key == key) return true;
   if ((nwide || rq.rp) && !reserve_pair_tables(e, rq, ops, count, wide)) return false;
+  const PlannedList pl(e, &f, ops, count, lut_used, &wide);
+  if (!pl.accepted) return false;
   ChainPlan plan;
-  if (!plan_chains(e, &f, ops, count, f.chain_max, f.chain_lds, lut_used, plan, &wide)) return false;
-  plan_folds(e, f, ops, count, f.chain_max, f.chain_lds, lut_used, fold_lds, plan);
-  plan_lookups(e, ops, count, lut_used, look_classes, plan);
-  if (defer) plan_defers(e, ops, count, defer & 255u, defer >> 8, plan);
-  if (!reserve_lookup_tables(e, plan, lut_used)) return false;
+  plan_chains(pl.list, pl.facts, f.chain_max, f.chain_lds, plan);
+  plan_folds(pl.list, pl.facts, f.chain_max, f.chain_lds, fold_lds, plan);
+  plan_lookups(pl.facts, lut_used, look_classes, plan);
+  if (defer.level) plan_defers(pl.facts, defer, plan);
+  std::vector<LookupRoom> room;
+  if (!reserve_lookup_tables(e, plan, lut_used, room)) return false;
   ScheduleBuild sb;
   sb.pops.resize(count);
-  emit_chains(e, f, ops, plan, chain_order(e, ops, count, plan, rq.mode == 0), wide, lut_used, rq, dp, sb);
+  emit_chains(e, f, ops, plan, chain_order(pl.facts, plan, rq.mode == 0), wide, lut_used, rq, dp, sb);
   emit_repeat_levels(e, f, rq, dp, sb);
-  emit_lookup_tables(e, f, ops, plan, lut_used, dp, sb);
+  emit_lookup_tables(e, f, ops, plan, room, lut_used, dp, sb);
   pack_schedule(dp, sb, lut_used);
   close_launch(dp, sb);                           // (the last launch also carries the class operations' bytes)
   if (rq.mode == 0) merge_single_chain_rounds(dp);
@@ -3257,22 +2800,14 @@ struct LevelPlan
 // idle -- are folded into the operation that consumes them (kernels_s61.hpp, k_partials_s61v4).
 // (2) Those that stay (their consumer already folds its other child) run as LATE as the consumer
 // allows, so that they share a launch with matrix-bound operations.  Both only for lists with the
-// shape of a tree traversal (plan_chains' test); PLLHIP_S61_CHERRIES=0 / PLLHIP_S61_ALAP=0 switch
+// shape of a tree traversal (analyse_list); PLLHIP_S61_CHERRIES=0 / PLLHIP_S61_ALAP=0 switch
 // them off.
 static int fold_s61_cherries(Engine * e, const pll_operation_t * ops, unsigned count, LevelPlan & lp)
 {
   static const int use_alap = getenv("PLLHIP_S61_ALAP") ? atoi(getenv("PLLHIP_S61_ALAP")) : 1;
-  ChainPlan shape;
-  if (!plan_chains(e, nullptr, ops, count, 1, ~0u, 1u, shape)) return PLL_SUCCESS;
-  std::vector<int> producer(e->nodes, -1), consumer(count, -1), prod1(count, -1), prod2(count, -1);
-  for (unsigned k = 0; k < count; ++k)
-  {
-    prod1[k] = producer[ops[k].child1_clv_index];
-    prod2[k] = producer[ops[k].child2_clv_index];
-    if (prod1[k] >= 0) consumer[prod1[k]] = (int)k;
-    if (prod2[k] >= 0) consumer[prod2[k]] = (int)k;
-    producer[ops[k].parent_clv_index] = (int)k;
-  }
+  const PlannedList shape(e, nullptr, ops, count, 1u);
+  if (!shape.accepted) return PLL_SUCCESS;
+  const std::vector<int> & producer = shape.facts.producer, & consumer = shape.facts.consumer;
   auto is_cherry = [&](unsigned k) { return tip_coded(e, ops[k].child1_clv_index) && tip_coded(e, ops[k].child2_clv_index); };
   std::vector<char> folded(count, 0);
   if (s61_cherries_supported(e))
@@ -3294,8 +2829,8 @@ static int fold_s61_cherries(Engine * e, const pll_operation_t * ops, unsigned c
     {
       if (folded[k]) { lp.level[k] = -1; continue; }
       int l = 0;
-      if (prod1[k] >= 0 && !folded[prod1[k]]) l = std::max(l, lp.level[prod1[k]] + 1);
-      if (prod2[k] >= 0 && !folded[prod2[k]]) l = std::max(l, lp.level[prod2[k]] + 1);
+      for (int p : {producer[2 * k], producer[2 * k + 1]})
+        if (p >= 0 && !folded[p]) l = std::max(l, lp.level[p] + 1);
       lp.level[k] = l;
       lp.max_level = std::max(lp.max_level, l);
     }
@@ -3460,9 +2995,16 @@ static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops
       for (unsigned k : rp.cherry_ops) e->cherries[ops[k].parent_clv_index].valid = false;     // the plain paths below compute them
   }
   if (!plain_scalers(e, ops, count)) return PLL_FAILURE;
-  ChainPlan plan;
-  if (f && f->chains && plan_chains(e, f, ops, count, f->chain_max, f->chain_lds, lut_used, plan))
-    return run_chains_by_value(e, *f, ops, count, lut_used, plan);
+  if (f && f->chains)
+  {
+    const PlannedList pl(e, f, ops, count, lut_used);
+    if (pl.accepted)
+    {
+      ChainPlan plan;
+      plan_chains(pl.list, pl.facts, f->chain_max, f->chain_lds, plan);
+      return run_chains_by_value(e, *f, ops, count, lut_used, plan);
+    }
+  }
   LevelPlan lp;
   if (!plan_levels(e, ops, count, lp)) return PLL_FAILURE;
   return run_levels(e, ops, count, lp);
