@@ -300,12 +300,18 @@ PLL_EXPORT unsigned int pllhip_free_trial_lengths(const pll_partition_t * partit
    target function is src/optimize/pll_optimize.c:1223-1287) for ONE partition whose sumtable is current
    (pll_update_sumtable), in ONE launch: scan, in-launch reduction, step rule, next scan.  The iterates are the
    host loop's, bit for bit (same scan, same summation order, the same fp64 expressions without contraction).
+   max_newton: 1 ... PLLHIP_NEWTON_MAX_ITERATIONS; a loop makes at most max_newton + 2 scans, the last of which finds
+   the limit exceeded.  Any two loops may follow one another on a partition, whatever their limits and however they
+   ended.
    Returns PLL_SUCCESS with *length = the length the loop ended at and *iterations = scans made; `trail`
-   (NULL, or room for 96 doubles) receives the iterate after every scan.  PLL_FAILURE with pll_errno =
-   PLLHIP_ERROR_NEWTON_LIMIT (more than max_newton iterations) / PLLHIP_ERROR_NEWTON_DERIVATIVES (a non-finite
-   derivative) -- the reference's two failure modes -- or PLLHIP_ERROR_NEWTON_UNSUPPORTED: this partition cannot
+   (NULL, or room for 96 doubles) receives the iterate after each of the first min(*iterations, 96) scans -- of a
+   longer loop the later iterates are not kept, *length and *iterations are complete.  PLL_FAILURE with pll_errno =
+   PLLHIP_ERROR_NEWTON_LIMIT (more than max_newton iterations; *iterations = max_newton + 2) /
+   PLLHIP_ERROR_NEWTON_DERIVATIVES (a non-finite derivative) -- the reference's two failure modes; *length,
+   *iterations and `trail` are set as on success -- or PLLHIP_ERROR_NEWTON_UNSUPPORTED: this partition cannot
    run the loop on the device (4-state / generic kernel family, ascertainment-bias correction, a partition spread
-   over devices, a scan grid larger than the chip holds at once); the caller then iterates itself.
+   over devices, a scan grid larger than the chip holds at once, max_newton 0 or above
+   PLLHIP_NEWTON_MAX_ITERATIONS); the caller then iterates itself.
    PLLHIP_ERROR_NEWTON_STUCK: the workgroups of the loop wait for one another inside the launch, so all of them
    have to be on the chip at once; the grid is sized for a device this partition has to itself, and other work on
    the device (another process, another stream) can keep a workgroup out.  Every wait is bounded: the launch then
@@ -315,6 +321,7 @@ PLL_EXPORT unsigned int pllhip_free_trial_lengths(const pll_partition_t * partit
 #define PLLHIP_ERROR_NEWTON_DERIVATIVES  911
 #define PLLHIP_ERROR_NEWTON_UNSUPPORTED  912
 #define PLLHIP_ERROR_NEWTON_STUCK        913
+#define PLLHIP_NEWTON_MAX_ITERATIONS     65536        /* 2^16 */
 PLL_EXPORT int pllhip_newton_branch(pll_partition_t * partition,
                                     int parent_scaler_index, int child_scaler_index,
                                     const unsigned int * params_indices, const double * sumtable,

@@ -19,6 +19,7 @@
 
 #include "pll.h"
 #include "pllhip.h"
+#include "newton_range.hpp"
 
 namespace pllhip {
 
@@ -347,7 +348,8 @@ struct Engine
   void * d_newton = nullptr;
   double * h_newton = nullptr;        // pinned + mapped: [0..7] results, [8..103] trail, [112] sequence word
   double * hd_newton = nullptr;
-  unsigned long long newton_seq = 0;
+  unsigned long long newton_seq = 0;  // loops started with this engine's control block (the host flag's value)
+  newton_range::Counter newton_iter;  // values of the control block's `iter` handed out to them (newton_range.hpp)
   int newton_capacity = -1;           // co-resident workgroups of the loop kernel (-1: not asked yet)
   int newton_resident = 0;            // blocks per wave that k_newton_mfma_resident keeps in registers (0: the streaming loop)
   const void * newton_fn = nullptr;   // the loop kernel of a partition on its own: the resident form where it fits, else the streaming one

@@ -1471,7 +1471,11 @@ struct NewtonControl          // device memory, one per engine
 // part / nparts / xscale: this launch is partition `part` of `nparts` that share the branch (nparts = 1: alone); it scans
 // its sumtable at xscale * x and leaves its totals in ro.dst, a scratch of its own
 // iter_base: the control block is not written by the host before a launch (a copy per branch saved): the loop counts its
-// scans from a base no earlier launch has used (the waiters compare `iter` with iter_base + it + 1), takes the bracket
+// scans from a base of its own (the waiters compare `iter` with iter_base + it + 1, modulo 2^32).  The host takes the
+// base from a running 32-bit counter per control block that advances by max_newton + 2 per loop -- the values a loop
+// can publish, scans 0 .. max_newton + 1 -- and never hands out 0 (newton_range.hpp), so `iter` as an earlier loop
+// left it, at whichever scan that loop ended, or as a memset left it, is no value this loop waits for; max_newton is
+// at most newton_range::MAX_NEWTON.  The loop takes the bracket
 // of its first step from here (every partition leaves its scaler next to its totals), and relies on `arrived` being zero
 // between loops (the last arriver of every scan resets it; a loop that was given up is followed by a memset,
 // newton_finish)

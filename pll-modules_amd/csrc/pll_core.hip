@@ -3941,18 +3941,23 @@ static NewtonParams newton_params(double start, double bl_min, double bl_max, do
   return np;
 }
 
+static_assert(newton_range::MAX_NEWTON == PLLHIP_NEWTON_MAX_ITERATIONS, "include/pllhip.h documents the bound of max_newton");
+
 // what the launches of one loop share: the control block in the lead partition's device memory, where the results go
 struct NewtonRun { NewtonControl * ctl; double * host_out; unsigned long long * host_flag; unsigned long long seq; };
 
 // Starts a loop on `lead`, on whose stream the caller has ordered everything that used the control block before.  The
-// block is initialised from the kernel arguments -- NewtonParams::iter_base, this loop's own range of `iter` values --;
+// block is initialised from the kernel arguments -- NewtonParams::iter_base, the start of this loop's own range of
+// `iter` values: the block's running counter (Engine::newton_iter) advances by the max_newton + 2 values the loop may
+// publish, so no value it publishes or waits for is one an earlier loop can have left in the block, however many scans
+// that loop made (newton_range.hpp; the entry points bound max_newton by newton_range::MAX_NEWTON) --;
 // with PLLHIP_NEWTON_DEBUG the counters of the dump are reset by a copy (pageable source, staged by the runtime before
 // the call returns).  nscales partitions with length_scalers (null: 1.0); 0: a loop of one partition, its scale in np.
 static int newton_begin(Engine * lead, NewtonParams & np, const double * length_scalers, unsigned nscales, NewtonRun & run)
 {
   run.ctl = static_cast<NewtonControl *>(lead->d_newton);
   run.seq = ++lead->newton_seq;
-  np.iter_base = (unsigned)(run.seq << 8);
+  np.iter_base = newton_range::take(lead->newton_iter, np.max_newton);
   if (np.debug)
   {
     NewtonControl init;
@@ -4044,9 +4049,10 @@ int pllhip_newton_branch(pll_partition_t * p, int parent_scaler_index, int child
                          double start, double bl_min, double bl_max, double tolerance, unsigned int max_newton,
                          double * length, unsigned int * iterations, double * trail)
 {
-  if (!max_newton)
+  if (!newton_range::supported(max_newton))
   {
-    set_error(PLLHIP_ERROR_NEWTON_UNSUPPORTED, "this partition does not run the Newton-Raphson loop on the device");
+    set_error(PLLHIP_ERROR_NEWTON_UNSUPPORTED, "the device-resident Newton-Raphson loop takes an iteration limit of 1 to %u",
+              (unsigned)newton_range::MAX_NEWTON);
     return PLL_FAILURE;
   }
   NewtonLaunch L;
@@ -4174,9 +4180,10 @@ int pllhip_newton_branch_multi(pll_partition_t * const * partitions, unsigned in
   if (count == 1 && (!length_scalers || length_scalers[0] == 1.0))
     return pllhip_newton_branch(partitions[0], parent_scaler_index, child_scaler_index, params_indices[0], sumtables[0],
                                 start, bl_min, bl_max, tolerance, max_newton, length, iterations, trail);
-  if (!count || count > NEWTON_MAX_PARTS || !max_newton)
+  if (!count || count > NEWTON_MAX_PARTS || !newton_range::supported(max_newton))
   {
-    set_error(PLLHIP_ERROR_NEWTON_UNSUPPORTED, "1 to %u partitions per device-resident Newton-Raphson loop", NEWTON_MAX_PARTS);
+    set_error(PLLHIP_ERROR_NEWTON_UNSUPPORTED, "1 to %u partitions and an iteration limit of 1 to %u per device-resident "
+              "Newton-Raphson loop", NEWTON_MAX_PARTS, (unsigned)newton_range::MAX_NEWTON);
     return PLL_FAILURE;
   }
   for (unsigned k = 0; k < count; ++k)

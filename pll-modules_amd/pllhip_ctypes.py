@@ -779,6 +779,24 @@ class PllLib:
         return out
 
 
+PLLHIP_ERROR_NEWTON_LIMIT, PLLHIP_ERROR_NEWTON_DERIVATIVES = 910, 911
+PLLHIP_ERROR_NEWTON_UNSUPPORTED, PLLHIP_ERROR_NEWTON_STUCK = 912, 913
+PLLHIP_NEWTON_MAX_ITERATIONS = 1 << 16
+
+
+class NewtonError(RuntimeError):
+    """pllhip_newton_branch / pllhip_newton_branch_multi failed: "[pll_errno] message", and what the call left in its
+    outputs -- after PLLHIP_ERROR_NEWTON_LIMIT / _DERIVATIVES the scans made, the length the loop stood at and the
+    iterates; untouched (0, nan) where no loop ran"""
+
+    def __init__(self, lib, length, iterations, trail):
+        self.errno = lib.errno
+        super().__init__(f"[{self.errno}] {lib.errmsg}")
+        self.length = length
+        self.iterations = iterations
+        self.trail = trail[:min(iterations, len(trail))]
+
+
 class Instance:
     """A partition plus the index bookkeeping of one (tree, model, alignment)."""
 
@@ -960,14 +978,15 @@ class Instance:
         return df.value, ddf.value
 
     def newton_branch(self, psc, csc, st, start, bl_min, bl_max, tolerance, max_newton):
-        """pllhip_newton_branch: (length, iterations, trail) or raises with the library's message"""
-        length, its = C.c_double(), C.c_uint()
+        """pllhip_newton_branch: (length, iterations, trail) -- the trail holds the first 96 iterates of a longer
+        loop -- or raises NewtonError with the library's message"""
+        length, its = C.c_double(float("nan")), C.c_uint(0)
         trail = np.zeros(96)
         self.lib.errno = 0
         ok = self.L.pllhip_newton_branch(self.p, psc, csc, self.params_p, st, start, bl_min, bl_max, tolerance,
                                          max_newton, C.byref(length), C.byref(its), trail.ctypes.data_as(c_double_p))
         if not ok:
-            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+            raise NewtonError(self.lib, length.value, its.value, trail)
         return length.value, its.value, trail[:its.value]
 
     def derivatives_multi(self, psc, csc, ts, st):
@@ -1955,20 +1974,20 @@ def build_instance(lib, states, rate_cats, ntips, nsites, coded=True, scalers=Tr
 
 def newton_branch_multi(lib, insts, psc, csc, sumtables, scalers, start, bl_min, bl_max, tolerance, max_newton):
     """pllhip_newton_branch_multi over `insts` (their own sumtables, optional branch-length scalers):
-    (length, iterations, trail) or raises with the library's message"""
+    (length, iterations, trail) or raises NewtonError with the library's message"""
     n = len(insts)
     parts = (C.POINTER(Partition) * n)(*[i.p for i in insts])
     params = (c_uint_p * n)(*[i.params_p for i in insts])
     sts = (c_double_p * n)(*[C.cast(s_, c_double_p) for s_ in sumtables])
     sc = _f64(scalers) if scalers is not None else None
-    length, its = C.c_double(), C.c_uint()
+    length, its = C.c_double(float("nan")), C.c_uint(0)
     trail = np.zeros(96)
     lib.errno = 0
     ok = lib.lib.pllhip_newton_branch_multi(parts, n, psc, csc, params, sts, sc.ctypes.data_as(c_double_p) if sc is not None else None,
                                             start, bl_min, bl_max, tolerance, max_newton, C.byref(length), C.byref(its),
                                             trail.ctypes.data_as(c_double_p))
     if not ok:
-        raise RuntimeError(f"[{lib.errno}] {lib.errmsg}")
+        raise NewtonError(lib, length.value, its.value, trail)
     return length.value, its.value, trail[:its.value]
 
 

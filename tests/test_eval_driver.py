@@ -569,6 +569,61 @@ def test_device_newton_over_several_partitions(product, spec, scalers):
             a.close()
 
 
+def _summed_derivatives(parts, scalers):
+    """the target function of a branch that partitions share (src/optimize/pll_optimize.c:1223-1287), added in
+    partition order as in test_device_newton_over_several_partitions"""
+    def deriv(x):
+        f = df = 0.0
+        for p, s_ in zip(parts, scalers):
+            fp, dfp = p.derivatives(s_ * x)
+            f += s_ * fp
+            df += s_ * s_ * dfp
+        return f, df
+    return deriv
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first", ["converged_after_257", "limit_after_257"])
+@pytest.mark.parametrize("spec,scalers", [([4, 20], [1.0, 0.7]), ([20, 61], None)])
+def test_device_newton_back_to_back_over_several_partitions(product, spec, scalers, first):
+    """tests/test_newton_loop_control.py, test_loops_back_to_back, for partitions that share the branch (5 000 sites, 800
+    at 61 states: every partition more than one workgroup): after a loop of 257 scans -- converged at bl_min, or given up
+    at the iteration limit -- the next loop on the same partitions makes the summed host loop's iterates, bit for bit, so
+    does a third, and every partition's blocking derivative call returns what it returned before"""
+    import newton_cases as nc
+    _needs_a_queue_per_stream(spec)
+    loop_a = {"converged_after_257": nc.LONG_257, "limit_after_257": nc.LIMIT_257}[first]
+    parts = [nc.Part(product, s_, seed_shift=k) for k, s_ in enumerate(spec)]
+    try:
+        insts, sts = [p.inst for p in parts], [p.st for p in parts]
+        deriv = _summed_derivatives(parts, scalers or [1.0] * len(parts))
+
+        def run(loop):
+            return pc.newton_branch_multi(product, insts, parts[0].sa, parts[0].sb, sts, scalers, loop.start,
+                                          nc.BL_MIN, nc.BL_MAX, loop.tol, loop.max_newton)
+        for p in parts:
+            p.load(nc.ORDINARY.data)
+        before = [p.derivatives(0.3) for p in parts]
+        course_b = nc.host_course(deriv, nc.ORDINARY)
+        nc.check_course(course_b, nc.ORDINARY)
+
+        for p in parts:
+            p.load(loop_a.data)
+        course_a = nc.host_course(deriv, loop_a)
+        nc.check_course(course_a, loop_a)
+        print(f"states {spec}: {first}: {course_a.evaluations} evaluations of the host loop, the ordinary loop {course_b.evaluations}")
+        nc.run_and_compare(run, loop_a, course_a)
+
+        for p in parts:
+            p.load(nc.ORDINARY.data)
+        nc.run_and_compare(run, nc.ORDINARY, course_b)
+        nc.run_and_compare(run, nc.ORDINARY, course_b)
+        assert [p.derivatives(0.3) for p in parts] == before
+    finally:
+        for p in parts:
+            p.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("linkage", [0, 1])
 def test_driver_with_device_newton_over_partitions(product, linkage):
