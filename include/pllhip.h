@@ -634,6 +634,55 @@ PLL_EXPORT int pllhip_node_ancestral_finish(pllhip_anc_batch_t * batch);
    of a sharded partition), and its staging chunks (the largest count of any device) */
 PLL_EXPORT void pllhip_node_ancestral_last_times(double * kernel_ms, unsigned long long * chunks);
 
+/* ---- simulated alignments: the parametric bootstrap ("Simulated alignments") ----
+ * Replicates of an alignment drawn from the partition's own model -- rate categories and their weights, p-inv and
+ * frequencies of params_indices[category], and the transition matrices as pll_update_prob_matrices left them -- along
+ * a tree given as edges (parent -> child, matrix).  The distribution is the one the edge log-likelihood evaluates.
+ * Every draw is a counter-based number of (seed, replicate, stream, absolute site), stream = 3 + matrix index for an
+ * edge: the bytes are a function of (seed, replicate, site, model, tree with its matrix indices, root) alone, not of
+ * the order of the edge list, of the site or replicate range a call asks for, of chunks or grids.  Edges that share a
+ * matrix index share their draws.
+ * The calls change nothing in the partition (no vector, scaler or result); queued matrix requests are flushed first.
+ * A sharded partition is served from its first shard's matrices.  Partitions with an ascertainment-bias attribute are
+ * refused.  The output goes through a device staging buffer of PLLHIP_SIM_STAGING_BYTES (environment, read at the
+ * call; default 1 GiB, never less than one chunk of 1024 sites of every row), in chunks over replicates and site
+ * ranges; PLLHIP_SIM_BLOCKS (environment, read at the call; unset or 0: no cap) caps the workgroups of a launch.
+ * Results depend on neither. */
+#define PLLHIP_SIM_INNER (1u << 0)   /* also return the rows of the inner nodes (the true ancestors) */
+
+typedef struct pllhip_sim_params
+{
+  unsigned long long seed;
+  unsigned long long first_site;     /* absolute number of column 0 */
+  unsigned int sites;                /* columns per replicate */
+  unsigned int first_replicate;      /* absolute number of replicate 0; first_replicate + replicates <= 2^32 */
+  unsigned int replicates;
+  unsigned int flags;                /* PLLHIP_SIM_* */
+  const char * alphabet;             /* NULL: the output holds state indices; else at least `states` characters and the
+                                        output holds alphabet[state] (ready for pll_set_tip_states) */
+} pllhip_sim_params_t;
+
+/* Nodes are numbered like CLVs (< partition->tips: a tip), all < node_count; edges in any order; root_node is an inner
+   node.  out[replicate][row][site], one byte each, row = node index: partition->tips rows, node_count rows with
+   PLLHIP_SIM_INNER (rows of nodes the list does not name are 0xFF).  PLL_ERROR_PARAM_INVALID, with nothing written to
+   `out`, for sites or replicates of 0, an index out of range, a list that is not a tree over the nodes it names (a
+   node reached twice, a tip used as a parent, a node never reached from the root), a missing tip, an alphabet shorter
+   than the states, or an ascertainment-bias attribute. */
+PLL_EXPORT int pllhip_simulate_edges(pll_partition_t * partition, const pllhip_sim_params_t * params,
+                                     unsigned int root_node, unsigned int edge_count, const unsigned int * parent,
+                                     const unsigned int * child, const unsigned int * matrix_indices,
+                                     const unsigned int * params_indices, unsigned int node_count, unsigned char * out);
+/* The same for a tree walked from `root` (an inner node): rows are clv_index, matrices pmatrix_index, node_count =
+   tips + clv_buffers.  update_matrices != 0: every edge's matrix is first requested from its `length`
+   (pll_update_prob_matrices with params_indices). */
+PLL_EXPORT int pllhip_simulate_utree(pll_partition_t * partition, const pllhip_sim_params_t * params,
+                                     const pll_unode_t * root, const unsigned int * params_indices, int update_matrices,
+                                     unsigned char * out);
+/* this thread's last simulation: device time of the table kernel and of the evolve kernels in ms between HIP events,
+   the copies (device to pinned memory, and from there into `out`) in ms, and the staging chunks */
+PLL_EXPORT void pllhip_simulate_last_times(double * tables_ms, double * kernel_ms, double * copy_ms,
+                                           unsigned long long * chunks);
+
 /* ---- topology tests and bootstrap weights ("Topology tests and bootstrap weights"; DESIGN.md
  *      section 20) ----
  * A site-likelihood set holds, on the device pllhip_get_device() names at its creation, a matrix L[trees][patterns]

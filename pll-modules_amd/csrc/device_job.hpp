@@ -86,6 +86,17 @@ inline bool caller_device(const char * who, int * device)
 // stream and complete on return (pll_core.hip)
 bool tip_pointer_tables(Engine * e, DevBuf<const double *> & clv, DevBuf<const uint8_t *> & codes);
 
+// the transition matrices and the model block of the engine that executes for `p` (its own, or its first shard's, which
+// gets the caller's model arrays first), as they stand once the queued matrix requests and a changed model have gone to
+// the device on that engine's stream; the offsets are in doubles from `model` (pll_core.hip)
+struct MatrixTables
+{
+  const double * pmat = nullptr;                   // [matrix][rate][S][Sp]
+  const double * model = nullptr;
+  unsigned off_weights = 0, off_pinv = 0, off_freqs = 0;
+};
+bool matrix_tables(pll_partition_t * p, MatrixTables & out);
+
 inline unsigned grid_for(size_t items, unsigned per_block)
 {
   return (unsigned)std::max<size_t>(1, std::min<size_t>((items + per_block - 1) / per_block, 4096));

@@ -5,9 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rell_mix.hpp"
+
 namespace pllhip {
 
-typedef unsigned long long rell_u64;
 typedef double rell_v4d __attribute__((ext_vector_type(4)));
 
 constexpr unsigned RELL_WG = 256;
@@ -22,15 +23,6 @@ __host__ __device__ inline unsigned rell_chunk_len(unsigned S)
   const unsigned per = (S + RELL_CHUNKS_MAX - 1) / RELL_CHUNKS_MAX;
   const unsigned len = per > RELL_CHUNK_MIN ? per : RELL_CHUNK_MIN;
   return (len + RELL_TILE - 1) / RELL_TILE * RELL_TILE;
-}
-
-// SplitMix64 output number c + 1 of the stream `seed`
-__host__ __device__ inline rell_u64 rell_mix(rell_u64 seed, rell_u64 c)
-{
-  rell_u64 z = seed + (c + 1ULL) * 0x9E3779B97F4A7C15ULL;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-  return z ^ (z >> 31);
 }
 
 // Draw k of replicate first_b + blockIdx.y lands on pattern s, cum[s - 1] <= site < cum[s] (cum == nullptr: unit

@@ -4040,6 +4040,25 @@ bool tip_pointer_tables(Engine * e, DevBuf<const double *> & clv, DevBuf<const u
          hip_ok(hipStreamSynchronize(e->stream), "upload tip table");
 }
 
+// device_job.hpp
+bool matrix_tables(pll_partition_t * p, MatrixTables & out)
+{
+  if (is_router(p))
+  {
+    pll_partition_t * c = engine_of(p)->shards[0];
+    push_model(p, c);
+    p = c;
+  }
+  Engine * e = engine_of(p);
+  if (!hip_ok(hipSetDevice(e->device), "hipSetDevice") || !sync_model(p) || !flush_pmatrices(p)) return false;
+  out.pmat = e->d_pmat;
+  out.model = e->d_model;
+  out.off_weights = (unsigned)e->off_weights;
+  out.off_pinv = (unsigned)e->off_pinv;
+  out.off_freqs = (unsigned)e->off_freqs;
+  return true;
+}
+
 } // namespace pllhip
 
 extern "C" {

@@ -206,7 +206,8 @@ pllhip_bootstrap_weights
 pllhip_sitelh_au pllhip_au_destroy pllhip_au_last_times pllhip_multiscale_weights
 pllhip_distances_partition pllhip_distances_msa pllhip_distmat_from_host pllhip_distmat_destroy pllhip_distmat_size
 pllhip_distmat_get pllhip_distmat_compared pllhip_distmat_counts pllhip_distmat_no_overlap pllhip_distmat_nj
-pllhip_distmat_nj_joins pllhip_distances_last_times""".split()
+pllhip_distmat_nj_joins pllhip_distances_last_times
+pllhip_simulate_edges pllhip_simulate_utree pllhip_simulate_last_times""".split()
 
 
 def _u32(a):
@@ -296,6 +297,15 @@ class DistParams(C.Structure):
     """pllhip_dist_params_t"""
     _fields_ = [("method", C.c_int), ("flags", C.c_uint), ("min_dist", C.c_double), ("max_dist", C.c_double),
                 ("budget_bytes", C.c_ulonglong), ("chunk_columns", C.c_uint)]
+
+
+PLLHIP_SIM_INNER = 1
+
+
+class SimParams(C.Structure):
+    """pllhip_sim_params_t"""
+    _fields_ = [("seed", C.c_ulonglong), ("first_site", C.c_ulonglong), ("sites", C.c_uint),
+                ("first_replicate", C.c_uint), ("replicates", C.c_uint), ("flags", C.c_uint), ("alphabet", C.c_char_p)]
 
 
 class Rell:
@@ -557,6 +567,13 @@ class PllLib:
             L.pllhip_distmat_nj_joins.argtypes = [C.c_void_p, c_uint_p, c_double_p]
             L.pllhip_distances_last_times.restype = None
             L.pllhip_distances_last_times.argtypes = [c_double_p] * 5
+        if hasattr(L, "pllhip_simulate_edges"):
+            ubyte_p = C.POINTER(C.c_ubyte)
+            L.pllhip_simulate_edges.argtypes = [pp, C.POINTER(SimParams), C.c_uint, C.c_uint, c_uint_p, c_uint_p, c_uint_p,
+                                                c_uint_p, C.c_uint, ubyte_p]
+            L.pllhip_simulate_utree.argtypes = [pp, C.POINTER(SimParams), up, c_uint_p, C.c_int, ubyte_p]
+            L.pllhip_simulate_last_times.restype = None
+            L.pllhip_simulate_last_times.argtypes = [c_double_p, c_double_p, c_double_p, C.POINTER(C.c_ulonglong)]
         if hasattr(L, "pllhip_msa_compute_stats"):
             L.pllhip_empirical_frequencies.restype = c_double_p
             L.pllhip_empirical_frequencies.argtypes = [pp]
@@ -1675,6 +1692,74 @@ def multiscale_weights(lib, weights, patterns, seed, scale_index, draws, first, 
     ok = lib.lib.pllhip_multiscale_weights(None if w is None else w.ctypes.data_as(c_uint_p), patterns, seed,
                                            scale_index, draws, first, count, out.ctypes.data_as(c_uint_p))
     return out if ok else None
+
+
+def tree_edges(tree, root=None):
+    """the edges of a Tree directed away from inner node `root` (default: the first inner node):
+    (parent, child, matrix) index arrays, depth-first"""
+    root = tree.ntips if root is None else root
+    parent, child, matrix = [], [], []
+    stack = [(root, -1)]
+    while stack:
+        node, came = stack.pop()
+        if node < tree.ntips:
+            continue
+        for v, k in tree.adj[node]:
+            if v != came:
+                parent.append(node)
+                child.append(v)
+                matrix.append(k)
+                stack.append((v, node))
+    return _u32(parent), _u32(child), _u32(matrix)
+
+
+def _sim_params(seed, sites, replicates, first_site, first_replicate, flags, alphabet):
+    a = None if alphabet is None else (alphabet if isinstance(alphabet, bytes) else alphabet.encode())
+    return SimParams(seed, first_site, sites, first_replicate, replicates, flags, a)
+
+
+def _sim_out(inst, rows, sites, replicates, canary):
+    shape = (replicates, rows, sites)
+    return np.zeros(shape, dtype=np.uint8) if canary is None else np.full(shape, canary, dtype=np.uint8)
+
+
+def simulate_edges(inst, root, parent, child, matrix, seed, sites, replicates=1, first_site=0, first_replicate=0,
+                   flags=0, alphabet=None, node_count=None, params_indices=None, out=None):
+    """pllhip_simulate_edges on an Instance with the matrices as they stand: uint8 [replicates][rows][sites], rows =
+    tips, or node_count with PLLHIP_SIM_INNER; raises RuntimeError with the library's message.  `out`: the array to
+    fill (left as it is on failure)."""
+    pa, ch, mi = _u32(parent), _u32(child), _u32(matrix)
+    nodes = inst.tips + inst.p.contents.clv_buffers if node_count is None else node_count
+    rows = nodes if flags & PLLHIP_SIM_INNER else inst.tips
+    if out is None:
+        out = _sim_out(inst, rows, sites, replicates, None)
+    prm = _sim_params(seed, sites, replicates, first_site, first_replicate, flags, alphabet)
+    idx = inst.params if params_indices is None else _u32(params_indices)
+    if not inst.L.pllhip_simulate_edges(inst.p, C.byref(prm), root, len(pa), pa.ctypes.data_as(c_uint_p),
+                                        ch.ctypes.data_as(c_uint_p), mi.ctypes.data_as(c_uint_p),
+                                        idx.ctypes.data_as(c_uint_p), nodes, out.ctypes.data_as(C.POINTER(C.c_ubyte))):
+        raise RuntimeError(inst.lib.errmsg)
+    return out
+
+
+def simulate_utree(inst, root, seed, sites, replicates=1, first_site=0, first_replicate=0, flags=0, alphabet=None,
+                   update_matrices=True, out=None):
+    """pllhip_simulate_utree from `root` (a POINTER(UNode) at an inner node)"""
+    rows = inst.tips + inst.p.contents.clv_buffers if flags & PLLHIP_SIM_INNER else inst.tips
+    if out is None:
+        out = _sim_out(inst, rows, sites, replicates, None)
+    prm = _sim_params(seed, sites, replicates, first_site, first_replicate, flags, alphabet)
+    if not inst.L.pllhip_simulate_utree(inst.p, C.byref(prm), root, inst.params_p, 1 if update_matrices else 0,
+                                        out.ctypes.data_as(C.POINTER(C.c_ubyte))):
+        raise RuntimeError(inst.lib.errmsg)
+    return out
+
+
+def simulate_last_times(lib):
+    """(tables_ms, kernel_ms, copy_ms, chunks) of this thread's last simulation"""
+    a, b, c, n = C.c_double(0), C.c_double(0), C.c_double(0), C.c_ulonglong(0)
+    lib.lib.pllhip_simulate_last_times(C.byref(a), C.byref(b), C.byref(c), C.byref(n))
+    return a.value, b.value, c.value, n.value
 
 
 def state_charmap(nstates):
