@@ -276,7 +276,7 @@ void plan_lookups(const ListFacts & facts, unsigned lut_used, unsigned max_class
 //   a looked-up child           -- its consumer gathers rows of the class table; the child's own chain (the cherry, or
 //                                  the cherry handed over in registers to the cherry x tip operation) feeds nobody else.
 // Such an operation is marked "parent vector not stored" (PlanOp::flags bit 0).  Coded tips and P-matrices alone
-// recompute it, so the engine keeps it as its operation (transient_mark, as for an evaluate-only traversal) and stores it
+// recompute it, so the engine keeps it as its operation (unstored.hpp, as for an evaluate-only traversal) and stores it
 // for the first reader or before an input changes.  Scaler counts are written as always.  The cherry below a looked-up
 // cherry x tip is marked only where that operation takes it over in registers.  Level 2: the looked-up children keep
 // their stores.
@@ -285,13 +285,13 @@ void plan_lookups(const ListFacts & facts, unsigned lut_used, unsigned max_class
 // chain, never a vector that an operation reads from memory or that nobody in the list reads.
 //   a vector inside a chain (level 4) -- every operation that passes the test, whatever its children are, however far
 //     up the chain.  The next evaluation overwrites it unread.  Such a vector is recomputed from stored child vectors,
-//     not from tip codes alone: the engine stores it before one of them is overwritten (transient_before_list).
+//     not from tip codes alone: the engine stores it before one of them is overwritten (UnstoredLedger::before_list).
 //   a tip-only run at the bottom of a chain (level 3) -- the same walk, as far as the result depends on tip codes
 //     alone: from the chain's first operation that is not folded, which has to be a cherry of coded tips, over the
 //     operations "handed-over child x coded tip", the first `depth` of them at the most (0: all), up to the first that
 //     fails the test or hands its vector across a folded cherry.
-// plan.run_up links two marked operations that stand next to each other in a chain (transient_materialize stores a run
-// in one list); across a folded cherry there is no link, and the reader of the lower one stores what it needs alone.
+// plan.run_up links two marked operations that stand next to each other in a chain (UnstoredLedger::recompute_list
+// stores a run in one list); across a folded cherry there is no link, and the reader of the lower one stores what it needs alone.
 // `plan`: after plan_folds and plan_lookups.
 void plan_defers(const ListFacts & facts, DeferPolicy policy, ChainPlan & plan)
 {

@@ -20,6 +20,7 @@
 #include "pll.h"
 #include "pllhip.h"
 #include "newton_range.hpp"
+#include "unstored.hpp"
 
 namespace pllhip {
 
@@ -181,8 +182,8 @@ struct BatchPlan
 
 enum class KernelFamily { Generic, S4, S16, S20, S61 };
 
-// why a vector exists as its operation only (Engine::transient_live)
-constexpr char TRANSIENT_MODE = 1, TRANSIENT_DEFERRED = 2;
+using unstored::TRANSIENT_MODE;            // why a vector exists as its operation only (unstored.hpp)
+using unstored::TRANSIENT_DEFERRED;
 
 struct Engine
 {
@@ -250,24 +251,12 @@ struct Engine
   unsigned char * d_looktab = nullptr;
   size_t looktab_cap = 0;
   pllhip_repeat_stats_t repeat_stats = {};
-  // Evaluate-only traversals (pllhip_set_transient): a resident schedule may hand the vectors inside its chains on
-  // in registers without storing them.  Such a vector stays recomputable -- the operation that made it is kept --
-  // and is stored for the first reader that needs it, or before one of its inputs changes.
+  // Vectors that exist as their operation only (unstored.hpp): what evaluate-only traversals (pllhip_set_transient)
+  // left out and the stores that storing traversals deferred.  The ledger keeps the books; the engine runs the lists.
   pll_partition_t * owner = nullptr;
   bool transient_mode = false;
-  bool transient_busy = false;                  // a materialisation is running (its lists are exempt from the checks)
-  unsigned ntransient = 0;                      // vectors that exist as their operation only
-  std::vector<char> transient_live;             // [nodes] 1: the mode left the vector out, 2: a deferred store (plan_defers)
-  std::vector<pll_operation_t> transient_op;    // [nodes] what recomputes the vector
-  std::vector<int> transient_run_up;            // [nodes] the vector above it in the same deferred run (-1: none; plan_defers)
-  std::vector<unsigned> transient_mat_users;    // [nmat] live operations that read the matrix
-  pllhip_transient_stats_t transient_stats = {};
-  pllhip_deferred_stats_t deferred_stats = {};  // the same records, for the stores that storing traversals defer
-  // how the caller has treated deferred vectors lately (run_resident; the default level of plan_defers goes by it):
-  // the lists in a row that left stores out with no deferred vector stored since the end of the first of them (0: no
-  // such list has run yet); stored_later at the end of the last one
-  unsigned defer_row = 0;
-  unsigned long long defer_stored_mark = 0;
+  bool transient_busy = false;                  // a list that stores such vectors is running (exempt from the checks)
+  unstored::UnstoredLedger ledger;
   size_t sc_len = 0;                  // entries per scale buffer on the device
   KernelFamily family = KernelFamily::Generic;
   unsigned cu_count = 256;

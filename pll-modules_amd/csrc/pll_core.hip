@@ -64,8 +64,37 @@ static int current_device()
 int flush_pmatrices(pll_partition_t * p);
 static int ensure_luts(pll_partition_t * p);
 static int update_partials_impl(pll_partition_t * p, const pll_operation_t * ops, unsigned count);
-static int transient_materialize(Engine * e, const std::vector<unsigned> & want, const std::vector<char> * going = nullptr);
-static int transient_flush_all(Engine * e);
+
+// Store the vectors of `want` that exist as their operation only (Engine::ledger): the operations that made them run
+// again as an ordinary list -- the same kernels on the same inputs, so what is stored is what the traversal would have
+// stored.  A member of a deferred run brings the members above it along, one launch for the run instead of one per
+// member (UnstoredLedger::recompute_list; PLLHIP_DEFER_GROUP=0: every reader stores what it reads and what lies below)
+static int store_unstored(Engine * e, const std::vector<unsigned> & want, const std::vector<char> * going = nullptr)
+{
+  if (e->ledger.empty()) return PLL_SUCCESS;
+  static const int env_group = getenv("PLLHIP_DEFER_GROUP") ? atoi(getenv("PLLHIP_DEFER_GROUP")) : 1;
+  std::vector<pll_operation_t> list;
+  unsigned ndeferred = 0;
+  e->ledger.recompute_list(want, env_group != 0, going, list, ndeferred);
+  if (list.empty()) return PLL_SUCCESS;
+  const bool mode = e->transient_mode;
+  e->transient_busy = true;
+  e->transient_mode = false;
+  const int rc = update_partials_impl(e->owner, list.data(), (unsigned)list.size());
+  e->transient_mode = mode;
+  e->transient_busy = false;
+  if (rc) e->ledger.stored((unsigned)list.size() - ndeferred, ndeferred);
+  return rc;
+}
+
+static int transient_flush_all(Engine * e)
+{
+  if (e->ledger.empty() || e->transient_busy) return PLL_SUCCESS;
+  std::vector<unsigned> all;
+  for (unsigned n = 0; n < e->nodes; ++n) if (e->ledger.live(n)) all.push_back(n);
+  return store_unstored(e, all);
+}
+
 static bool cherry_storage(Engine * e, unsigned node, unsigned nclasses);
 // tip lookup tables exist: PLL_ATTRIB_PATTERN_TIP, or the engine's own codes (Engine::shadow_codes)
 static bool lut_active(const Engine * e) { return e->coded_tips || e->shadow_codes; }
@@ -333,10 +362,7 @@ Engine * engine_create(pll_partition_t * p)
   e->pmat_brlen.assign(e->nmat, std::numeric_limits<double>::quiet_NaN());
   e->pmat_params.assign(e->nmat, std::vector<unsigned>());
   e->owner = p;
-  e->transient_live.assign(e->nodes, 0);
-  e->transient_op.assign(e->nodes, pll_operation_t());
-  e->transient_run_up.assign(e->nodes, -1);
-  e->transient_mat_users.assign(e->nmat, 0);
+  e->ledger.reset(e->nodes, e->nmat);
   e->transient_mode = getenv("PLLHIP_TRANSIENT") && atoi(getenv("PLLHIP_TRANSIENT")) != 0;
 
   // model block layout
@@ -738,9 +764,9 @@ int flush_pmatrices(pll_partition_t * p)
   PLLHIP_TRY(hipSetDevice(e->device));
   // a vector that an evaluate-only traversal did not store is recomputed with the matrices it was made with: stored
   // now, before one of them changes (an operation list gives the vectors it overwrites up BEFORE it comes here)
-  if (e->ntransient && !e->transient_busy)
+  if (!e->ledger.empty() && !e->transient_busy)
     for (unsigned m : e->pend_midx)
-      if (e->transient_mat_users[m])
+      if (e->ledger.matrix_in_use(m))
       {
         if (!transient_flush_all(e)) return PLL_FAILURE;
         break;
@@ -1128,7 +1154,7 @@ static unsigned s20_look_classes(const Engine * e, unsigned lut_used)
 // Without PLLHIP_DEFER the level follows what the caller does with the vectors that were left out (DESIGN.md sections
 // 22 and 26): a higher level gains on an evaluation that is followed by another evaluation, and costs an evaluation that
 // is followed by a pass over all branches more than it saved.  So level 1 is planned until S20_DEFER_RUN_ROW lists in a
-// row that left stores out have come and gone without one deferred vector being stored later (Engine::defer_row,
+// row that left stores out have come and gone without one deferred vector being stored later (UnstoredLedger::unread_row,
 // run_resident), level 3 from then on, level 4 once S20_DEFER_CHAIN_ROW such lists have, and level 1 again as soon as a
 // reader asks for a deferred vector.  S20_DEFER_CHAIN_ROW = max(4, ceil(T / G)) at the size where T / G is largest: G is
 // what level 4 gains per evaluation over level 3, T what the turn "evaluation, then a pass over all branches" costs more
@@ -1147,7 +1173,7 @@ static DeferPolicy s20_defer(const Engine * e)
   static const int env_depth = getenv("PLLHIP_DEFER_DEPTH") ? atoi(getenv("PLLHIP_DEFER_DEPTH")) : -1;
   if (!use_defer || (use_defer < 0 && e->nblk < S20_DEFER_MIN_BLOCKS)) return {};
   // (the lists in a row that went unread so far; a vector stored since the last of them ends the row)
-  const unsigned row = e->deferred_stats.stored_later == e->defer_stored_mark ? e->defer_row : 0u;
+  const unsigned row = e->ledger.unread_row();
   const unsigned level = use_defer < 0 ? (row >= S20_DEFER_CHAIN_ROW ? 4u : row >= S20_DEFER_RUN_ROW ? 3u : 1u)
                        : use_defer == 2 ? 2u : use_defer == 3 ? 3u : use_defer >= 4 ? 4u : 1u;
   const unsigned depth = env_depth < 0 ? S20_DEFER_DEPTH : (unsigned)std::min(env_depth, 1023);
@@ -1518,8 +1544,8 @@ static int need_scaler(Engine * e, int sidx)
 static int need_clv(Engine * e, unsigned idx)
 {
   // (an evaluate-only traversal kept it in registers: recomputed and stored now)
-  if (e->ntransient && !e->transient_busy && idx < e->transient_live.size() && e->transient_live[idx] &&
-      !transient_materialize(e, std::vector<unsigned>(1, idx))) return PLL_FAILURE;
+  if (!e->ledger.empty() && !e->transient_busy && e->ledger.live(idx) &&
+      !store_unstored(e, std::vector<unsigned>(1, idx))) return PLL_FAILURE;
   if (e->cherries.empty() || idx >= e->cherries.size()) return PLL_SUCCESS;
   Engine::Cherry & c = e->cherries[idx];
   if (c.valid && c.scaler_index >= 0 && (size_t)c.scaler_index < e->scaler_lazy.size() && e->scaler_lazy[c.scaler_index] == (int)idx &&
@@ -1694,178 +1720,15 @@ static bool class_map(Engine * e, unsigned node, unsigned c1, unsigned c2, unsig
   return true;
 }
 
-// ---------------------------------------------------------------------------
-// evaluate-only traversals (include/pllhip.h, pllhip_set_transient): host side
-// ---------------------------------------------------------------------------
-// the vector of `node` stops being "its operation only": it is being stored (dead = false) or replaced / given up
-static int transient_materialize_list(Engine * e, const std::vector<unsigned> & want);
-
-static void transient_drop(Engine * e, unsigned node, bool dead)
-{
-  if (!e->ntransient || !e->transient_live[node]) return;
-  const pll_operation_t & o = e->transient_op[node];
-  const bool deferred = e->transient_live[node] == TRANSIENT_DEFERRED;
-  e->transient_live[node] = 0;
-  --e->transient_mat_users[o.child1_matrix_index];
-  --e->transient_mat_users[o.child2_matrix_index];
-  --e->ntransient;
-  if (dead && deferred) e->deferred_stats.given_up++;
-  else if (dead) e->transient_stats.discarded++;
-}
-
-// kind: TRANSIENT_MODE = an evaluate-only traversal left the vector out, TRANSIENT_DEFERRED = a storing traversal
-// deferred its store (plan_defers); the two are counted apart (pllhip_transient_stats / pllhip_deferred_stats)
-static void transient_mark(Engine * e, const pll_operation_t & o, char kind)
-{
-  transient_drop(e, o.parent_clv_index, true);
-  e->transient_live[o.parent_clv_index] = kind;
-  e->transient_op[o.parent_clv_index] = o;
-  e->transient_run_up[o.parent_clv_index] = -1;
-  ++e->transient_mat_users[o.child1_matrix_index];
-  ++e->transient_mat_users[o.child2_matrix_index];
-  ++e->ntransient;
-  if (kind == TRANSIENT_DEFERRED) e->deferred_stats.deferred++;
-  else e->transient_stats.skipped++;
-}
-
-// store the vectors of `want` that exist as their operation only: the operations that made them run again (and,
-// below them, the ones of the children that were not stored either), as an ordinary list -- the same kernels on the
-// same inputs, so what is stored is what the traversal would have stored.
-// A member of a deferred chain-bottom run (plan_defers, level 3), or of a stretch of deferred vectors that stand next to
-// each other inside a chain (level 4), brings the members above it along: one list, one
-// chain, one launch for the run instead of a launch per member that re-reads what the one before just wrote
-// (PLLHIP_DEFER_GROUP=0: every reader stores what it reads and what lies below, as for every other vector).
-// going: [nodes] vectors that the caller is about to overwrite -- a run is not followed into them (null: none)
-static int transient_materialize(Engine * e, const std::vector<unsigned> & want, const std::vector<char> * going)
-{
-  if (!e->ntransient) return PLL_SUCCESS;
-  static const int env_group = getenv("PLLHIP_DEFER_GROUP") ? atoi(getenv("PLLHIP_DEFER_GROUP")) : 1;
-  std::vector<unsigned> grouped;
-  if (env_group)
-  {
-    for (unsigned w : want)
-    {
-      if (w >= e->nodes || e->transient_live[w] != TRANSIENT_DEFERRED) { grouped.push_back(w); continue; }
-      // (the link holds while the vector above is still the deferred operation that takes this one as a child)
-      for (unsigned steps = 0; steps < e->nodes; ++steps)
-      {
-        const int up = e->transient_run_up[w];
-        if (up < 0 || e->transient_live[up] != TRANSIENT_DEFERRED || (going && (*going)[up])) break;
-        const pll_operation_t & o = e->transient_op[up];
-        if (o.child1_clv_index != w && o.child2_clv_index != w) break;
-        w = (unsigned)up;
-      }
-      grouped.push_back(w);
-    }
-  }
-  return transient_materialize_list(e, env_group ? grouped : want);
-}
-
-static int transient_materialize_list(Engine * e, const std::vector<unsigned> & want)
-{
-  std::vector<pll_operation_t> list;
-  unsigned long long ndeferred = 0;                   // of them: deferred stores
-  std::vector<char> seen(e->nodes, 0);
-  std::vector<std::pair<unsigned, unsigned>> stack;   // (node, children looked at)
-  for (unsigned w : want)
-  {
-    if (w >= e->nodes || !e->transient_live[w] || seen[w]) continue;
-    seen[w] = 1;
-    stack.emplace_back(w, 0u);
-    while (!stack.empty())
-    {
-      const unsigned node = stack.back().first;
-      const pll_operation_t & o = e->transient_op[node];
-      if (stack.back().second < 2)
-      {
-        const unsigned c = stack.back().second++ ? o.child2_clv_index : o.child1_clv_index;
-        if (e->transient_live[c] && !seen[c]) { seen[c] = 1; stack.emplace_back(c, 0u); }
-      }
-      else
-      {
-        if (e->transient_live[node] == TRANSIENT_DEFERRED) ++ndeferred;
-        list.push_back(o);
-        stack.pop_back();
-      }
-    }
-  }
-  if (list.empty()) return PLL_SUCCESS;
-  const bool mode = e->transient_mode;
-  e->transient_busy = true;
-  e->transient_mode = false;
-  const int rc = update_partials_impl(e->owner, list.data(), (unsigned)list.size());
-  e->transient_mode = mode;
-  e->transient_busy = false;
-  if (rc)
-  {
-    e->transient_stats.materialized += list.size() - ndeferred;
-    e->deferred_stats.stored_later += ndeferred;
-  }
-  return rc;
-}
-
-static int transient_flush_all(Engine * e)
-{
-  if (!e->ntransient || e->transient_busy) return PLL_SUCCESS;
-  std::vector<unsigned> all;
-  for (unsigned n = 0; n < e->nodes; ++n) if (e->transient_live[n]) all.push_back(n);
-  return transient_materialize(e, all);
-}
-
-// before an operation list runs: vectors it reads that were not stored, and vectors that were not stored whose
-// inputs (children, scaler buffers) the list overwrites, are stored first; what the list itself overwrites is given up
-static int transient_before_list(Engine * e, const pll_operation_t * ops, unsigned count)
-{
-  if (!e->ntransient) return PLL_SUCCESS;
-  if (!e->transient_busy)
-  {
-    std::vector<char> written(e->nodes, 0), swritten(e->nscalers, 0);
-    std::vector<unsigned> want;
-    for (unsigned k = 0; k < count; ++k)
-    {
-      const unsigned child[2] = {ops[k].child1_clv_index, ops[k].child2_clv_index};
-      for (int x = 0; x < 2; ++x)
-        if (e->transient_live[child[x]] && !written[child[x]]) want.push_back(child[x]);
-      written[ops[k].parent_clv_index] = 1;
-      if (ops[k].parent_scaler_index >= 0) swritten[ops[k].parent_scaler_index] = 1;
-    }
-    for (unsigned t = 0; t < e->nodes; ++t)
-    {
-      if (!e->transient_live[t] || written[t]) continue;
-      const pll_operation_t & o = e->transient_op[t];
-      if (written[o.child1_clv_index] || written[o.child2_clv_index] ||
-          (o.child1_scaler_index >= 0 && swritten[o.child1_scaler_index]) ||
-          (o.child2_scaler_index >= 0 && swritten[o.child2_scaler_index]) ||
-          (o.parent_scaler_index >= 0 && swritten[o.parent_scaler_index]))
-        want.push_back(t);
-    }
-    if (!want.empty() && !transient_materialize(e, want, &written)) return PLL_FAILURE;
-  }
-  for (unsigned k = 0; k < count && e->ntransient; ++k) transient_drop(e, ops[k].parent_clv_index, !e->transient_busy);
-  return PLL_SUCCESS;
-}
-
-// after the launches of a resident schedule: the operations whose vectors stayed in registers (kind: transient_mark)
-static void transient_after_list(Engine * e, const pll_operation_t * ops, unsigned count, const DevicePlan & dp, char kind)
+// after the launches of a resident schedule: the operations whose vectors it left out (PlanOp::flags bit 0) go into
+// the ledger, with the deferred runs of the schedule (kind: TRANSIENT_MODE / TRANSIENT_DEFERRED)
+static void record_unstored(Engine * e, const pll_operation_t * ops, unsigned count, const DevicePlan & dp, char kind)
 {
   const PlanOp * pops = reinterpret_cast<const PlanOp *>(dp.bytes.data());
-  std::vector<int> by_parent;
+  std::vector<unsigned> left_out;
   for (unsigned i = 0; i < dp.nops; ++i)
-  {
-    if (!(pops[i].flags & 1u)) continue;
-    if (by_parent.empty())
-    {
-      by_parent.assign(e->nodes, -1);
-      for (unsigned k = 0; k < count; ++k) by_parent[ops[k].parent_clv_index] = (int)k;
-    }
-    const int k = by_parent[pops[i].d.parent_index];
-    if (k >= 0) transient_mark(e, ops[k], kind);
-  }
-  // the deferred runs at the bottom of chains: which vector stands above which (transient_materialize)
-  if (kind == TRANSIENT_DEFERRED)
-    for (const std::pair<unsigned, unsigned> & r : dp.defer_runs)
-      if (e->transient_live[r.first] == TRANSIENT_DEFERRED && e->transient_live[r.second] == TRANSIENT_DEFERRED)
-        e->transient_run_up[r.first] = (int)r.second;
+    if (pops[i].flags & 1u) left_out.push_back(pops[i].d.parent_index);
+  e->ledger.after_list(ops, count, left_out, dp.defer_runs, kind);
 }
 
 // resolve one operation to device pointers and add its algorithmic bytes
@@ -2546,9 +2409,16 @@ static int begin_list(Engine * e, pll_partition_t * p, const pll_operation_t * o
   PLLHIP_TRY(hipSetDevice(e->device));
   if (!validate_ops(e, ops, count)) return PLL_FAILURE;
   // (before the queued P-matrices are launched: vectors that were not stored and that this list overwrites are given
-  // up, the ones it reads are stored with the matrices they were made with; a list that stores such vectors -- 
+  // up, the ones it reads are stored with the matrices they were made with; a list that stores such vectors --
   // transient_busy -- runs on the matrices the device holds)
-  if (!transient_before_list(e, ops, count)) return PLL_FAILURE;
+  if (!e->ledger.empty())
+  {
+    std::vector<unsigned> want;
+    std::vector<char> going;
+    e->ledger.before_list(ops, count, e->nscalers, e->transient_busy, want, going);
+    if (!want.empty() && !store_unstored(e, want, &going)) return PLL_FAILURE;
+    e->ledger.give_up_written(ops, count, e->transient_busy);
+  }
   if (e->shadow_codes)
     for (unsigned k = 0; k < count; ++k)
       if (ops[k].parent_clv_index < e->tips) e->tip_has_codes[ops[k].parent_clv_index] = 0;    // (a tip vector is overwritten)
@@ -2710,16 +2580,12 @@ static int run_resident(Engine * e, const ChainFamily & f, const pll_operation_t
   }
   if (!launch_resident(e, f, dp, view, 0, !e->cherries.empty(), transient)) return PLL_FAILURE;
   // (a storing schedule marks only the stores it deferred: plan_defers)
-  if (transient || dp.ndeferred) transient_after_list(e, ops, count, dp, transient ? TRANSIENT_MODE : TRANSIENT_DEFERRED);
+  if (transient || dp.ndeferred) record_unstored(e, ops, count, dp, transient ? TRANSIENT_MODE : TRANSIENT_DEFERRED);
   // what became of the vectors that the deferring lists before this one left out: all given up unread -- the row of
   // such lists grows by this one --, or some stored for a reader -- a new row starts here (the family's default level
   // goes by its length: s20_defer; lists that leave nothing out -- the single operations of a smoothing pass -- say
   // nothing about it)
-  if (dp.ndeferred)
-  {
-    e->defer_row = e->defer_row && e->deferred_stats.stored_later == e->defer_stored_mark ? e->defer_row + 1u : 1u;
-    e->defer_stored_mark = e->deferred_stats.stored_later;
-  }
+  if (dp.ndeferred) e->ledger.deferring_list_ran();
   count_list(e, count);
   return PLL_SUCCESS;
 }
@@ -3068,12 +2934,10 @@ static int update_partials_group(const std::vector<pll_partition_t *> & g, const
   for (pll_partition_t * p : g)
   {
     Engine * e = engine_of(p);
-    if (!validate_ops(e, ops, count)) return -1;
-    if (e->ntransient && (hipSetDevice(e->device) != hipSuccess || !transient_before_list(e, ops, count))) return -1;
-    // (tips kept per class are written off as class nodes by an operation that overwrote one: never -- tips are not
-    // parents; the vectors this list writes stop being whatever class node they were)
-    if (!e->cherries.empty())
-      for (unsigned k = 0; k < count; ++k) e->cherries[ops[k].parent_clv_index].valid = false;
+    // (a member never has site repeats -- batch_family --, so none of the vectors this list writes is a valid class node
+    // and the prologue's loop over them only writes them off; where a later member makes this function return 0, the
+    // per-partition calls run the prologue on the earlier members again, and find nothing left to do)
+    if (!begin_list(e, p, ops, count)) return -1;
     if (!prepare_schedule(e, p, f, {ops, count, mode, e->transient_mode && !e->site_repeats, nullptr})) return 0;
   }
   // launches can be shared when every member's schedule has the same shape (same list, same family: always,
@@ -3197,7 +3061,7 @@ static int update_partials_group(const std::vector<pll_partition_t *> & g, const
   for (pll_partition_t * p : g)
   {
     Engine * e = engine_of(p);
-    if (e->transient_mode && !e->site_repeats) transient_after_list(e, ops, count, e->plan, TRANSIENT_MODE);
+    if (e->transient_mode && !e->site_repeats) record_unstored(e, ops, count, e->plan, TRANSIENT_MODE);
     count_list(e, count);
   }
   return 1;
@@ -3212,16 +3076,16 @@ extern "C" int pllhip_update_partials_batch(pll_partition_t * const * partitions
   if (!count) return PLL_SUCCESS;
   int rc = PLL_SUCCESS;
   std::vector<char> taken(partition_count, 0);
-  // pending P-matrices and the tip tables first: whether a partition's traversals can run from a shared
-  // schedule depends on its tables (and every member needs them anyway)
+  // the tip tables first: whether a partition's traversals can run from a shared schedule depends on their size
+  // (chain_family reads lut_codes, the row count and not the contents: the 4-state chains want 16 rows).  Coming before
+  // the queued P-matrices is no change of order: flush_pmatrices itself calls ensure_luts first where the tables are
+  // stale, and the matrix kernel then fills the rows of what was queued.  Everything else -- unstored vectors, pending
+  // P-matrices, class nodes -- is begin_list's, per member or per partition
   for (unsigned i = 0; i < partition_count; ++i)
     if (partitions[i] && !is_router(partitions[i]))
     {
-      Engine * e = engine_of(partitions[i]);
-      PLLHIP_TRY(hipSetDevice(e->device));
-      // (vectors an evaluate-only traversal did not store: settled before the queued P-matrices are launched)
-      if (e->ntransient && (!validate_ops(e, ops, count) || !transient_before_list(e, ops, count))) return PLL_FAILURE;
-      if (!flush_pmatrices(partitions[i]) || !ensure_luts(partitions[i])) return PLL_FAILURE;
+      PLLHIP_TRY(hipSetDevice(engine_of(partitions[i])->device));
+      if (!ensure_luts(partitions[i])) return PLL_FAILURE;
     }
   for (unsigned i = 0; i < partition_count; ++i)
   {
@@ -3396,7 +3260,7 @@ int pll_update_prob_matrices(pll_partition_t * p,
   // per-branch calls of the next (src/tree/treeinfo.c:845-865 loops the partitions inside every branch)
   // (not while vectors exist as their operation only: the launch waits for the consumer -- if that is the next
   // traversal, it gives those vectors up before the matrices they were made with change; flush_pmatrices)
-  if (!e->ntransient && (e->pend_midx.size() >= 4 * MAX_PMAT_PER_LAUNCH || e->pend_midx.size() == e->nmat)) return flush_pmatrices(p);
+  if (e->ledger.empty() && (e->pend_midx.size() >= 4 * MAX_PMAT_PER_LAUNCH || e->pend_midx.size() == e->nmat)) return flush_pmatrices(p);
   return PLL_SUCCESS;
 }
 
@@ -4852,21 +4716,19 @@ int pllhip_discard_transient(pll_partition_t * p)
 {
   Engine * e = engine_of(p);
   for (pll_partition_t * c : e->shards) (void)pllhip_discard_transient(c);
-  // (a deferred store is not the caller's doing: it stays recomputable)
-  for (unsigned n = 0; n < e->nodes && e->ntransient; ++n)
-    if (e->transient_live[n] == TRANSIENT_MODE) transient_drop(e, n, true);
+  e->ledger.discard_mode_vectors();         // (a deferred store is not the caller's doing: it stays recomputable)
   return PLL_SUCCESS;
 }
 
 int pllhip_transient_stats(const pll_partition_t * p, pllhip_transient_stats_t * out)
 {
-  *out = exec_engine(p)->transient_stats;
+  *out = exec_engine(p)->ledger.transient_stats();
   return PLL_SUCCESS;
 }
 
 int pllhip_deferred_stats(const pll_partition_t * p, pllhip_deferred_stats_t * out)
 {
-  *out = exec_engine(p)->deferred_stats;
+  *out = exec_engine(p)->ledger.deferred_stats();
   return PLL_SUCCESS;
 }
 
