@@ -532,11 +532,99 @@ __device__ inline const unsigned * s20_wide_codes(const double * clv, const uint
   return (!clv && !codes) ? reinterpret_cast<const unsigned *>(pfrag) : nullptr;
 }
 
+// the in-place form of s20_child_regs_c: x <- P . x, the same ten plus ten instructions in the same order; the result
+// takes the operand's registers after the last k-step (the carried phase of s20_chain_op)
+__device__ inline void s20_child_regs_ip(double2 x[5], const double * cfrag_r, unsigned lane)
+{
+  double2 t[5];
+  s20_child_regs_c(x, cfrag_r, lane, t);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) x[k] = t[k];
+}
+
+// the codes of an even / odd pair of sites in one 16-bit word (bits 0 .. 7: the even site)
+__device__ inline unsigned s20_ld_code_pair(const uint8_t * p)
+{
+  unsigned short v;
+  __builtin_memcpy(&v, p, 2);
+  return v;
+}
+
+// Keeps the loads in front of it where they stand (no wait, no instruction: the optimiser otherwise sinks a load into
+// the block that consumes it, behind the carried phase of s20_chain_op).
+__device__ inline void s20_pin_loads() { asm volatile("" ::: "memory"); }
+
+// what a child of an operation is read from (s20_chain_op): codes = a coded tip (its table in `slot` when staged, else
+// `lut`), wide = a wide tip (class codes; `index` rows per rate, in `slot` when wide_lds), else a vector `clv` whose
+// matrix fragments are in `slot` -- or, for child 2 alone, a folded cherry or a class table
+struct S20Child
+{
+  const double * clv;
+  const uint8_t * codes;
+  const unsigned * wide;
+  const double * lut;
+  const double * slot;
+  unsigned index;
+  bool wide_lds;
+};
+
+// what s20_chain_op knows of a folded cherry / a looked-up child (child 2 of its operation)
+struct S20Fold
+{
+  const double * fa, * fb;      // the cherry's tip tables in LDS
+  unsigned codes, small;        // its four tip codes / the two class codes; the cherry's scaling decisions
+  bool fold, look, store;
+};
+
+// The term of one child that is not handed over in registers, for rate r, in D layout: a table row (tip, wide tip,
+// class table), or P . b through the matrix sequence with b read from memory (b0: the block of rate 0 where the
+// caller's fetch group has requested it) or built from a folded cherry's tables (and stored).  One helper for either child.
+template <unsigned RT, bool WIDE, bool FOLD, bool LOOK>
+__device__ inline void s20_side_term(const S20Child & c, const S20Fold & f, unsigned r, unsigned ce, unsigned co,
+                                     const double2 b0[5], bool b0_valid, size_t ubase, unsigned lane, unsigned lut_codes,
+                                     unsigned lut_used, bool lut_lds, bool nt_ld, bool nt_st, double2 t[5])
+{
+  const unsigned q = lane >> 4;
+  if (WIDE && c.wide && c.wide_lds) s20_child_tip(c.slot + r * c.index * S20_LUT_RS, ce, co, q, t, S20_LUT_RS);
+  else if (WIDE && c.wide) s20_child_tip(c.lut + (size_t)r * c.index * 20, ce, co, q, t);
+  else if (c.codes)
+  {
+    if (lut_lds) s20_child_tip(c.slot + r * lut_used * S20_LUT_RS, ce, co, q, t, S20_LUT_RS);
+    else s20_child_tip(c.lut + (size_t)r * lut_codes * 20, ce, co, q, t);
+  }
+  else if (LOOK && f.look) s20_child_tip(c.lut + (size_t)r * c.index * 20, f.codes & 0xffffu, f.codes >> 16, q, t);
+  else
+  {
+    // the operand block: built from the cherry's tables (and stored), or read from memory -- one product either way
+    double2 b[5];
+    if (FOLD && f.fold)
+    {
+      s20_fold_block(f.fa + r * lut_used * S20_LUT_RS, f.fb + r * lut_used * S20_LUT_RS, f.codes, f.small, q, b);
+      if (f.store) s20_store_d(const_cast<double *>(c.clv) + ubase, lane, b, nt_st);
+    }
+    else if (b0_valid && r == 0)
+    {
+#pragma unroll
+      for (int ks = 0; ks < 5; ++ks) b[ks] = b0[ks];
+    }
+    else
+    {
+#pragma unroll
+      for (int ks = 0; ks < 5; ++ks) b[ks] = s20_ld(c.clv + ubase + ks * 128 + lane * 2, nt_ld);
+    }
+    s20_child_regs_c(b, c.slot + r * S20_CFRAGS, lane, t);
+  }
+}
+
 // one operation for one site block; X holds the handed-over operand on entry (when
 // carried != 0) and the result on exit.  s1 / s2: the children's LDS tables.
 // xe / xo: the scaler counts that go with X (per rate with RS = PLL_ATTRIB_RATE_SCALERS, where
 // the vote covers one (site, rate) unit and the counts live at scaler[site * R + rate];
 // otherwise one count per site, held in element 0).
+// Order: the fetch group requests everything the operation reads from memory that depends on no
+// other vector load; the carried phase multiplies the handed-over child in place, X[r] <- P_r . X[r], under those loads;
+// the side phase takes the other child's term per rate (s20_side_term) and multiplies it in.  With carried == 0 both
+// children are side terms.  The factors are those of t1 * t2 in either order: every bit of the result is the same.
 // WIDE: the schedule may hold wide tips (site repeats); without them the instantiation carries none of their
 // pointers and branches (the attribute-off kernel is the round-2 one: 13 instead of 19 spilled registers).
 // store: false = the result is handed to the next operation of the chain in registers only (an evaluate-only
@@ -547,8 +635,8 @@ __device__ inline const unsigned * s20_wide_codes(const double * clv, const uint
 // its flags counts with ftrans).  The cherry's vector and scaler buffer are the consumer's clv2 / scaler2.  Vector and
 // counts are what the cherry's own operation would have stored (the same product, the same factor); the counts are
 // stored, the vector unless bit 0 of the cherry's entry says that nobody reads it (an evaluate-only traversal, or a
-// store that the planner deferred: plan_defers).  (Only what is needed of the entry is fetched, and only in front of a fold: both entries in scalar
-// registers at once spilled over a hundred of them.)
+// store that the planner deferred: plan_defers).  (Only what is needed of the entry is fetched, and only in front of a
+// fold: both entries in scalar registers at once spilled over a hundred of them.)
 // LOOK: child 2 may be a small subtree read through its class table (`look`; PlanOp::flags bit 5, plan_lookups): a
 // cherry or a cherry x tip, whose vector depends on the two or three tip codes below it alone.  The entry carries those
 // codes' arrays in clv2 / pmat2 / pfrag2 (pfrag2 null: a cherry), the rows P . vector(class) of all U^2 / U^3 classes in
@@ -571,55 +659,140 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
   // wide_lds: PlanOp::flags -- bit 1 / 2: the rows of wide tip 1 / 2 are staged in LDS (s1 / s2, rows of S20_LUT_RS)
   const unsigned q = lane >> 4, n = lane & 15;
   const size_t site0 = (size_t)blk * S20_BS + 2 * n;
-  // the folded cherry: its four tip codes in one register, its scaling decisions in another (bit 0 / 1: even / odd site)
-  unsigned fcodes = 0, fsmall = 0;
-  const double * fa = nullptr, * fb = nullptr;
-  bool fstore = true;
-  if (FOLD && fold)
+  // What the fetch group needs of the entry arrives by one group of scalar loads and one wait (left alone, the compiler
+  // fetches each field in front of its first use: one scalar round trip after the other in front of the first product).
+  asm volatile("" :: "s"(op.clv1), "s"(op.codes1), "s"(op.clv2), "s"(op.codes2), "s"(op.scaler1), "s"(op.scaler2),
+               "s"(op.parent_scaler), "s"(carried));
+  const bool fold2 = FOLD && fold, look2 = LOOK && look;
+  const bool scaling = op.parent_scaler != nullptr;
+  // a "wide tip" (kernels_repeats.hpp: a cherry known per class of sites): neither vector nor byte codes; the
+  // pfrag field holds its class codes (32 bits each), lut its table, childN_index the rows of that table
+  const S20Child ch1 = { op.clv1, op.codes1, WIDE ? s20_wide_codes(op.clv1, op.codes1, op.pfrag1) : nullptr, op.lut1, s1,
+                         op.child1_index, (wide_lds & 2u) != 0 };
+  const S20Child ch2 = { op.clv2, op.codes2, WIDE ? s20_wide_codes(op.clv2, op.codes2, op.pfrag2) : nullptr, op.lut2, s2,
+                         op.child2_index, (wide_lds & 4u) != 0 };
+  // The side child: the one that is not handed over (carried != 0), or the second of two (carried == 0: the term of
+  // child 1 then stands in for the handed-over product).  A folded cherry or a class table is child 2 of its operation.
+  const bool side2 = carried != 2;
+  const S20Child side = side2 ? ch2 : ch1;
+  const bool side_mem = !side.codes && !side.wide && !(side2 && (fold2 || look2));
+
+  // ---- fetch group: every load of this operation that depends on no other vector load goes out here, back to back;
+  // nothing is consumed (and so nothing waited for) before the carried phase below has issued its products.  A child that
+  // is absent costs a scalar branch, no wait.
+  unsigned raw1e = 0, raw1o = 0, raw2e = 0, raw2o = 0;            // tip codes: a 16-bit pair in raw?e, or two wide codes
+  if (op.codes1) raw1e = s20_ld_code_pair(op.codes1 + site0);
+  else if (ch1.wide) { raw1e = ch1.wide[site0]; raw1o = ch1.wide[site0 + 1]; }
+  if (op.codes2) raw2e = s20_ld_code_pair(op.codes2 + site0);
+  else if (ch2.wide) { raw2e = ch2.wide[site0]; raw2o = ch2.wide[site0 + 1]; }
+  // a folded cherry's two code words, or the two or three of a class-table child
+  unsigned rawf[3];                 // (defined where the operation has such a child; never set from a constant: a
+                                    // move into a register that another path loads into waits for that load)
+  S20Fold f = { nullptr, nullptr, 0, 0, fold2, look2, true };
+  struct Tail { unsigned carried, slot1, slot2, flags; };      // what follows PlanOp::d
+  static_assert(offsetof(PlanOp, carried) % 8 == 0 && offsetof(PlanOp, flags) == offsetof(PlanOp, carried) + 12, "PlanOp layout");
+  Tail tail = { 0, 0, 0, 0 };
+  if (fold2)
   {
+    // (only what is needed of the cherry's entry: both scalar fetches go out here, the tail is consumed after the
+    // carried phase)
     const uint8_t * ca = as_global(plan_fetch(&fentry->d.codes1)), * cb = as_global(plan_fetch(&fentry->d.codes2));
-    struct Tail { unsigned carried, slot1, slot2, flags; };      // what follows PlanOp::d
-    static_assert(offsetof(PlanOp, carried) % 8 == 0 && offsetof(PlanOp, flags) == offsetof(PlanOp, carried) + 12, "PlanOp layout");
-    const Tail tail = plan_fetch(reinterpret_cast<const Tail *>(&fentry->carried));
-    fa = lds + tail.slot1;
-    fb = lds + tail.slot2;
-    if (ftrans) fstore = !(tail.flags & 1u);
-    const unsigned ae = ca[site0], ao = ca[site0 + 1], be = cb[site0], bo = cb[site0 + 1];
-    fcodes = ae | (ao << 8) | (be << 16) | (bo << 24);
-    // (one register through the rate loop, not four: without the fence the optimiser sees through the packing)
-    asm volatile("" : "+v"(fcodes));
-    unsigned * fscaler = const_cast<unsigned *>(op.scaler2);
-    if (fscaler)
-    {
-      const unsigned * bits = reinterpret_cast<const unsigned *>(fb + s20_tip_slot(RT, lut_used));
-      const unsigned pe = ae * lut_used + be, po = ao * lut_used + bo;
-      fsmall = ((bits[pe >> 5] >> (pe & 31u)) & 1u) | (((bits[po >> 5] >> (po & 31u)) & 1u) << 1);
-      if (q == 0)
-      {
-        fscaler[site0] = fsmall & 1u;
-        fscaler[site0 + 1] = fsmall >> 1;
-      }
-    }
+    tail = plan_fetch(reinterpret_cast<const Tail *>(&fentry->carried));
+    rawf[0] = s20_ld_code_pair(ca + site0);
+    rawf[1] = s20_ld_code_pair(cb + site0);
   }
-  if (LOOK && look)
+  else if (look2)
   {
     const uint8_t * ca = reinterpret_cast<const uint8_t *>(op.clv2), * cb = reinterpret_cast<const uint8_t *>(op.pmat2);
     const uint8_t * cc = reinterpret_cast<const uint8_t *>(op.pfrag2);
-    unsigned ke = ca[site0] * lut_used + cb[site0], ko = ca[site0 + 1] * lut_used + cb[site0 + 1];
-    if (cc) { ke = ke * lut_used + cc[site0]; ko = ko * lut_used + cc[site0 + 1]; }
-    fcodes = ke | (ko << 16);                   // (at most S20_LOOK_MAX classes)
-    asm volatile("" : "+v"(fcodes));
+    rawf[0] = s20_ld_code_pair(ca + site0);
+    rawf[1] = s20_ld_code_pair(cb + site0);
+    if (cc) rawf[2] = s20_ld_code_pair(cc + site0);
   }
-  unsigned c1e = 0, c1o = 0, c2e = 0, c2o = 0;
-  // a "wide tip" (kernels_repeats.hpp: a cherry known per class of sites): neither vector nor byte codes; the
-  // pfrag field holds its class codes (32 bits each), lut its table, childN_index the rows of that table
-  const unsigned * w1 = WIDE ? s20_wide_codes(op.clv1, op.codes1, op.pfrag1) : nullptr;
-  const unsigned * w2 = WIDE ? s20_wide_codes(op.clv2, op.codes2, op.pfrag2) : nullptr;
-  if (op.codes1) { c1e = op.codes1[site0]; c1o = op.codes1[site0 + 1]; }
-  else if (w1) { c1e = w1[site0]; c1o = w1[site0 + 1]; }
-  if (op.codes2) { c2e = op.codes2[site0]; c2o = op.codes2[site0 + 1]; }
-  else if (w2) { c2e = w2[site0]; c2o = w2[site0 + 1]; }
-  const bool scaling = op.parent_scaler != nullptr;
+  // the scaler counts the tail adds for a child that is not handed over and whose counts are kept per site
+  // (per class: requested below, once the codes are there)
+  constexpr unsigned NS = RS ? RT : 1;
+  unsigned cnt_e[NS] = {}, cnt_o[NS] = {}, cnt2_e[NS] = {}, cnt2_o[NS] = {};
+  if (scaling && op.scaler1 && carried != 1 && (RS || !ch1.wide))
+  {
+#pragma unroll
+    for (unsigned r = 0; r < NS; ++r)
+    {
+      cnt_e[r] = op.scaler1[RS ? site0 * RT + r : site0];
+      cnt_o[r] = op.scaler1[RS ? (site0 + 1) * RT + r : site0 + 1];
+    }
+  }
+  if (scaling && op.scaler2 && carried != 2 && !fold2 && !look2 && (RS || !ch2.wide))
+  {
+#pragma unroll
+    for (unsigned r = 0; r < NS; ++r)
+    {
+      cnt2_e[r] = op.scaler2[RS ? site0 * RT + r : site0];
+      cnt2_o[r] = op.scaler2[RS ? (site0 + 1) * RT + r : site0 + 1];
+    }
+  }
+  // a side child read from memory: the five words of rate 0
+  double2 b0[5];
+  if (side_mem)
+  {
+#pragma unroll
+    for (int ks = 0; ks < 5; ++ks) b0[ks] = s20_ld(side.clv + (size_t)blk * RT * S20_UNIT + ks * 128 + lane * 2, nt_ld);
+  }
+  s20_pin_loads();
+
+  // ---- carried phase: X[r] <- P_r . X[r] for the handed-over child, under the loads above (it needs none of them)
+  if (carried)
+  {
+    const double * sc = (carried == 1) ? s1 : s2;
+#pragma unroll
+    for (unsigned r = 0; r < RT; ++r) s20_child_regs_ip(X[r], sc + r * S20_CFRAGS, lane);
+  }
+
+  // ---- the fetched words are consumed from here on (the fences keep the optimiser from unpacking a word in the block
+  // that loads it, which puts a wait there)
+  asm volatile("" : "+v"(raw1e), "+v"(raw2e));
+  if (fold2 || look2) asm volatile("" : "+v"(rawf[0]), "+v"(rawf[1]));
+  // the folded cherry: its four tip codes in one register, its scaling decisions in another (bit 0 / 1: even / odd site)
+  if (fold2)
+  {
+    f.fa = lds + tail.slot1;
+    f.fb = lds + tail.slot2;
+    if (ftrans) f.store = !(tail.flags & 1u);
+    const unsigned ae = rawf[0] & 255u, ao = rawf[0] >> 8, be = rawf[1] & 255u, bo = rawf[1] >> 8;
+    f.codes = rawf[0] | (rawf[1] << 16);
+    // (one register through the rate loop, not four: without the fence the optimiser sees through the packing)
+    asm volatile("" : "+v"(f.codes));
+    unsigned * fscaler = const_cast<unsigned *>(op.scaler2);
+    if (fscaler)
+    {
+      const unsigned * bits = reinterpret_cast<const unsigned *>(f.fb + s20_tip_slot(RT, lut_used));
+      const unsigned pe = ae * lut_used + be, po = ao * lut_used + bo;
+      f.small = ((bits[pe >> 5] >> (pe & 31u)) & 1u) | (((bits[po >> 5] >> (po & 31u)) & 1u) << 1);
+      if (q == 0)
+      {
+        fscaler[site0] = f.small & 1u;
+        fscaler[site0 + 1] = f.small >> 1;
+      }
+    }
+  }
+  else if (look2)
+  {
+    unsigned ke = (rawf[0] & 255u) * lut_used + (rawf[1] & 255u), ko = (rawf[0] >> 8) * lut_used + (rawf[1] >> 8);
+    if (op.pfrag2) asm volatile("" : "+v"(rawf[2]));
+    if (op.pfrag2) { ke = ke * lut_used + (rawf[2] & 255u); ko = ko * lut_used + (rawf[2] >> 8); }
+    f.codes = ke | (ko << 16);                  // (at most S20_LOOK_MAX classes)
+    asm volatile("" : "+v"(f.codes));
+  }
+  unsigned c1e = raw1e, c1o = raw1o, c2e = raw2e, c2o = raw2o;
+  if (op.codes1) { c1e = raw1e & 255u; c1o = raw1e >> 8; }
+  if (op.codes2) { c2e = raw2e & 255u; c2o = raw2e >> 8; }
+  // counts kept per class (a wide tip's, like its vector; a class table's): indexed by the class codes
+  if (!RS && scaling)
+  {
+    if (WIDE && op.scaler1 && carried != 1 && ch1.wide) { cnt_e[0] = op.scaler1[c1e]; cnt_o[0] = op.scaler1[c1o]; }
+    if (WIDE && op.scaler2 && carried != 2 && ch2.wide) { cnt2_e[0] = op.scaler2[c2e]; cnt2_o[0] = op.scaler2[c2o]; }
+    if (look2 && op.scaler2) { cnt2_e[0] = op.scaler2[f.codes & 0xffffu]; cnt2_o[0] = op.scaler2[f.codes >> 16]; }
+  }
   int small_e = 1, small_o = 1;
   // (FOLD: the tips' codes share a register too -- the instantiation has none to spare)
   unsigned cpack = 0;
@@ -628,53 +801,30 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
     cpack = c1e | (c1o << 8) | (c2e << 16) | (c2o << 24);
     asm volatile("" : "+v"(cpack));
   }
+  // ---- side phase
 #pragma unroll
   for (unsigned r = 0; r < RT; ++r)
   {
     const size_t ubase = ((size_t)blk * RT + r) * S20_UNIT;
-    double2 t1[5], t2[5];
+    double2 t[5];
     if (FOLD) { c1e = cpack & 255u; c1o = (cpack >> 8) & 255u; c2e = (cpack >> 16) & 255u; c2o = cpack >> 24; }
-    if (carried == 1) s20_child_regs_c(X[r], s1 + r * S20_CFRAGS, lane, t1);
-    else if (w1 && (wide_lds & 2u)) s20_child_tip(s1 + r * op.child1_index * S20_LUT_RS, c1e, c1o, q, t1, S20_LUT_RS);
-    else if (w1) s20_child_tip(op.lut1 + (size_t)r * op.child1_index * 20, c1e, c1o, q, t1);
-    else if (!op.codes1) s20_child_inner_c(op.clv1 + ubase, s1 + r * S20_CFRAGS, lane, t1, nt_ld);
-    else if (lut_lds) s20_child_tip(s1 + r * lut_used * S20_LUT_RS, c1e, c1o, q, t1, S20_LUT_RS);
-    else s20_child_tip(op.lut1 + (size_t)r * lut_codes * 20, c1e, c1o, q, t1);
-    if (FOLD)
+    if (!carried)
     {
-      if (carried == 2) s20_child_regs_c(X[r], s2 + r * S20_CFRAGS, lane, t2);
-      else if (op.codes2) s20_child_tip(s2 + r * lut_used * S20_LUT_RS, c2e, c2o, q, t2, S20_LUT_RS);
-      else if (LOOK && look) s20_child_tip(op.lut2 + (size_t)r * op.child2_index * 20, fcodes & 0xffffu, fcodes >> 16, q, t2);
-      else
-      {
-        // the operand block: built from the cherry's tables (and stored), or read from memory -- one product either way
-        double2 b[5];
-        if (fold)
-        {
-          s20_fold_block(fa + r * lut_used * S20_LUT_RS, fb + r * lut_used * S20_LUT_RS, fcodes, fsmall, q, b);
-          if (fstore) s20_store_d(const_cast<double *>(op.clv2) + ubase, lane, b, nt_st);
-        }
-        else
-        {
+      // both children are side terms: child 1's takes the place of the handed-over product
+      const S20Fold none = { nullptr, nullptr, 0, 0, false, false, true };
+      s20_side_term<RT, WIDE, false, false>(ch1, none, r, c1e, c1o, b0, false, ubase, lane, lut_codes, lut_used, lut_lds,
+                                            nt_ld, nt_st, t);
 #pragma unroll
-          for (int ks = 0; ks < 5; ++ks) b[ks] = s20_ld(op.clv2 + ubase + ks * 128 + lane * 2, nt_ld);
-        }
-        s20_child_regs_c(b, s2 + r * S20_CFRAGS, lane, t2);
-      }
+      for (int k = 0; k < 5; ++k) X[r][k] = t[k];
     }
-    else if (carried == 2) s20_child_regs_c(X[r], s2 + r * S20_CFRAGS, lane, t2);
-    else if (w2 && (wide_lds & 4u)) s20_child_tip(s2 + r * op.child2_index * S20_LUT_RS, c2e, c2o, q, t2, S20_LUT_RS);
-    else if (w2) s20_child_tip(op.lut2 + (size_t)r * op.child2_index * 20, c2e, c2o, q, t2);
-    else if (!op.codes2) s20_child_inner_c(op.clv2 + ubase, s2 + r * S20_CFRAGS, lane, t2, nt_ld);
-    else if (lut_lds) s20_child_tip(s2 + r * lut_used * S20_LUT_RS, c2e, c2o, q, t2, S20_LUT_RS);
-    else s20_child_tip(op.lut2 + (size_t)r * lut_codes * 20, c2e, c2o, q, t2);
-    // X[r] has been consumed (if it was an operand at all): it now takes the result
+    s20_side_term<RT, WIDE, FOLD, LOOK>(side, f, r, side2 ? c2e : c1e, side2 ? c2o : c1o, b0, true, ubase, lane, lut_codes,
+                                        lut_used, lut_lds, nt_ld, nt_st, t);
     int re = 1, ro = 1;
 #pragma unroll
     for (int k = 0; k < 5; ++k)
     {
-      X[r][k].x = t1[k].x * t2[k].x;
-      X[r][k].y = t1[k].y * t2[k].y;
+      X[r][k].x = X[r][k].x * t[k].x;
+      X[r][k].y = X[r][k].y * t[k].y;
       re &= (X[r][k].x < SCALE_THRESHOLD);
       ro &= (X[r][k].y < SCALE_THRESHOLD);
     }
@@ -701,16 +851,10 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
         const size_t ie = site0 * RT + r, io = (site0 + 1) * RT + r;
         ce = se ? 1u : 0u;
         co = so ? 1u : 0u;
-        if (op.scaler1)
-        {
-          if (carried == 1) { ce += xe[RS ? r : 0]; co += xo[RS ? r : 0]; }
-          else { ce += op.scaler1[ie]; co += op.scaler1[io]; }
-        }
-        if (op.scaler2)
-        {
-          if (carried == 2) { ce += xe[RS ? r : 0]; co += xo[RS ? r : 0]; }
-          else { ce += op.scaler2[ie]; co += op.scaler2[io]; }
-        }
+        // (the counts of the children that are not handed over came with the fetch group)
+        ce += cnt_e[RS ? r : 0] + cnt2_e[RS ? r : 0];
+        co += cnt_o[RS ? r : 0] + cnt2_o[RS ? r : 0];
+        if (carried && (carried == 1 ? op.scaler1 : op.scaler2)) { ce += xe[RS ? r : 0]; co += xo[RS ? r : 0]; }
         op.parent_scaler[ie] = ce;
         op.parent_scaler[io] = co;
       }
@@ -744,21 +888,12 @@ __device__ inline void s20_chain_op(const OpDesc & op, unsigned carried, double2
   {
     ce = small_e ? 1u : 0u;
     co = small_o ? 1u : 0u;
-    // (a wide tip's counts are kept per class, like its vector: indexed by the class codes)
-    if (op.scaler1)
-    {
-      if (carried == 1) { ce += xe[0]; co += xo[0]; }
-      else if (w1) { ce += op.scaler1[c1e]; co += op.scaler1[c1o]; }
-      else { ce += op.scaler1[site0]; co += op.scaler1[site0 + 1]; }
-    }
-    if (op.scaler2)
-    {
-      if (carried == 2) { ce += xe[0]; co += xo[0]; }
-      else if (FOLD && fold) { ce += fsmall & 1u; co += fsmall >> 1; }
-      else if (LOOK && look) { ce += op.scaler2[fcodes & 0xffffu]; co += op.scaler2[fcodes >> 16]; }
-      else if (w2) { ce += op.scaler2[c2e]; co += op.scaler2[c2o]; }
-      else { ce += op.scaler2[site0]; co += op.scaler2[site0 + 1]; }
-    }
+    // (the counts of the children that are not handed over were requested with the fetch group, or per class code
+    // right behind the carried phase)
+    ce += cnt_e[0] + cnt2_e[0];
+    co += cnt_o[0] + cnt2_o[0];
+    if (FOLD) { ce += f.small & 1u; co += f.small >> 1; }       // a folded cherry's own decisions (0 without one)
+    if (carried && (carried == 1 ? op.scaler1 : op.scaler2)) { ce += xe[0]; co += xo[0]; }
     op.parent_scaler[site0] = ce;
     op.parent_scaler[site0 + 1] = co;
   }
@@ -920,6 +1055,10 @@ __global__ __launch_bounds__(64 * S20_CHAIN_WAVES, 1) void k_traverse_s20(PlanVi
           const PlanOp po = plan_fetch_op(plan_ops_ + ch.first + i);
           if (FOLD)
           {
+            // (the whole entry in one group of scalar loads, the flags among them: s20_chain_op's own fence stands
+            // behind the test of the flags, which would cost a round trip of its own)
+            asm volatile("" :: "s"(po.flags), "s"(po.carried), "s"(po.d.clv1), "s"(po.d.codes1), "s"(po.d.clv2),
+                         "s"(po.d.codes2), "s"(po.d.scaler1), "s"(po.d.scaler2), "s"(po.d.parent_scaler));
             if (po.flags & 8u) continue;                // built by the next entry
             // (tip tables are staged wherever cherries are folded: s20_fold_lds)
             // (bit 0 counts here without TRANS as well: a storing schedule with folds defers the stores of folded
