@@ -634,6 +634,85 @@ PLL_EXPORT int pllhip_node_ancestral_finish(pllhip_anc_batch_t * batch);
    of a sharded partition), and its staging chunks (the largest count of any device) */
 PLL_EXPORT void pllhip_node_ancestral_last_times(double * kernel_ms, unsigned long long * chunks);
 
+/* ---- site categories: per-site posteriors of the rate categories / mixture components, site rates and the EM fit of
+ * the category weights ("Site categories") ----
+ * A set holds, on one device, the table of an edge kept per category: for site n and category r
+ *     l[n][r] = sum_i pi_r[i] parent[n, r, i] sum_j P_r[i][j] child[n, r, j]      (pi_r, q_r: those of freqs_indices[r])
+ * under the scaling and p-inv rules of pll_compute_edge_loglikelihood, as rate part A = (1 - q_r) l, invariant part
+ * B = q_r pi_r[invariant[n]] and scaler count c[n]; g = A + B.  With weights w: T[n] = sum_r w_r g[n][r],
+ * lnl[n] = log T[n] - c[n] 256 ln 2 (the per-site value of the edge log-likelihood, up to rounding),
+ * post[n][r] = w_r A[n][r] / T[n], inv[n] = sum_r w_r B[n][r] / T[n], rate[n] = sum_r post[n][r] rates[r],
+ * category[n] = the smallest r with the largest post[n][r] and category_prob[n] that very double,
+ * expected[r] = sum_n m_n w_r g[n][r] / T[n] with the pattern weights m.  A site with T[n] = 0 has all-zero rows, rate 0,
+ * category 0 and lnl = -inf, and adds nothing to `expected`.
+ * The vectors do not depend on the weights, so with the table resident the weights are fitted by EM with no further
+ * traversal: w'_r = expected[r] / sum_n m_n, one pass over the table per iteration (the divisor is taken as
+ * sum_r expected[r], the same number up to rounding, so that the new weights add up to 1 to `cats` roundings).
+ * PLLHIP_SITECAT_BLOCKS (environment, read at the call; unset or 0: no cap) caps the workgroups of every launch of
+ * these calls; per-site results do not depend on it, sums are bit-identical from run to run at a given cap. */
+typedef struct pllhip_sitecat pllhip_sitecat_t;
+
+/* The table of an edge (arguments as for pll_compute_edge_loglikelihood).  Snapshots the partition's category weights,
+   p-inv, rates and pattern weights; owns its buffers on the partition's device and stays valid after the partition has
+   changed or gone.  Changes nothing in the partition (vectors that exist as their operation only are stored, as for
+   any reader).  NULL on error: NULL arguments, an index out of range, a partition spread over devices. */
+PLL_EXPORT pllhip_sitecat_t * pllhip_sitecat_edge(pll_partition_t * partition, unsigned int parent_clv_index,
+                                                  int parent_scaler_index, unsigned int child_clv_index,
+                                                  int child_scaler_index, unsigned int matrix_index,
+                                                  const unsigned int * freqs_indices);
+/* A set from a host table g[sites][cats] (non-negative, finite), on the device of pllhip_get_device(): the EM fit and
+   the posteriors of any mixture (no invariant parts, no rates: `rate` and `invariant_prob` of its posteriors are NULL).
+   pattern_weights NULL: 1 each; weights NULL: 1 / cats each.  At most 256 categories. */
+PLL_EXPORT pllhip_sitecat_t * pllhip_sitecat_from_table(unsigned int sites, unsigned int cats, const double * g,
+                                                        const unsigned int * pattern_weights, const double * weights);
+PLL_EXPORT void pllhip_sitecat_destroy(pllhip_sitecat_t * set);
+PLL_EXPORT unsigned int pllhip_sitecat_sites(const pllhip_sitecat_t * set);
+PLL_EXPORT unsigned int pllhip_sitecat_categories(const pllhip_sitecat_t * set);
+/* rate_part / inv_part [sites][cats] (A and B above), counts [sites]; any may be NULL */
+PLL_EXPORT int pllhip_sitecat_table(pllhip_sitecat_t * set, double * rate_part, double * inv_part,
+                                    unsigned int * counts);
+
+#define PLLHIP_SITECAT_POSTERIORS (1u << 0)   /* also the full post[sites][cats] */
+typedef struct pllhip_site_posteriors
+{
+  unsigned int sites, cats;
+  double * rate;                 /* [sites]; NULL for a set made from a host table */
+  unsigned char * category;      /* [sites] */
+  double * category_prob;        /* [sites] */
+  double * invariant_prob;       /* [sites]; NULL for a set made from a host table */
+  double * lnl;                  /* [sites] */
+  double * posterior;            /* [sites][cats]; NULL without PLLHIP_SITECAT_POSTERIORS */
+  double * expected;             /* [cats] */
+  double loglh;                  /* sum_n m_n lnl[n] (-inf if a site with m_n > 0 has T = 0) */
+} pllhip_site_posteriors_t;
+
+/* weights NULL: the set's own.  Weights must be finite, non-negative and not all zero.  NULL on error. */
+PLL_EXPORT pllhip_site_posteriors_t * pllhip_sitecat_posteriors(pllhip_sitecat_t * set, const double * weights,
+                                                                unsigned int flags);
+PLL_EXPORT void pllhip_site_posteriors_destroy(pllhip_site_posteriors_t * posteriors);
+
+typedef struct pllhip_sitecat_em_params
+{
+  const double * start;          /* NULL: the set's own weights */
+  double epsilon;                /* stop once an iteration gains less than this in sum_n m_n lnl[n] */
+  unsigned int max_iterations;
+} pllhip_sitecat_em_params_t;
+
+#define PLLHIP_SITECAT_TRAIL_MAX 64
+/* EM on the weights (rates, p-inv and vectors fixed).  Iteration i (from 0) evaluates the table at w_i, which gives
+   L_i = sum_n m_n lnl[n] and w_(i+1); it stops at the first i > 0 with L_i - L_(i-1) < epsilon, or at
+   i = max_iterations.  Out: weights = w_i, *loglh = L_i, *iterations = i (the updates made).  trail_weights [64][cats]
+   and trail_loglh [64] (or NULL) receive w_i and L_i of the first 64 evaluations, the final one included.
+   The set's own weights are not changed.  Fails with PLL_ERROR_PARAM_INVALID for a set made from a partition with an
+   ascertainment-bias correction (the correction depends on the weights), and when a site with m_n > 0 has T = 0 (the
+   message names the site). */
+PLL_EXPORT int pllhip_sitecat_em_weights(pllhip_sitecat_t * set, const pllhip_sitecat_em_params_t * params,
+                                         double * weights, double * loglh, unsigned int * iterations,
+                                         double * trail_weights, double * trail_loglh);
+/* this thread's last calls: device time of the table kernel, of the last pllhip_sitecat_posteriors (posterior and
+   reduction kernels) and of the last EM fit (all its iterations, host waits included) in ms */
+PLL_EXPORT void pllhip_sitecat_last_times(double * table_ms, double * posterior_ms, double * em_ms);
+
 /* ---- simulated alignments: the parametric bootstrap ("Simulated alignments") ----
  * Replicates of an alignment drawn from the partition's own model -- rate categories and their weights, p-inv and
  * frequencies of params_indices[category], and the transition matrices as pll_update_prob_matrices left them -- along

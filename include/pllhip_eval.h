@@ -29,6 +29,7 @@
 #define PLLHIP_EVAL_H_INCLUDED
 
 #include "pll.h"
+#include "pllhip.h"   /* pllhip_site_posteriors_t */
 
 #ifdef __cplusplus
 extern "C" {
@@ -254,6 +255,29 @@ typedef struct pllhip_ancestral
 
 PLL_EXPORT pllhip_ancestral_t * pllhip_eval_compute_ancestral(pllhip_eval_t * ev, unsigned int flags);
 PLL_EXPORT void pllhip_eval_destroy_ancestral(pllhip_ancestral_t * anc);
+
+/* ---------------------------------------------------------------------------
+ * Site categories (include/pllhip.h, "site categories"): which rate category or mixture component every site
+ * belongs to, its empirical-Bayes rate, and the EM fit of the category weights -- what IQ-TREE writes to .rate and
+ * .siteprob, and the E-step of a free-rate (+R) or mixture-weight fit.
+ * pllhip_eval_site_rates evaluates incrementally at the current root edge and returns one pllhip_site_posteriors_t
+ * per local partition, in partition order, behind a NULL entry; flags: PLLHIP_SITECAT_POSTERIORS for the full
+ * sites x categories table.  NULL on error (pll_errno set).
+ * pllhip_eval_optimize_rate_weights evaluates likewise, fits the category weights of one local partition by EM from
+ * its current weights (rates, p-inv and vectors fixed: no traversal per iteration), installs them with
+ * pll_set_category_weights and returns the log-likelihood of the whole driver afterwards; NaN on error.  It does NOT
+ * renormalise sum_r w_r rate_r = 1 nor rescale the branch lengths: a +R fit does both after its rate step, and that
+ * stays the caller's.  pllhip_eval_rate_weights_trail copies what the last fit evaluated -- the weights
+ * [evaluations][categories] and the partition's log-likelihood at them, the first 64 -- and returns their number.
+ * On the HIP engine the table, the posteriors and the EM run on the device (pllhip_sitecat_*).  Where the library has
+ * no such calls (the CPU oracle) the driver computes the same definitions on the host from the partition's own arrays
+ * (clv, tipchars / tipmap, pmatrix, scale_buffer, invariant).
+ * ------------------------------------------------------------------------- */
+PLL_EXPORT pllhip_site_posteriors_t ** pllhip_eval_site_rates(pllhip_eval_t * ev, unsigned int flags);
+PLL_EXPORT void pllhip_eval_destroy_site_rates(pllhip_site_posteriors_t ** rates);
+PLL_EXPORT double pllhip_eval_optimize_rate_weights(pllhip_eval_t * ev, unsigned int partition, double epsilon,
+                                                    unsigned int max_iterations);
+PLL_EXPORT unsigned int pllhip_eval_rate_weights_trail(const pllhip_eval_t * ev, double * weights, double * loglh);
 
 PLL_EXPORT unsigned long pllhip_eval_ops(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_pmatrix_updates(const pllhip_eval_t * ev);

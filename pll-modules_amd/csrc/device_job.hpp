@@ -97,9 +97,33 @@ struct MatrixTables
 };
 bool matrix_tables(pll_partition_t * p, MatrixTables & out);
 
+// the per-site, per-rate likelihood table of an edge (kernels_sitecat.hpp) into the caller's rate-major planes on the
+// partition's device: A[r][plane] and c[sites], B[r][plane] when it is not null; `plane` is even and the planes are
+// 16-byte aligned.  Makes the operand set-up every edge reader makes (model, queued matrices, lookup tables, vectors
+// and scaler counts that exist as their operation only) and enqueues the family's kernel on the engine's stream; the
+// partition must not be a router (pll_core.hip)
+struct SiteCatPlanes
+{
+  double * A = nullptr, * B = nullptr;
+  unsigned * c = nullptr;
+  size_t plane = 0;
+};
+bool sitecat_edge_table(pll_partition_t * p, unsigned parent_clv, int parent_scaler, unsigned child_clv, int child_scaler,
+                        unsigned matrix_index, const unsigned * freqs_indices, const SiteCatPlanes & planes);
+
 inline unsigned grid_for(size_t items, unsigned per_block)
 {
   return (unsigned)std::max<size_t>(1, std::min<size_t>((items + per_block - 1) / per_block, 4096));
+}
+
+// <env>=<n>: at most n workgroups (0 or unset: no cap), read at every call -- a test knob: with a small cap a wave or a
+// thread walks several strides at a size a test can afford
+inline unsigned capped_grid(const char * env, unsigned long long wanted)
+{
+  const char * v = getenv(env);
+  const long long cap = v ? atoll(v) : 0;
+  if (cap > 0 && (unsigned long long)cap < wanted) wanted = (unsigned long long)cap;
+  return (unsigned)std::max<unsigned long long>(1, wanted);
 }
 
 // <env>=<0..64>: only that many bits of a hash are used (a test knob: with few bits the full compare and the probing

@@ -15,6 +15,10 @@
 #pragma weak pllhip_node_ancestral_begin
 #pragma weak pllhip_node_ancestral_add
 #pragma weak pllhip_node_ancestral_finish
+#pragma weak pllhip_sitecat_edge          /* HIP engine only: with the CPU oracle the driver computes the table itself */
+#pragma weak pllhip_sitecat_posteriors
+#pragma weak pllhip_sitecat_em_weights
+#pragma weak pllhip_sitecat_destroy
 #include <stdarg.h>
 
 static __thread pllhip_eval_t * cb_self;   /* pll_utree_traverse callbacks carry no user pointer */
@@ -124,7 +128,7 @@ void pllhip_eval_destroy(pllhip_eval_t * ev)
   free(ev->parts); free(ev->params); free(ev->sumtables); free(ev->part_lnl);
   free(ev->clv_valid); free(ev->pmat_valid); free(ev->trav); free(ev->ops);
   free(ev->brlens); free(ev->midx); free(ev->slot_buf);
-  free(ev->brlen_scalers); free(ev->nr_x); free(ev->nr_converged);
+  free(ev->brlen_scalers); free(ev->nr_x); free(ev->nr_converged); free(ev->em_trail_w);
   if (ev->part_brlens)
   {
     for (p = 0; p < ev->nparts; ++p) free(ev->part_brlens[p]);
@@ -704,6 +708,343 @@ fail:
   pllhip_eval_destroy_ancestral(anc);
   ev->root = old_root;
   return NULL;
+}
+
+/* ---------------------------------------------------------------------- */
+/* Site categories: posteriors of the rate categories, site rates, and the */
+/* EM fit of the category weights (include/pllhip.h, "site categories")    */
+/* ---------------------------------------------------------------------- */
+
+#define SC_LN_SCALE 177.445678223345993274     /* 256 ln 2 */
+#define SC_RATE_MAXDIFF 4                      /* libpll-2's PLL_SCALE_RATE_MAXDIFF */
+
+/* element (n, r, j) of a vector as the host arrays hold it: a coded tip through tipchars / tipmap */
+static double sc_elem(const pll_partition_t * p, unsigned int clv, size_t n, unsigned int r, unsigned int j)
+{
+  if ((p->attributes & PLL_ATTRIB_PATTERN_TIP) && clv < p->tips)
+    return (double)((p->tipmap[p->tipchars[clv][n]] >> j) & 1);
+  return p->clv[clv][(n * p->rate_cats + r) * p->states_padded + j];
+}
+
+static unsigned int sc_count(const pll_partition_t * p, int ps, int cs, size_t x)
+{
+  return (ps == PLL_SCALE_BUFFER_NONE ? 0u : p->scale_buffer[ps][x]) + (cs == PLL_SCALE_BUFFER_NONE ? 0u : p->scale_buffer[cs][x]);
+}
+
+/* The definitions of include/pllhip.h in plain C from the partition's host arrays: A, B [sites][cats], c [sites].
+   The second implementation of the table kernels (kernels_sitecat.hpp), for libraries that keep host arrays. */
+static void sc_host_table(const pll_partition_t * p, unsigned int pc, int ps, unsigned int cc, int cs, unsigned int m,
+                          const unsigned int * fi, double * A, double * B, unsigned int * c)
+{
+  const unsigned int S = p->states, Sp = p->states_padded, R = p->rate_cats;
+  const int per_rate = (p->attributes & PLL_ATTRIB_RATE_SCALERS) != 0;
+  size_t n;
+  unsigned int r, i, j;
+  for (n = 0; n < p->sites; ++n)
+  {
+    unsigned int cnt = per_rate ? ~0u : sc_count(p, ps, cs, n);
+    const int state = p->invariant ? p->invariant[n] : -1;
+    double binv = 0.0;
+    int descale;
+    for (r = 0; per_rate && r < R; ++r)
+      if (sc_count(p, ps, cs, n * R + r) < cnt) cnt = sc_count(p, ps, cs, n * R + r);
+    for (r = 0; r < R; ++r)
+      if (p->prop_invar[fi[r]] > 0.0 && state >= 0)
+        binv += p->rate_weights[r] * p->prop_invar[fi[r]] * p->frequencies[fi[r]][state];
+    descale = binv > 0.0 && cnt > 0;
+    for (r = 0; r < R; ++r)
+    {
+      const double * pi = p->frequencies[fi[r]], q = p->prop_invar[fi[r]];
+      const double * P = p->pmatrix[m] + (size_t)r * S * Sp;
+      double l = 0.0;
+      for (i = 0; i < S; ++i)
+      {
+        double a = 0.0;
+        for (j = 0; j < S; ++j) a += P[i * Sp + j] * sc_elem(p, cc, n, r, j);
+        l += pi[i] * sc_elem(p, pc, n, r, i) * a;
+      }
+      if (per_rate)
+      {
+        unsigned int d = sc_count(p, ps, cs, n * R + r) - cnt;
+        if (d > SC_RATE_MAXDIFF) d = SC_RATE_MAXDIFF;
+        if (d) l *= ldexp(1.0, -256 * (int)d);
+      }
+      if (descale) l = (cnt <= 3) ? ldexp(l, -256 * (int)cnt) : 0.0;
+      A[n * R + r] = (q > 0.0) ? (1.0 - q) * l : l;
+      B[n * R + r] = (q > 0.0 && state >= 0) ? q * pi[state] : 0.0;
+    }
+    c[n] = descale ? 0u : cnt;
+  }
+}
+
+/* T[n], and what follows from it: any of the outputs may be NULL.  Returns sum_n m_n lnl[n]. */
+static double sc_host_posteriors(size_t N, unsigned int R, const double * A, const double * B, const unsigned int * c,
+                                 const unsigned int * m, const double * w, const double * rho,
+                                 pllhip_site_posteriors_t * po, double * expected)
+{
+  size_t n;
+  unsigned int r;
+  double loglh = 0.0;
+  for (r = 0; r < R; ++r) expected[r] = 0.0;
+  for (n = 0; n < N; ++n)
+  {
+    const double * a = A + n * R, * b = B + n * R;
+    double T = 0.0, rate = 0.0, inv = 0.0, best = 0.0, lnl;
+    unsigned int idx = 0;
+    for (r = 0; r < R; ++r) T += w[r] * (a[r] + b[r]);
+    lnl = log(T) - (double)c[n] * SC_LN_SCALE;
+    for (r = 0; r < R; ++r)
+    {
+      const double post = (T > 0.0) ? (w[r] * a[r]) / T : 0.0;
+      if (po && po->posterior) po->posterior[n * R + r] = post;
+      rate += post * rho[r];
+      inv += w[r] * b[r];
+      if (post > best) { best = post; idx = r; }
+      if (T > 0.0 && m[n]) expected[r] += (double)m[n] * ((w[r] * (a[r] + b[r])) / T);
+    }
+    if (m[n]) loglh += (double)m[n] * lnl;
+    if (!po) continue;
+    po->rate[n] = rate;
+    po->category[n] = (unsigned char)idx;
+    po->category_prob[n] = best;
+    po->invariant_prob[n] = (T > 0.0) ? inv / T : 0.0;
+    po->lnl[n] = lnl;
+  }
+  return loglh;
+}
+
+static void sc_destroy_one(pllhip_site_posteriors_t * po)
+{
+  if (!po) return;
+  free(po->rate); free(po->category); free(po->category_prob); free(po->invariant_prob); free(po->lnl);
+  free(po->posterior); free(po->expected);
+  free(po);
+}
+
+void pllhip_eval_destroy_site_rates(pllhip_site_posteriors_t ** rates)
+{
+  unsigned int k;
+  if (!rates) return;
+  for (k = 0; rates[k]; ++k) sc_destroy_one(rates[k]);
+  free(rates);
+}
+
+static pllhip_site_posteriors_t * sc_alloc_posteriors(size_t N, unsigned int R, int full)
+{
+  pllhip_site_posteriors_t * po = (pllhip_site_posteriors_t *)calloc(1, sizeof(*po));
+  if (!po) return NULL;
+  po->sites = (unsigned int)N;
+  po->cats = R;
+  po->rate = (double *)calloc(N ? N : 1, sizeof(double));
+  po->category = (unsigned char *)calloc(N ? N : 1, 1);
+  po->category_prob = (double *)calloc(N ? N : 1, sizeof(double));
+  po->invariant_prob = (double *)calloc(N ? N : 1, sizeof(double));
+  po->lnl = (double *)calloc(N ? N : 1, sizeof(double));
+  if (full) po->posterior = (double *)calloc(N ? N * R : 1, sizeof(double));
+  po->expected = (double *)calloc(R, sizeof(double));
+  if (po->rate && po->category && po->category_prob && po->invariant_prob && po->lnl && (!full || po->posterior) && po->expected)
+    return po;
+  sc_destroy_one(po);
+  return NULL;
+}
+
+static int sc_check_partition(const pll_partition_t * part, unsigned int p)
+{
+  if (part->rate_cats <= 256) return 1;
+  pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "partition %u: more than 256 categories do not fit the category array", p);
+  return 0;
+}
+
+/* the host table of partition `part` at the current root edge (vectors up to date); 0: out of memory */
+static int sc_host_root_table(pllhip_eval_t * ev, unsigned int p, double ** A, double ** B, unsigned int ** c)
+{
+  const pll_partition_t * part = ev->parts[p];
+  const pll_unode_t * e = ev->root;
+  const size_t cells = (size_t)part->sites * part->rate_cats;
+  *A = (double *)calloc(cells ? cells : 1, sizeof(double));
+  *B = (double *)calloc(cells ? cells : 1, sizeof(double));
+  *c = (unsigned int *)calloc(part->sites ? part->sites : 1, sizeof(unsigned int));
+  if (!*A || !*B || !*c)
+  {
+    free(*A); free(*B); free(*c);
+    pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the site-category table");
+    return 0;
+  }
+  sc_host_table(part, e->clv_index, e->scaler_index, e->back->clv_index, e->back->scaler_index, e->pmatrix_index,
+                ev->params[p], *A, *B, *c);
+  return 1;
+}
+
+pllhip_site_posteriors_t ** pllhip_eval_site_rates(pllhip_eval_t * ev, unsigned int flags)
+{
+  const int device = pllhip_sitecat_edge && pllhip_sitecat_posteriors && pllhip_sitecat_destroy;
+  const pll_unode_t * e;
+  pllhip_site_posteriors_t ** out;
+  unsigned int p, k = 0, local = 0;
+  pll_errno = 0;
+  if (flags & ~PLLHIP_SITECAT_POSTERIORS)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "unknown flags for the site rates");
+    return NULL;
+  }
+  for (p = 0; p < ev->nparts; ++p)
+    if (ev->parts[p])
+    {
+      if (!sc_check_partition(ev->parts[p], p)) return NULL;
+      ++local;
+    }
+  ev->last_was_full = 0;
+  if (!update_vectors(ev, 0))
+  {
+    if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "site rates: the traversal failed");
+    return NULL;
+  }
+  e = ev->root;
+  out = (pllhip_site_posteriors_t **)calloc((size_t)local + 1, sizeof(*out));
+  if (!out) goto nomem;
+  for (p = 0; p < ev->nparts; ++p)
+  {
+    pll_partition_t * part = ev->parts[p];
+    if (!part) continue;
+    if (device)
+    {
+      pllhip_sitecat_t * set = pllhip_sitecat_edge(part, e->clv_index, e->scaler_index, e->back->clv_index,
+                                                   e->back->scaler_index, e->pmatrix_index, ev->params[p]);
+      if (!set) goto fail;
+      out[k] = pllhip_sitecat_posteriors(set, NULL, flags);
+      pllhip_sitecat_destroy(set);
+      if (!out[k]) goto fail;
+    }
+    else
+    {
+      double * A, * B;
+      unsigned int * c;
+      out[k] = sc_alloc_posteriors(part->sites, part->rate_cats, (flags & PLLHIP_SITECAT_POSTERIORS) != 0);
+      if (!out[k]) goto nomem;
+      if (!sc_host_root_table(ev, p, &A, &B, &c)) goto fail;
+      out[k]->loglh = sc_host_posteriors(part->sites, part->rate_cats, A, B, c, part->pattern_weights, part->rate_weights,
+                                         part->rates, out[k], out[k]->expected);
+      free(A); free(B); free(c);
+    }
+    ++k;
+  }
+  return out;
+nomem:
+  pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the site rates");
+fail:
+  pllhip_eval_destroy_site_rates(out);
+  return NULL;
+}
+
+unsigned int pllhip_eval_rate_weights_trail(const pllhip_eval_t * ev, double * weights, double * loglh)
+{
+  if (weights && ev->em_evals) memcpy(weights, ev->em_trail_w, sizeof(double) * ev->em_evals * ev->em_cats);
+  if (loglh && ev->em_evals) memcpy(loglh, ev->em_trail_l, sizeof(double) * ev->em_evals);
+  return ev->em_evals;
+}
+
+double pllhip_eval_optimize_rate_weights(pllhip_eval_t * ev, unsigned int partition, double epsilon,
+                                         unsigned int max_iterations)
+{
+  const int device = pllhip_sitecat_edge && pllhip_sitecat_em_weights && pllhip_sitecat_destroy;
+  pll_partition_t * part;
+  const pll_unode_t * e;
+  double w[256], L = 0.0;
+  unsigned int R, r, its = 0;
+  pll_errno = 0;
+  ev->em_evals = 0;
+  if (partition >= ev->nparts || !ev->parts[partition])
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "rate weights: partition %u is not local", partition);
+    return NAN;
+  }
+  part = ev->parts[partition];
+  R = part->rate_cats;
+  if (!sc_check_partition(part, partition)) return NAN;
+  if (!(epsilon >= 0.0))
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "rate weights: epsilon is negative or not a number");
+    return NAN;
+  }
+  ev->last_was_full = 0;
+  if (!update_vectors(ev, 0))
+  {
+    if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "rate weights: the traversal failed");
+    return NAN;
+  }
+  e = ev->root;
+  ev->em_cats = R;
+  free(ev->em_trail_w);
+  ev->em_trail_w = (double *)calloc((size_t)PLLHIP_SITECAT_TRAIL_MAX * R, sizeof(double));
+  if (!ev->em_trail_w)
+  {
+    pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the weight trail");
+    return NAN;
+  }
+  if (device)
+  {
+    pllhip_sitecat_em_params_t prm;
+    int ok;
+    pllhip_sitecat_t * set = pllhip_sitecat_edge(part, e->clv_index, e->scaler_index, e->back->clv_index,
+                                                 e->back->scaler_index, e->pmatrix_index, ev->params[partition]);
+    if (!set) return NAN;
+    prm.start = NULL;
+    prm.epsilon = epsilon;
+    prm.max_iterations = max_iterations;
+    ok = pllhip_sitecat_em_weights(set, &prm, w, &L, &its, ev->em_trail_w, ev->em_trail_l);
+    pllhip_sitecat_destroy(set);
+    if (!ok) return NAN;
+  }
+  else
+  {
+    double * A, * B, expected[256], Lprev = 0.0, msum = 0.0, esum;
+    unsigned int * c;
+    size_t n;
+    if (part->attributes & PLL_ATTRIB_AB_MASK)
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "rate weights: the partition has an ascertainment-bias correction, which depends on the weights");
+      return NAN;
+    }
+    for (n = 0; n < part->sites; ++n) msum += (double)part->pattern_weights[n];
+    for (r = 0; r < R; ++r) w[r] = part->rate_weights[r];
+    if (!(msum > 0.0))
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "rate weights: the pattern weights add up to 0");
+      return NAN;
+    }
+    if (!sc_host_root_table(ev, partition, &A, &B, &c)) return NAN;
+    for (its = 0;; ++its)
+    {
+      L = sc_host_posteriors(part->sites, R, A, B, c, part->pattern_weights, w, part->rates, NULL, expected);
+      if (its < PLLHIP_SITECAT_TRAIL_MAX)
+      {
+        memcpy(ev->em_trail_w + (size_t)its * R, w, sizeof(double) * R);
+        ev->em_trail_l[its] = L;
+      }
+      if (!(L > -INFINITY))
+      {
+        for (n = 0; n < part->sites; ++n)
+        {
+          double T = 0.0;
+          for (r = 0; r < R; ++r) T += w[r] * (A[n * R + r] + B[n * R + r]);
+          if (part->pattern_weights[n] && !(T > 0.0)) break;
+        }
+        free(A); free(B); free(c);
+        pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "rate weights: site %zu has a pattern weight and likelihood 0 under the weights of iteration %u", n, its);
+        return NAN;
+      }
+      if ((its > 0 && L - Lprev < epsilon) || its == max_iterations) break;
+      /* (sum_r expected[r] is sum_n m_n up to rounding; as the divisor it makes the new weights add up to 1 to R roundings) */
+      for (r = 0, esum = 0.0; r < R; ++r) esum += expected[r];
+      for (r = 0; r < R; ++r) w[r] = expected[r] / esum;
+      Lprev = L;
+    }
+    free(A); free(B); free(c);
+  }
+  ev->em_evals = (its + 1 < PLLHIP_SITECAT_TRAIL_MAX) ? its + 1 : PLLHIP_SITECAT_TRAIL_MAX;
+  pll_set_category_weights(part, w);
+  /* (the vectors are per category and do not depend on the weights: the edge log-likelihood alone is new) */
+  return pllhip_eval_loglh(ev, 1);
 }
 
 /* ---------------------------------------------------------------------- */

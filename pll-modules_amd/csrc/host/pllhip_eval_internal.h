@@ -38,6 +38,9 @@ struct pllhip_eval
   int * nr_converged;
   int transient;                  /* PLLHIP_EVAL_TRANSIENT_*: which full evaluations run evaluate-only */
   int last_was_full;              /* the previous call into the driver was a full evaluation */
+  double * em_trail_w;            /* [64][em_cats]: the weights the last pllhip_eval_optimize_rate_weights evaluated ... */
+  double em_trail_l[64];          /* ... and the log-likelihood of the partition at them */
+  unsigned int em_evals, em_cats;
 };
 
 #define PLLHIP_EVAL_MAX_TRIALS 8

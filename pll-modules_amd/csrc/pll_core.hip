@@ -28,6 +28,7 @@
 #include "kernels_repeats.hpp"
 #include "kernels_newton_s4.hpp"
 #include "kernels_ancestral.hpp"
+#include "kernels_sitecat.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -3921,6 +3922,78 @@ bool matrix_tables(pll_partition_t * p, MatrixTables & out)
   out.off_pinv = (unsigned)e->off_pinv;
   out.off_freqs = (unsigned)e->off_freqs;
   return true;
+}
+
+static int sitecat_allow_lds()
+{
+#define PLLHIP_ATTR(KK) \
+  PLLHIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sitecat_s16<KK>), hipFuncAttributeMaxDynamicSharedMemorySize, S16_MAX_LDS_BYTES))
+  PLLHIP_ATTR(5); PLLHIP_ATTR(6); PLLHIP_ATTR(7); PLLHIP_ATTR(8);
+#undef PLLHIP_ATTR
+  return PLL_SUCCESS;
+}
+
+// device_job.hpp: the operand set-up of an edge reader (as anc_stage_add and loglikelihood_impl make it), then the
+// family's table kernel on the engine's stream; nothing is waited for
+bool sitecat_edge_table(pll_partition_t * p, unsigned parent_clv, int parent_scaler, unsigned child_clv, int child_scaler,
+                        unsigned matrix_index, const unsigned * freqs_indices, const SiteCatPlanes & planes)
+{
+  Engine * e = engine_of(p);
+  if (!hip_ok(hipSetDevice(e->device), "hipSetDevice")) return false;
+  if (!check_clv_index(e, parent_clv, "parent") || !check_clv_index(e, child_clv, "child") ||
+      !check_scaler_index(e, parent_scaler) || !check_scaler_index(e, child_scaler)) return false;
+  if (matrix_index >= e->nmat)
+  {
+    set_error(PLL_ERROR_PARAM_INVALID, "matrix index out of range");
+    return false;
+  }
+  if (!sync_model(p) || !flush_pmatrices(p) || !ensure_luts(p) || !ensure_invariant(p)) return false;
+  const unsigned N = e->Nreal;
+  if (!N) return true;
+  if (!need_clv(e, parent_clv) || !need_clv(e, child_clv) || !need_scaler(e, parent_scaler) ||
+      !need_scaler(e, child_scaler)) return false;
+  const ModelView mv = model_view(e);
+  const ParamIdx fidx = make_params(p, freqs_indices);
+  const NodeRef parent = node_ref(e, parent_clv), child = node_ref(e, child_clv);
+  const double * pm = e->d_pmat + (size_t)matrix_index * e->R * e->S * e->Sp;
+  const double * lut = child.codes ? e->d_lut + (size_t)matrix_index * e->R * e->lut_codes * e->S : nullptr;
+  SiteCatSide sd;
+  sd.ps = scaler_ptr(e, parent_scaler);
+  sd.cs = scaler_ptr(e, child_scaler);
+  sd.invariant = planes.B ? e->d_invariant : nullptr;
+  sd.rate_scalers = e->rate_scalers ? 1u : 0u;
+  SiteCatOut out;
+  out.A = planes.A; out.B = planes.B; out.c = planes.c; out.plane = planes.plane;
+  if (e->family == KernelFamily::S20 || e->family == KernelFamily::S16)
+  {
+    const unsigned nblk = (N + S20_BS - 1) / S20_BS;
+    const unsigned grid = capped_grid("PLLHIP_SITECAT_BLOCKS", std::min((nblk + 3) / 4, e->cu_count * 8));
+    if (e->family == KernelFamily::S20)
+      hipLaunchKernelGGL(k_sitecat_s20, dim3(grid), dim3(256), sizeof(double) * e->R * s16_fr(5), e->stream,
+                         mv, fidx, parent, child, pm, lut, e->lut_codes, e->d_tipmap, sd, N, nblk, e->R, out);
+    else
+    {
+      if (sizeof(double) * e->R * s16_frags(e) > 64 * 1024 && !sitecat_allow_lds()) return false;
+#define PLLHIP_CALL(KK) \
+      hipLaunchKernelGGL(k_sitecat_s16<KK>, dim3(grid), dim3(256), sizeof(double) * e->R * s16_fr(KK), e->stream, \
+                         mv, fidx, parent, child, pm, lut, e->lut_codes, e->d_tipmap, sd, N, nblk, e->R, out)
+      PLLHIP_DISPATCH_KS(s16_ks(e), PLLHIP_CALL);
+#undef PLLHIP_CALL
+    }
+  }
+  else
+  {
+    // one thread per site; 4 states: per (site, rate)
+    const size_t items = e->family == KernelFamily::S4 ? (size_t)N * e->R : N;
+    const unsigned gx = capped_grid("PLLHIP_SITECAT_BLOCKS", grid_for(items, 256));
+    if (e->family == KernelFamily::S4)
+      hipLaunchKernelGGL(k_sitecat_s4, dim3(gx), dim3(256), 0, e->stream,
+                         mv, fidx, parent, child, pm, lut, e->lut_codes, e->d_tipmap, sd, N, e->R, out);
+    else
+      hipLaunchKernelGGL(k_sitecat_generic, dim3(gx), dim3(256), 0, e->stream,
+                         mv, fidx, parent, child, pm, lut, e->lut_codes, e->d_tipmap, e->rows, sd, N, e->R, out);
+  }
+  return hip_ok(hipGetLastError(), "site-category table kernel");
 }
 
 } // namespace pllhip

@@ -176,7 +176,9 @@ pllhip_eval_set_branch_length pllhip_eval_optimize_branches pllhip_eval_ops
 pllhip_eval_pmatrix_updates pllhip_eval_derivative_calls pllhip_eval_spr_round
 pllhip_eval_set_fused pllhip_eval_newton_iterations pllhip_eval_set_brlen_linkage
 pllhip_eval_set_brlen_scaler pllhip_eval_get_brlen_scaler pllhip_eval_get_partition_branch_length
-pllhip_eval_set_partition_branch_length pllhip_eval_set_transient""".split()
+pllhip_eval_set_partition_branch_length pllhip_eval_set_transient
+pllhip_eval_site_rates pllhip_eval_destroy_site_rates pllhip_eval_optimize_rate_weights
+pllhip_eval_rate_weights_trail""".split()
 
 PLLHIP_H_FUNCTIONS = """pllhip_device_count pllhip_set_device pllhip_get_device
 pllhip_device_arch pllhip_eigen_decompose pllhip_sync_to_host pllhip_sync_to_device pllhip_get_clv
@@ -207,7 +209,10 @@ pllhip_sitelh_au pllhip_au_destroy pllhip_au_last_times pllhip_multiscale_weight
 pllhip_distances_partition pllhip_distances_msa pllhip_distmat_from_host pllhip_distmat_destroy pllhip_distmat_size
 pllhip_distmat_get pllhip_distmat_compared pllhip_distmat_counts pllhip_distmat_no_overlap pllhip_distmat_nj
 pllhip_distmat_nj_joins pllhip_distances_last_times
-pllhip_simulate_edges pllhip_simulate_utree pllhip_simulate_last_times""".split()
+pllhip_simulate_edges pllhip_simulate_utree pllhip_simulate_last_times
+pllhip_sitecat_edge pllhip_sitecat_from_table pllhip_sitecat_destroy pllhip_sitecat_sites pllhip_sitecat_categories
+pllhip_sitecat_table pllhip_sitecat_posteriors pllhip_site_posteriors_destroy pllhip_sitecat_em_weights
+pllhip_sitecat_last_times""".split()
 
 
 def _u32(a):
@@ -255,6 +260,46 @@ class Ancestral:
     def rows(self, i, k, states):
         a, b = self.prob_offset[k], self.prob_offset[k + 1]
         return self.probs[i, a:b].reshape(-1, states)
+
+
+PLLHIP_SITECAT_POSTERIORS = 1
+SITECAT_TRAIL_MAX = 64
+
+
+class SitePosteriorsResult(C.Structure):
+    """pllhip_site_posteriors_t (include/pllhip.h)"""
+    _fields_ = [("sites", C.c_uint), ("cats", C.c_uint), ("rate", c_double_p), ("category", C.POINTER(C.c_ubyte)),
+                ("category_prob", c_double_p), ("invariant_prob", c_double_p), ("lnl", c_double_p),
+                ("posterior", c_double_p), ("expected", c_double_p), ("loglh", C.c_double)]
+
+
+class SiteCatEmParams(C.Structure):
+    """pllhip_sitecat_em_params_t"""
+    _fields_ = [("start", c_double_p), ("epsilon", C.c_double), ("max_iterations", C.c_uint)]
+
+
+class SitePosteriors:
+    """numpy copy of a pllhip_site_posteriors_t: rate, category (uint8), category_prob, invariant_prob, lnl [sites]
+    (rate / invariant_prob None for a set made from a host table), posterior [sites][cats] or None, expected [cats],
+    loglh"""
+
+    def __init__(self, res):
+        n, r = res.sites, res.cats
+
+        def take(ptr, shape, dtype=np.float64):
+            return np.ctypeslib.as_array(ptr, shape=shape).astype(dtype, copy=True) if ptr and n else \
+                (np.zeros(shape, dtype=dtype) if ptr else None)
+        self.sites, self.cats, self.loglh = n, r, res.loglh
+        self.rate, self.invariant_prob = take(res.rate, (n,)), take(res.invariant_prob, (n,))
+        self.category = take(res.category, (n,), np.uint8)
+        self.category_prob, self.lnl = take(res.category_prob, (n,)), take(res.lnl, (n,))
+        self.posterior = take(res.posterior, (n, r))
+        self.expected = np.ctypeslib.as_array(res.expected, shape=(r,)).copy()
+
+
+class EmFit:
+    """outcome of an EM fit of the category weights: weights [cats], loglh, iterations (updates made), and the trail:
+    trail_weights [evaluations][cats], trail_loglh [evaluations] (the first 64)"""
 
 
 PLLHIP_RELL_REPLICATES = 1
@@ -447,6 +492,15 @@ class PllLib:
                 L.pllhip_eval_compute_ancestral.argtypes = [C.c_void_p, C.c_uint]
                 L.pllhip_eval_destroy_ancestral.restype = None
                 L.pllhip_eval_destroy_ancestral.argtypes = [C.POINTER(AncestralResult)]
+            if hasattr(L, "pllhip_eval_site_rates"):
+                L.pllhip_eval_site_rates.restype = C.POINTER(C.POINTER(SitePosteriorsResult))
+                L.pllhip_eval_site_rates.argtypes = [C.c_void_p, C.c_uint]
+                L.pllhip_eval_destroy_site_rates.restype = None
+                L.pllhip_eval_destroy_site_rates.argtypes = [C.POINTER(C.POINTER(SitePosteriorsResult))]
+                L.pllhip_eval_optimize_rate_weights.restype = C.c_double
+                L.pllhip_eval_optimize_rate_weights.argtypes = [C.c_void_p, C.c_uint, C.c_double, C.c_uint]
+                L.pllhip_eval_rate_weights_trail.restype = C.c_uint
+                L.pllhip_eval_rate_weights_trail.argtypes = [C.c_void_p, c_double_p, c_double_p]
             for fn in ("pllhip_eval_ops", "pllhip_eval_pmatrix_updates", "pllhip_eval_derivative_calls",
                        "pllhip_eval_newton_iterations"):
                 getattr(L, fn).restype = C.c_ulong
@@ -519,6 +573,27 @@ class PllLib:
             L.pllhip_node_ancestral_finish.argtypes = [C.c_void_p]
             L.pllhip_node_ancestral_last_times.restype = None
             L.pllhip_node_ancestral_last_times.argtypes = [c_double_p, C.POINTER(C.c_ulonglong)]
+        if hasattr(L, "pllhip_sitecat_edge"):
+            sp = C.POINTER(SitePosteriorsResult)
+            L.pllhip_sitecat_edge.restype = C.c_void_p
+            L.pllhip_sitecat_edge.argtypes = [pp, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p]
+            L.pllhip_sitecat_from_table.restype = C.c_void_p
+            L.pllhip_sitecat_from_table.argtypes = [C.c_uint, C.c_uint, c_double_p, c_uint_p, c_double_p]
+            L.pllhip_sitecat_destroy.restype = None
+            L.pllhip_sitecat_destroy.argtypes = [C.c_void_p]
+            L.pllhip_sitecat_sites.restype = C.c_uint
+            L.pllhip_sitecat_sites.argtypes = [C.c_void_p]
+            L.pllhip_sitecat_categories.restype = C.c_uint
+            L.pllhip_sitecat_categories.argtypes = [C.c_void_p]
+            L.pllhip_sitecat_table.argtypes = [C.c_void_p, c_double_p, c_double_p, c_uint_p]
+            L.pllhip_sitecat_posteriors.restype = sp
+            L.pllhip_sitecat_posteriors.argtypes = [C.c_void_p, c_double_p, C.c_uint]
+            L.pllhip_site_posteriors_destroy.restype = None
+            L.pllhip_site_posteriors_destroy.argtypes = [sp]
+            L.pllhip_sitecat_em_weights.argtypes = [C.c_void_p, C.POINTER(SiteCatEmParams), c_double_p, c_double_p,
+                                                    c_uint_p, c_double_p, c_double_p]
+            L.pllhip_sitecat_last_times.restype = None
+            L.pllhip_sitecat_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
         if hasattr(L, "pllhip_sitelh_rell"):
             L.pllhip_sitelh_create.restype = C.c_void_p
             L.pllhip_sitelh_create.argtypes = [C.c_uint, c_uint_p]
@@ -1580,6 +1655,85 @@ class SiteLikelihoods:
         return out
 
 
+class SiteCat:
+    """a pllhip_sitecat_t: SiteCat.edge(inst, parent, parent_scaler, child, child_scaler, matrix) or
+    SiteCat.from_table(lib, g, pattern_weights=None, weights=None); raises RuntimeError with the library's message"""
+
+    def __init__(self, lib, handle):
+        if not handle:
+            raise RuntimeError(f"[{lib.errno}] {lib.errmsg}")
+        self.lib, self.L, self.h = lib, lib.lib, handle
+        self.sites, self.cats = self.L.pllhip_sitecat_sites(handle), self.L.pllhip_sitecat_categories(handle)
+
+    @classmethod
+    def edge(cls, inst, pc_, psc, cc, csc, matrix, params=None):
+        inst.lib.errno = 0
+        prm = inst.params_p if params is None else _u32(params).ctypes.data_as(c_uint_p)
+        return cls(inst.lib, inst.L.pllhip_sitecat_edge(inst.p, pc_, psc, cc, csc, matrix, prm))
+
+    @classmethod
+    def from_table(cls, lib, g, pattern_weights=None, weights=None):
+        g = _f64(g)
+        m = _u32(pattern_weights) if pattern_weights is not None else None
+        w = _f64(weights) if weights is not None else None
+        lib.errno = 0
+        return cls(lib, lib.lib.pllhip_sitecat_from_table(g.shape[0], g.shape[1], g.ctypes.data_as(c_double_p),
+                                                          m.ctypes.data_as(c_uint_p) if m is not None else None,
+                                                          w.ctypes.data_as(c_double_p) if w is not None else None))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.h:
+            self.L.pllhip_sitecat_destroy(self.h)
+            self.h = None
+
+    def table(self):
+        """(rate_part [sites][cats], inv_part [sites][cats], counts [sites])"""
+        a, b = np.zeros((self.sites, self.cats)), np.zeros((self.sites, self.cats))
+        c = np.zeros(self.sites, dtype=np.uint32)
+        if not self.L.pllhip_sitecat_table(self.h, a.ctypes.data_as(c_double_p), b.ctypes.data_as(c_double_p),
+                                           c.ctypes.data_as(c_uint_p)):
+            raise RuntimeError(self.lib.errmsg)
+        return a, b, c
+
+    def posteriors(self, weights=None, flags=0):
+        w = _f64(weights) if weights is not None else None
+        self.lib.errno = 0
+        ptr = self.L.pllhip_sitecat_posteriors(self.h, w.ctypes.data_as(c_double_p) if w is not None else None, flags)
+        if not ptr:
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        try:
+            return SitePosteriors(ptr.contents)
+        finally:
+            self.L.pllhip_site_posteriors_destroy(ptr)
+
+    def em_weights(self, epsilon, max_iterations, start=None):
+        s = _f64(start) if start is not None else None
+        prm = SiteCatEmParams(s.ctypes.data_as(c_double_p) if s is not None else None, epsilon, max_iterations)
+        w, tw, tl = np.zeros(self.cats), np.zeros((SITECAT_TRAIL_MAX, self.cats)), np.zeros(SITECAT_TRAIL_MAX)
+        ll, its = C.c_double(0.0), C.c_uint(0)
+        self.lib.errno = 0
+        if not self.L.pllhip_sitecat_em_weights(self.h, C.byref(prm), w.ctypes.data_as(c_double_p), C.byref(ll),
+                                                C.byref(its), tw.ctypes.data_as(c_double_p),
+                                                tl.ctypes.data_as(c_double_p)):
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        fit, n = EmFit(), min(its.value + 1, SITECAT_TRAIL_MAX)
+        fit.weights, fit.loglh, fit.iterations = w, ll.value, its.value
+        fit.trail_weights, fit.trail_loglh = tw[:n].copy(), tl[:n].copy()
+        return fit
+
+    def last_times(self):
+        """(table_ms, posterior_ms, em_ms) of this thread's last calls"""
+        t = [C.c_double(0.0) for _ in range(3)]
+        self.L.pllhip_sitecat_last_times(*[C.byref(x) for x in t])
+        return tuple(x.value for x in t)
+
+
 class DistMat:
     """pllhip_distmat_t (include/pllhip.h): made by distances_partition / distances_msa / distmat_from_host below.
     A failed call returns None / False with lib.errno set."""
@@ -1934,6 +2088,37 @@ class Evaluation:
             return out
         finally:
             self.L.pllhip_eval_destroy_ancestral(ptr)
+
+    def site_rates(self, flags=0):
+        """pllhip_eval_site_rates -> [SitePosteriors per local partition] (numpy copies)"""
+        self.lib.errno = 0
+        arr = self.L.pllhip_eval_site_rates(self.ev, flags)
+        if not arr:
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        try:
+            out, k = [], 0
+            while arr[k]:
+                out.append(SitePosteriors(arr[k].contents))
+                k += 1
+            return out
+        finally:
+            self.L.pllhip_eval_destroy_site_rates(arr)
+
+    def optimize_rate_weights(self, partition=0, epsilon=1e-3, max_iterations=100):
+        """pllhip_eval_optimize_rate_weights -> (lnL of the driver afterwards, EmFit of the trail)"""
+        self.lib.errno = 0
+        v = self.L.pllhip_eval_optimize_rate_weights(self.ev, partition, epsilon, max_iterations)
+        if v != v:
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        cats = self.parts[partition].R
+        tw, tl = np.zeros((SITECAT_TRAIL_MAX, cats)), np.zeros(SITECAT_TRAIL_MAX)
+        n = self.L.pllhip_eval_rate_weights_trail(self.ev, tw.ctypes.data_as(c_double_p), tl.ctypes.data_as(c_double_p))
+        fit = EmFit()
+        fit.trail_weights, fit.trail_loglh = tw[:n].copy(), tl[:n].copy()
+        p = self.parts[partition].p.contents
+        fit.weights = np.array([p.rate_weights[r] for r in range(cats)])
+        fit.loglh, fit.iterations = (tl[n - 1] if n else float("nan")), n - 1
+        return v, fit
 
     def optimize_branches(self, bl_min=1e-4, bl_max=10.0, eps=0.01, iters=8, radius=-1):
         self.lib.errno = 0
