@@ -713,6 +713,57 @@ PLL_EXPORT int pllhip_sitecat_em_weights(pllhip_sitecat_t * set, const pllhip_si
    reduction kernels) and of the last EM fit (all its iterations, host waits included) in ms */
 PLL_EXPORT void pllhip_sitecat_last_times(double * table_ms, double * posterior_ms, double * em_ms);
 
+/* ---- substitution mapping: posterior expectations per branch ("Substitution mapping"; DESIGN.md
+ * section 31) ----
+ * Given the data, the expected joint states at the two ends of an edge (endpoint pairs); from them, on the host
+ * (pllhip_substmap_counts, include/pllhip_eval.h), the expected number of a -> b substitutions along the edge and the
+ * expected time spent in each state.  Notation of the site-category block above: A[n][r], B[n][r], c[n] and
+ * T[n] = sum_r w_r (A + B) are the site-category table of the same edge, q_r and pi_r those of freqs_indices[r], m_n
+ * the pattern weights.  For site n, category r, parent-side state i and child-side state j:
+ *     s[n][r]       = w_r (1 - q_r) d[n][r] / T[n]     d: the descaling the table applied to l[n][r] -- the rate factor
+ *                                                      and, for a site with an invariant term and c > 0, 2^(-256 c) or
+ *                                                      0; s = 0 where T[n] = 0
+ *     J[n][r][i][j] = s[n][r] pi_r[i] parent[n,r,i] P_r[i][j] child[n,r,j]
+ *                     so that sum_ij J[n][r] = post[n][r] = w_r A[n][r] / T[n] up to rounding
+ *     F[r][i][j]    = sum_n m_n s[n][r] pi_r[i] parent[n,r,i] child[n,r,j]      (no P: nothing is ever divided by P)
+ *     pairs[r][i][j] = F[r][i][j] P_r[i][j]                                     (= sum_n m_n J)
+ *     posterior[r]  = sum_ij pairs[r][i][j]
+ *     differ[n]     = sum_r sum_(i != j) J[n][r][i][j]
+ * differ is summed over the off-diagonal entries themselves (the table of the edge under matrices with a zeroed
+ * diagonal), never as 1 - same, which cancels on short branches.  A coded parent contributes parent[n,r,i] = bit i of
+ * tipmap[code], a coded child child[n,r,j] = bit j of its mask.  A site with T[n] = 0 adds nothing and has differ = 0;
+ * `dropped` counts such sites with m_n > 0.  The invariant component contributes to neither table.  With an
+ * ascertainment-bias correction the expectations are those of the OBSERVED sites: nothing is corrected.
+ * The call accepts the partitions pllhip_sitecat_edge accepts (not one spread over devices: PLL_ERROR_PARAM_INVALID),
+ * changes nothing in the partition (vectors that exist as their operation only are stored, as for any reader), and
+ * waits once.  F is summed without floating-point atomics: bit-identical from run to run at a given grid.
+ * PLLHIP_SUBSTMAP_BLOCKS (environment, read at the call; unset or 0: no cap) caps the workgroups of the scale kernel
+ * and of the pair kernel, whose grid decides the order in which F is summed; differ does not depend on it.  The two
+ * table launches of the scale pass obey PLLHIP_SITECAT_BLOCKS, as in pllhip_sitecat_edge (per-site values: no effect
+ * on the results); the launches over the matrices and the reduction have fixed grids. */
+#define PLLHIP_SUBST_SITES (1u << 0)       /* also differ[sites] */
+typedef struct pllhip_edge_pairs
+{
+  unsigned int states, cats, sites;
+  double * F;                    /* [cats][states][states] */
+  double * pairs;                /* [cats][states][states] */
+  double * posterior;            /* [cats]: sum_ij pairs[r] */
+  double * differ;               /* [sites]; NULL without PLLHIP_SUBST_SITES */
+  double weight_sum;             /* sum_n m_n */
+  unsigned long long dropped;    /* sites with m_n > 0 and T = 0 */
+} pllhip_edge_pairs_t;
+
+/* arguments as for pll_compute_edge_loglikelihood; NULL on error: NULL arguments, an index out of range, unknown flags,
+   a partition spread over devices */
+PLL_EXPORT pllhip_edge_pairs_t * pllhip_substmap_edge(pll_partition_t * partition, unsigned int parent_clv_index,
+                                                      int parent_scaler_index, unsigned int child_clv_index,
+                                                      int child_scaler_index, unsigned int matrix_index,
+                                                      const unsigned int * freqs_indices, unsigned int flags);
+PLL_EXPORT void pllhip_edge_pairs_destroy(pllhip_edge_pairs_t * pairs);
+/* this thread's last call: device time of the scale pass (both tables and the scale kernel), of the pair kernel and of
+   the reduction in ms between HIP events */
+PLL_EXPORT void pllhip_substmap_last_times(double * scale_ms, double * pairs_ms, double * reduce_ms);
+
 /* ---- simulated alignments: the parametric bootstrap ("Simulated alignments") ----
  * Replicates of an alignment drawn from the partition's own model -- rate categories and their weights, p-inv and
  * frequencies of params_indices[category], and the transition matrices as pll_update_prob_matrices left them -- along

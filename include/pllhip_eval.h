@@ -279,6 +279,57 @@ PLL_EXPORT double pllhip_eval_optimize_rate_weights(pllhip_eval_t * ev, unsigned
                                                     unsigned int max_iterations);
 PLL_EXPORT unsigned int pllhip_eval_rate_weights_trail(const pllhip_eval_t * ev, double * weights, double * loglh);
 
+/* ---------------------------------------------------------------------------
+ * Substitution mapping (include/pllhip.h, "substitution mapping"): per branch and given the data, the expected joint
+ * states at its two ends, the expected number of a -> b substitutions along it and the expected time spent in each
+ * state -- what Bio++ mapnh and HyPhy call substitution mapping, PAML's changes per branch, and the E-step of
+ * Holmes-Rubin EM for a rate matrix (counts[a][b] / dwell[a] is the update of q_ab).
+ *
+ * pllhip_substmap_counts is the host stage for ONE category: pure C, no device.  From F_r [states][states] (row-major,
+ * not padded; pairs = F o P) and the eigen system in libpll's storage, P = inv_eigenvecs diag(exp(lambda tau)) eigenvecs
+ * (V = inv_eigenvecs, V^-1 = eigenvecs, both [states][states_padded]; tau_r = rates[r] t / (1 - q_r)):
+ *     K[k][l] = tau e^(lambda_l tau) phi((lambda_k - lambda_l) tau),  phi(x) = expm1(x) / x, phi(0) = 1   (symmetric)
+ *     G = V^T F V^-T,   M = V^-T (G o K) V^T
+ *     counts[a][b] = q_ab M[a][b]  (a != b, q = V Lambda V^-1),  counts[a][a] = 0,   dwell[a] = M[a][a]
+ * dwell is rate-scaled time: sum_a dwell[a] = tau posterior[r].  tau = 0 gives all zeros.  Reversible models only (real
+ * eigenvalues).
+ *
+ * pllhip_eval_substitution_map evaluates incrementally, then visits every branch once by the re-rooting walk of
+ * pllhip_eval_optimize_branches and returns, for every local partition and every branch (by pmatrix_index), the record
+ * below: counts and dwell summed over the categories (the invariant component contributes to neither), total =
+ * sum_ab counts, posterior_weight = sum_r sum_ij pairs (sum_n m_n less the invariant share), flags: PLLHIP_SUBST_SITES
+ * for differ[sites].  tau comes from the driver's own branch length and linkage mode.  The root, the branch lengths,
+ * the vectors and the log-likelihood are afterwards what they were.  On the HIP engine the pair tables come from
+ * pllhip_substmap_edge; where the library has no such call (the CPU oracle) the driver computes them on the host from
+ * the partition's own arrays.  NULL on error: unknown flags, no local partition.
+ * ------------------------------------------------------------------------- */
+PLL_EXPORT int pllhip_substmap_counts(unsigned int states, unsigned int states_padded, const double * eigenvecs,
+                                      const double * inv_eigenvecs, const double * eigenvals, double tau,
+                                      const double * F, double * counts, double * dwell);
+
+typedef struct pllhip_branch_subst
+{
+  pll_unode_t * node;            /* orientation: i on node's side, j on node->back's side */
+  double * pairs;                /* [cats][states][states] */
+  double * counts;               /* [states][states] */
+  double * dwell;                /* [states] */
+  double * differ;               /* [sites]; NULL without PLLHIP_SUBST_SITES */
+  double total, posterior_weight;
+  unsigned long long dropped;    /* sites with m_n > 0 and likelihood 0 */
+  unsigned int states, cats, sites;
+} pllhip_branch_subst_t;
+
+typedef struct pllhip_substitution_map
+{
+  unsigned int partition_count;          /* local partitions */
+  unsigned int branch_count;
+  unsigned int * partition_indices;      /* [partition_count] */
+  pllhip_branch_subst_t ** branches;     /* [partition_count][branch_count], by pmatrix_index */
+} pllhip_substitution_map_t;
+
+PLL_EXPORT pllhip_substitution_map_t * pllhip_eval_substitution_map(pllhip_eval_t * ev, unsigned int flags);
+PLL_EXPORT void pllhip_eval_destroy_substitution_map(pllhip_substitution_map_t * map);
+
 PLL_EXPORT unsigned long pllhip_eval_ops(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_pmatrix_updates(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_derivative_calls(const pllhip_eval_t * ev);   /* sumtable scans */

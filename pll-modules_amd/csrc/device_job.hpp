@@ -6,6 +6,7 @@
 #include "engine.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <vector>
 
@@ -110,6 +111,60 @@ struct SiteCatPlanes
 };
 bool sitecat_edge_table(pll_partition_t * p, unsigned parent_clv, int parent_scaler, unsigned child_clv, int child_scaler,
                         unsigned matrix_index, const unsigned * freqs_indices, const SiteCatPlanes & planes);
+
+// the endpoint-pair table of an edge (kernels_substmap.hpp) in three steps, each enqueued on the engine's stream and
+// none waited for, so that the caller can put events between them; the partition must not be a router (pll_core.hip).
+// substmap_shape: what the caller has to allocate for this partition.  substmap_scale: the operand set-up of
+// sitecat_edge_table, the table of the edge (and, for `differ`, the table under the matrices with a zeroed diagonal,
+// which needs pm0 and lut0), then scale, differ and dropped.  substmap_pairs: the family's pair kernel into `partial`.
+// substmap_reduce: F and pairs.  All buffers are the caller's, on the partition's device.
+struct SubstmapShape
+{
+  size_t plane = 0;           // doubles per rate of the table planes (even)
+  size_t splane = 0;          // doubles per rate of the scale plane (whole 32-site blocks)
+  unsigned grid = 0;          // workgroups of the pair kernel = partial tiles per rate
+  size_t pm_cells = 0;        // doubles of a matrix set [R][S][Sp]
+  size_t lut_cells = 0;       // doubles of a lookup-table set [R][codes][S] (0: no coded tips)
+  bool pinv = false;          // some category has an invariant part: the table has a B plane
+};
+struct SubstmapBuffers
+{
+  double * A = nullptr, * B = nullptr, * A0 = nullptr;       // [R][plane]; B, A0 may be null
+  unsigned * c = nullptr;                                    // [N]
+  unsigned * m = nullptr;                                    // [N] pattern weights
+  double * scale = nullptr;                                  // [R][splane]
+  double * differ = nullptr;                                 // [N] or null
+  unsigned long long * dropped = nullptr;                    // 1, zeroed by substmap_scale
+  double * pm0 = nullptr, * lut0 = nullptr;                  // with differ only
+  double * partial = nullptr;                                // [grid][R][S][S]
+  double * F = nullptr, * pairs = nullptr;                   // [R][S][S]
+};
+bool substmap_shape(pll_partition_t * p, const unsigned * freqs_indices, SubstmapShape & shape);
+bool substmap_scale(pll_partition_t * p, unsigned parent_clv, int parent_scaler, unsigned child_clv, int child_scaler,
+                    unsigned matrix_index, const unsigned * freqs_indices, const SubstmapShape & shape,
+                    const SubstmapBuffers & buf);
+bool substmap_pairs(pll_partition_t * p, unsigned parent_clv, unsigned child_clv, const SubstmapShape & shape,
+                    const SubstmapBuffers & buf);
+bool substmap_reduce(pll_partition_t * p, unsigned matrix_index, const unsigned * freqs_indices,
+                     const SubstmapShape & shape, const SubstmapBuffers & buf);
+
+// category weights a site-category or pair table can be made under: finite, non-negative, not all zero
+inline bool check_category_weights(const double * w, unsigned R, const char * who)
+{
+  double sum = 0.0;
+  for (unsigned r = 0; r < R; ++r)
+  {
+    if (!(w[r] >= 0.0) || !std::isfinite(w[r]))
+    {
+      set_error(PLL_ERROR_PARAM_INVALID, "%s: weight %u is negative or not finite", who, r);
+      return false;
+    }
+    sum += w[r];
+  }
+  if (sum > 0.0) return true;
+  set_error(PLL_ERROR_PARAM_INVALID, "%s: the weights add up to 0", who);
+  return false;
+}
 
 inline unsigned grid_for(size_t items, unsigned per_block)
 {

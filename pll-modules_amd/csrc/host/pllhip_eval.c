@@ -19,6 +19,8 @@
 #pragma weak pllhip_sitecat_posteriors
 #pragma weak pllhip_sitecat_em_weights
 #pragma weak pllhip_sitecat_destroy
+#pragma weak pllhip_substmap_edge         /* HIP engine only: with the CPU oracle the driver computes the pair table itself */
+#pragma weak pllhip_edge_pairs_destroy
 #include <stdarg.h>
 
 static __thread pllhip_eval_t * cb_self;   /* pll_utree_traverse callbacks carry no user pointer */
@@ -733,8 +735,9 @@ static unsigned int sc_count(const pll_partition_t * p, int ps, int cs, size_t x
 
 /* The definitions of include/pllhip.h in plain C from the partition's host arrays: A, B [sites][cats], c [sites].
    The second implementation of the table kernels (kernels_sitecat.hpp), for libraries that keep host arrays. */
-static void sc_host_table(const pll_partition_t * p, unsigned int pc, int ps, unsigned int cc, int cs, unsigned int m,
-                          const unsigned int * fi, double * A, double * B, unsigned int * c)
+/* ... and, where D is not NULL, D[n][r] = (1 - q_r) d[n][r]: what the table did to l = 1 (the substitution map's scale) */
+static void sc_host_table_scaled(const pll_partition_t * p, unsigned int pc, int ps, unsigned int cc, int cs, unsigned int m,
+                                 const unsigned int * fi, double * A, double * B, unsigned int * c, double * D)
 {
   const unsigned int S = p->states, Sp = p->states_padded, R = p->rate_cats;
   const int per_rate = (p->attributes & PLL_ATTRIB_RATE_SCALERS) != 0;
@@ -756,7 +759,7 @@ static void sc_host_table(const pll_partition_t * p, unsigned int pc, int ps, un
     {
       const double * pi = p->frequencies[fi[r]], q = p->prop_invar[fi[r]];
       const double * P = p->pmatrix[m] + (size_t)r * S * Sp;
-      double l = 0.0;
+      double l = 0.0, one = 1.0;
       for (i = 0; i < S; ++i)
       {
         double a = 0.0;
@@ -767,14 +770,21 @@ static void sc_host_table(const pll_partition_t * p, unsigned int pc, int ps, un
       {
         unsigned int d = sc_count(p, ps, cs, n * R + r) - cnt;
         if (d > SC_RATE_MAXDIFF) d = SC_RATE_MAXDIFF;
-        if (d) l *= ldexp(1.0, -256 * (int)d);
+        if (d) { l *= ldexp(1.0, -256 * (int)d); one *= ldexp(1.0, -256 * (int)d); }
       }
-      if (descale) l = (cnt <= 3) ? ldexp(l, -256 * (int)cnt) : 0.0;
+      if (descale) { l = (cnt <= 3) ? ldexp(l, -256 * (int)cnt) : 0.0; one = (cnt <= 3) ? ldexp(one, -256 * (int)cnt) : 0.0; }
       A[n * R + r] = (q > 0.0) ? (1.0 - q) * l : l;
+      if (D) D[n * R + r] = (q > 0.0) ? (1.0 - q) * one : one;
       B[n * R + r] = (q > 0.0 && state >= 0) ? q * pi[state] : 0.0;
     }
     c[n] = descale ? 0u : cnt;
   }
+}
+
+static void sc_host_table(const pll_partition_t * p, unsigned int pc, int ps, unsigned int cc, int cs, unsigned int m,
+                          const unsigned int * fi, double * A, double * B, unsigned int * c)
+{
+  sc_host_table_scaled(p, pc, ps, cc, cs, m, fi, A, B, c, NULL);
 }
 
 /* T[n], and what follows from it: any of the outputs may be NULL.  Returns sum_n m_n lnl[n]. */
@@ -1500,6 +1510,305 @@ static int optimise_around(const blo_t * b, pll_unode_t * p_edge, int radius)
     if (!reorient(ev, p_edge, z, q)) return PLL_FAILURE;
   }
   return PLL_SUCCESS;
+}
+
+/* ---------------------------------------------------------------------- */
+/* Substitution mapping: expected endpoint pairs, substitution counts and  */
+/* dwell times per branch (include/pllhip.h, "substitution mapping")       */
+/* ---------------------------------------------------------------------- */
+
+/* phi(x) = expm1(x) / x, phi(0) = 1 */
+static double sm_phi(double x) { return x == 0.0 ? 1.0 : expm1(x) / x; }
+
+int pllhip_substmap_counts(unsigned int states, unsigned int states_padded, const double * eigenvecs,
+                           const double * inv_eigenvecs, const double * eigenvals, double tau, const double * F,
+                           double * counts, double * dwell)
+{
+  const unsigned int S = states, Sp = states_padded;
+  const double * V = inv_eigenvecs, * W = eigenvecs;         /* V[i][k] = V[i * Sp + k], V^-1[k][j] = W[k * Sp + j] */
+  double * X, * G, * Y;
+  unsigned int a, b, i, j, k, l;
+  if (!S || Sp < S || !eigenvecs || !inv_eigenvecs || !eigenvals || !F || !counts || !dwell || !(tau >= 0.0) || isinf(tau))
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "pllhip_substmap_counts: NULL arguments, or a time that is negative or not finite");
+    return PLL_FAILURE;
+  }
+  X = (double *)calloc((size_t)3 * S * S, sizeof(double));
+  if (!X)
+  {
+    pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "pllhip_substmap_counts: cannot allocate the work space");
+    return PLL_FAILURE;
+  }
+  G = X + (size_t)S * S;
+  Y = G + (size_t)S * S;
+  /* X[k][j] = sum_i V[i][k] F[i][j];  G[k][l] = sum_j X[k][j] V^-1[l][j], times K[k][l] */
+  for (k = 0; k < S; ++k)
+    for (j = 0; j < S; ++j)
+    {
+      double x = 0.0;
+      for (i = 0; i < S; ++i) x += V[i * Sp + k] * F[i * S + j];
+      X[k * S + j] = x;
+    }
+  for (k = 0; k < S; ++k)
+    for (l = 0; l < S; ++l)
+    {
+      /* K = tau e^(hi tau) phi((lo - hi) tau) with hi >= lo: symmetric, the argument of phi never positive */
+      const double hi = eigenvals[k] > eigenvals[l] ? eigenvals[k] : eigenvals[l];
+      const double lo = eigenvals[k] > eigenvals[l] ? eigenvals[l] : eigenvals[k];
+      const double K = tau * exp(hi * tau) * sm_phi((lo - hi) * tau);
+      double g = 0.0;
+      for (j = 0; j < S; ++j) g += X[k * S + j] * W[l * Sp + j];
+      G[k * S + l] = g * K;
+    }
+  /* Y[a][l] = sum_k V^-1[k][a] (G o K)[k][l];  M[a][b] = sum_l Y[a][l] V[b][l] */
+  for (a = 0; a < S; ++a)
+    for (l = 0; l < S; ++l)
+    {
+      double y = 0.0;
+      for (k = 0; k < S; ++k) y += W[k * Sp + a] * G[k * S + l];
+      Y[a * S + l] = y;
+    }
+  for (a = 0; a < S; ++a)
+    for (b = 0; b < S; ++b)
+    {
+      double M = 0.0, q = 0.0;
+      for (l = 0; l < S; ++l) M += Y[a * S + l] * V[b * Sp + l];
+      if (a == b)
+      {
+        dwell[a] = M;
+        counts[a * S + b] = 0.0;
+        continue;
+      }
+      for (k = 0; k < S; ++k) q += V[a * Sp + k] * eigenvals[k] * W[k * Sp + b];
+      counts[a * S + b] = q * M;
+    }
+  free(X);
+  return PLL_SUCCESS;
+}
+
+/* F [cats][S][S] and differ [sites] (or NULL) of an edge on the host, from the partition's own arrays: the definitions of
+   include/pllhip.h in plain C, in the order of the device kernels (scale = m ((w D) / T), pi applied to the sum) */
+static int sm_host_pairs(const pll_partition_t * p, unsigned int pc, int ps, unsigned int cc, int cs, unsigned int m,
+                         const unsigned int * fi, double * F, double * differ, unsigned long long * dropped)
+{
+  const unsigned int S = p->states, Sp = p->states_padded, R = p->rate_cats;
+  const size_t N = p->sites, cells = N * R;
+  double * A = (double *)calloc(cells ? 3 * cells : 1, sizeof(double)), * B = A ? A + cells : NULL, * D = A ? B + cells : NULL;
+  unsigned int * c = (unsigned int *)calloc(N ? N : 1, sizeof(unsigned int));
+  size_t n;
+  unsigned int r, i, j;
+  if (!A || !c)
+  {
+    free(A); free(c);
+    pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the site-category table");
+    return 0;
+  }
+  sc_host_table_scaled(p, pc, ps, cc, cs, m, fi, A, B, c, D);
+  memset(F, 0, sizeof(double) * R * S * S);
+  *dropped = 0;
+  for (n = 0; n < N; ++n)
+  {
+    double T = 0.0, df = 0.0;
+    for (r = 0; r < R; ++r) T += p->rate_weights[r] * (A[n * R + r] + B[n * R + r]);
+    if (!(T > 0.0))
+    {
+      if (p->pattern_weights[n]) ++*dropped;
+      if (differ) differ[n] = 0.0;
+      continue;
+    }
+    for (r = 0; r < R; ++r)
+    {
+      const double * pi = p->frequencies[fi[r]];
+      const double * P = p->pmatrix[m] + (size_t)r * S * Sp;
+      const double scale = (double)p->pattern_weights[n] * ((p->rate_weights[r] * D[n * R + r]) / T);
+      double * Fr = F + (size_t)r * S * S, l0 = 0.0;
+      for (i = 0; i < S; ++i)
+      {
+        const double pa = sc_elem(p, pc, n, r, i), a = scale * pa;
+        double off = 0.0;
+        if (pa == 0.0) continue;
+        for (j = 0; j < S; ++j)
+        {
+          const double ch = sc_elem(p, cc, n, r, j);
+          Fr[i * S + j] += a * ch;
+          if (j != i) off += P[i * Sp + j] * ch;
+        }
+        l0 += pi[i] * pa * off;
+      }
+      df += (p->rate_weights[r] * (D[n * R + r] * l0)) / T;
+    }
+    if (differ) differ[n] = df;
+  }
+  for (r = 0; r < R; ++r)
+    for (i = 0; i < S; ++i)
+      for (j = 0; j < S; ++j) F[((size_t)r * S + i) * S + j] *= p->frequencies[fi[r]][i];
+  free(A); free(c);
+  return 1;
+}
+
+static void sm_destroy_branch(pllhip_branch_subst_t * b)
+{
+  free(b->pairs); free(b->counts); free(b->dwell); free(b->differ);
+}
+
+void pllhip_eval_destroy_substitution_map(pllhip_substitution_map_t * map)
+{
+  unsigned int k, m;
+  if (!map) return;
+  for (k = 0; map->branches && k < map->partition_count; ++k)
+  {
+    for (m = 0; map->branches[k] && m < map->branch_count; ++m) sm_destroy_branch(&map->branches[k][m]);
+    free(map->branches[k]);
+  }
+  free(map->branches);
+  free(map->partition_indices);
+  free(map);
+}
+
+typedef struct
+{
+  pllhip_eval_t * ev;
+  pllhip_substitution_map_t * map;
+  unsigned int flags;
+  int device;
+} sm_walk_t;
+
+/* the record of branch `edge` in every local partition; the vectors of both ends point at each other */
+static int sm_edge(const sm_walk_t * w, pll_unode_t * edge)
+{
+  pllhip_eval_t * ev = w->ev;
+  const unsigned int m = edge->pmatrix_index;
+  unsigned int p, k = 0, r, x;
+  for (p = 0; p < ev->nparts; ++p)
+  {
+    pll_partition_t * part = ev->parts[p];
+    const unsigned int * fi = ev->params[p];
+    pllhip_branch_subst_t * b;
+    unsigned int S, R;
+    size_t cells;
+    double t, * F = NULL, * cr, * dr;
+    if (!part) continue;
+    S = part->states; R = part->rate_cats; cells = (size_t)R * S * S;
+    b = &w->map->branches[k++][m];
+    b->node = edge;
+    b->states = S; b->cats = R; b->sites = part->sites;
+    b->pairs = (double *)calloc(cells, sizeof(double));
+    b->counts = (double *)calloc((size_t)S * S, sizeof(double));
+    b->dwell = (double *)calloc(S, sizeof(double));
+    if (w->flags & PLLHIP_SUBST_SITES) b->differ = (double *)calloc(part->sites ? part->sites : 1, sizeof(double));
+    F = (double *)calloc(cells + (size_t)S * S + S, sizeof(double));
+    if (!b->pairs || !b->counts || !b->dwell || ((w->flags & PLLHIP_SUBST_SITES) && !b->differ) || !F)
+    {
+      free(F);
+      pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the substitution map");
+      return 0;
+    }
+    cr = F + cells; dr = cr + (size_t)S * S;
+    if (w->device)
+    {
+      pllhip_edge_pairs_t * ep = pllhip_substmap_edge(part, edge->clv_index, edge->scaler_index, edge->back->clv_index,
+                                                      edge->back->scaler_index, m, fi, w->flags);
+      if (!ep) { free(F); return 0; }
+      memcpy(F, ep->F, sizeof(double) * cells);
+      memcpy(b->pairs, ep->pairs, sizeof(double) * cells);
+      if (b->differ && part->sites) memcpy(b->differ, ep->differ, sizeof(double) * part->sites);
+      b->dropped = ep->dropped;
+      pllhip_edge_pairs_destroy(ep);
+    }
+    else
+    {
+      if (!sm_host_pairs(part, edge->clv_index, edge->scaler_index, edge->back->clv_index, edge->back->scaler_index, m, fi,
+                         F, b->differ, &b->dropped)) { free(F); return 0; }
+      for (r = 0; r < R; ++r)
+        for (x = 0; x < S * S; ++x)
+          b->pairs[(size_t)r * S * S + x] = F[(size_t)r * S * S + x] * part->pmatrix[m][((size_t)r * S + x / S) * part->states_padded + x % S];
+    }
+    for (x = 0; x < cells; ++x) b->posterior_weight += b->pairs[x];
+    /* the time of category r: what pll_update_prob_matrices exponentiates under */
+    t = effective_length(ev, p, m, edge->length);
+    for (r = 0; r < R; ++r)
+    {
+      const double q = part->prop_invar[fi[r]];
+      const double tau = part->rates[r] * t / (1.0 - q);
+      if (!part->eigen_decomp_valid[fi[r]] && !pll_update_eigen(part, fi[r])) { free(F); return 0; }
+      if (!pllhip_substmap_counts(S, part->states_padded, part->eigenvecs[fi[r]], part->inv_eigenvecs[fi[r]],
+                                  part->eigenvals[fi[r]], tau, F + (size_t)r * S * S, cr, dr)) { free(F); return 0; }
+      for (x = 0; x < S * S; ++x) b->counts[x] += cr[x];
+      for (x = 0; x < S; ++x) b->dwell[x] += dr[x];
+    }
+    for (x = 0; x < S * S; ++x) b->total += b->counts[x];
+    free(F);
+  }
+  return 1;
+}
+
+/* every branch once, by the re-rooting walk of optimise_around: the vector of an inner node is turned towards each of
+   its neighbours in turn and put back as it was */
+static int sm_walk(const sm_walk_t * w, pll_unode_t * edge, int visit)
+{
+  pll_unode_t * q = edge->next, * z = q ? q->next : NULL;
+  if (visit && !sm_edge(w, edge)) return 0;
+  if (q && z)
+  {
+    if (!reorient(w->ev, q, edge, z) || !sm_walk(w, q->back, 1)) return 0;
+    if (!reorient(w->ev, z, q, edge) || !sm_walk(w, z->back, 1)) return 0;
+    if (!reorient(w->ev, edge, z, q)) return 0;
+  }
+  return 1;
+}
+
+pllhip_substitution_map_t * pllhip_eval_substitution_map(pllhip_eval_t * ev, unsigned int flags)
+{
+  sm_walk_t w;
+  pllhip_substitution_map_t * map;
+  unsigned int p, k = 0, local = 0;
+  pll_errno = 0;
+  if (flags & ~PLLHIP_SUBST_SITES)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "unknown flags for the substitution map");
+    return NULL;
+  }
+  for (p = 0; p < ev->nparts; ++p) if (ev->parts[p]) ++local;
+  if (!local)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "substitution map: no local partition");
+    return NULL;
+  }
+  ev->last_was_full = 0;
+  if (!update_vectors(ev, 0))
+  {
+    if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "substitution map: the traversal failed");
+    return NULL;
+  }
+  map = (pllhip_substitution_map_t *)calloc(1, sizeof(*map));
+  if (map)
+  {
+    map->partition_count = local;
+    map->branch_count = ev->edges;
+    map->partition_indices = (unsigned int *)calloc(local, sizeof(unsigned int));
+    map->branches = (pllhip_branch_subst_t **)calloc(local, sizeof(*map->branches));
+    for (p = 0; map->partition_indices && map->branches && p < ev->nparts; ++p)
+      if (ev->parts[p])
+      {
+        map->partition_indices[k] = p;
+        map->branches[k] = (pllhip_branch_subst_t *)calloc(ev->edges, sizeof(pllhip_branch_subst_t));
+        if (!map->branches[k++]) break;
+      }
+  }
+  if (!map || k < local)
+  {
+    pllhip_eval_destroy_substitution_map(map);
+    pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the substitution map");
+    return NULL;
+  }
+  w.ev = ev; w.map = map; w.flags = flags;
+  w.device = pllhip_substmap_edge && pllhip_edge_pairs_destroy;
+  if (sm_walk(&w, ev->root, 1) && sm_walk(&w, ev->root->back, 0) && !pll_errno) return map;
+  if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "substitution map: the walk failed");
+  pllhip_eval_destroy_substitution_map(map);
+  /* the walk stopped with some vector turned away from the root: let the next evaluation rebuild them */
+  memset(ev->clv_valid, 0, ev->records);
+  return NULL;
 }
 
 double pllhip_eval_optimize_branches(pllhip_eval_t * ev, double min_brlen, double max_brlen,

@@ -31,7 +31,7 @@ struct SiteCatOut
 {
   double * A;          // [R][plane]
   double * B;          // [R][plane] or null (no rate has an invariant part)
-  unsigned * c;        // [N]
+  unsigned * c;        // [N] or null (a pass that wants the A planes alone)
   size_t plane;        // doubles between the planes of two rates: even, so that an even site is 16-byte aligned
 };
 
@@ -156,7 +156,7 @@ __device__ inline void sitecat_blocked_body(const ModelView & mv, const ParamIdx
         }
       }
     }
-    if (q == 0 && live_e)
+    if (q == 0 && live_e && out.c)
     {
       out.c[site0] = desc_e ? 0u : cnt_e;
       if (live_o) out.c[site0 + 1] = desc_o ? 0u : cnt_o;
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256) void k_sitecat_s4(ModelView mv, ParamIdx fidx,
     const d4 pv = parent.codes ? tip_value4(tipmap[parent.codes[n]]) : load4(parent.clv + x * 4);
     const double l = (pi[0] * pv.x * t.x + pi[1] * pv.y * t.y) + (pi[2] * pv.z * t.z + pi[3] * pv.w * t.w);
     sitecat_store(mv, fidx, sd, st, n, R, r, l, out);
-    if (r == 0) out.c[n] = st.descale ? 0u : st.cnt;
+    if (r == 0 && out.c) out.c[n] = st.descale ? 0u : st.cnt;
   }
 }
 
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void k_sitecat_generic(ModelView mv, ParamIdx 
       }
       sitecat_store(mv, fidx, sd, st, n, R, r, l, out);
     }
-    out.c[n] = st.descale ? 0u : st.cnt;
+    if (out.c) out.c[n] = st.descale ? 0u : st.cnt;
   }
 }
 

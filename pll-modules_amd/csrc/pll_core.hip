@@ -29,6 +29,7 @@
 #include "kernels_newton_s4.hpp"
 #include "kernels_ancestral.hpp"
 #include "kernels_sitecat.hpp"
+#include "kernels_substmap.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -3935,8 +3936,12 @@ static int sitecat_allow_lds()
 
 // device_job.hpp: the operand set-up of an edge reader (as anc_stage_add and loglikelihood_impl make it), then the
 // family's table kernel on the engine's stream; nothing is waited for
-bool sitecat_edge_table(pll_partition_t * p, unsigned parent_clv, int parent_scaler, unsigned child_clv, int child_scaler,
-                        unsigned matrix_index, const unsigned * freqs_indices, const SiteCatPlanes & planes)
+// pm_other / lut_other: matrices [R][S][Sp] and lookup tables [R][codes][S] to use in place of those of `matrix_index`
+// (the pair table's zeroed diagonal); null: the partition's own.  Such a pass writes its A planes alone: planes.B only
+// says whether the case split has invariant terms, as in the pass before it
+static bool sitecat_edge_table_with(pll_partition_t * p, unsigned parent_clv, int parent_scaler, unsigned child_clv,
+                                    int child_scaler, unsigned matrix_index, const unsigned * freqs_indices,
+                                    const SiteCatPlanes & planes, const double * pm_other, const double * lut_other)
 {
   Engine * e = engine_of(p);
   if (!hip_ok(hipSetDevice(e->device), "hipSetDevice")) return false;
@@ -3955,15 +3960,15 @@ bool sitecat_edge_table(pll_partition_t * p, unsigned parent_clv, int parent_sca
   const ModelView mv = model_view(e);
   const ParamIdx fidx = make_params(p, freqs_indices);
   const NodeRef parent = node_ref(e, parent_clv), child = node_ref(e, child_clv);
-  const double * pm = e->d_pmat + (size_t)matrix_index * e->R * e->S * e->Sp;
-  const double * lut = child.codes ? e->d_lut + (size_t)matrix_index * e->R * e->lut_codes * e->S : nullptr;
+  const double * pm = pm_other ? pm_other : e->d_pmat + (size_t)matrix_index * e->R * e->S * e->Sp;
+  const double * lut = !child.codes ? nullptr : pm_other ? lut_other : e->d_lut + (size_t)matrix_index * e->R * e->lut_codes * e->S;
   SiteCatSide sd;
   sd.ps = scaler_ptr(e, parent_scaler);
   sd.cs = scaler_ptr(e, child_scaler);
   sd.invariant = planes.B ? e->d_invariant : nullptr;
   sd.rate_scalers = e->rate_scalers ? 1u : 0u;
   SiteCatOut out;
-  out.A = planes.A; out.B = planes.B; out.c = planes.c; out.plane = planes.plane;
+  out.A = planes.A; out.B = pm_other ? nullptr : planes.B; out.c = pm_other ? nullptr : planes.c; out.plane = planes.plane;
   if (e->family == KernelFamily::S20 || e->family == KernelFamily::S16)
   {
     const unsigned nblk = (N + S20_BS - 1) / S20_BS;
@@ -3994,6 +3999,118 @@ bool sitecat_edge_table(pll_partition_t * p, unsigned parent_clv, int parent_sca
                          mv, fidx, parent, child, pm, lut, e->lut_codes, e->d_tipmap, e->rows, sd, N, e->R, out);
   }
   return hip_ok(hipGetLastError(), "site-category table kernel");
+}
+
+bool sitecat_edge_table(pll_partition_t * p, unsigned parent_clv, int parent_scaler, unsigned child_clv, int child_scaler,
+                        unsigned matrix_index, const unsigned * freqs_indices, const SiteCatPlanes & planes)
+{
+  return sitecat_edge_table_with(p, parent_clv, parent_scaler, child_clv, child_scaler, matrix_index, freqs_indices, planes,
+                                 nullptr, nullptr);
+}
+
+// ---- the endpoint-pair table of an edge (device_job.hpp, kernels_substmap.hpp) ----
+constexpr size_t SUBSTMAP_PARTIAL_BYTES = (size_t)32 << 20;      // the partial tiles of a call stay below this
+
+static bool substmap_blocked(const Engine * e) { return e->family == KernelFamily::S20 || e->family == KernelFamily::S16; }
+
+// sites a workgroup of the generic pair kernel stages at a time, and the slices of its tile
+static unsigned substmap_chunk(const Engine * e) { return std::max(16u, std::min(256u, 1024u / e->S)); }
+static unsigned substmap_slices(const Engine * e) { return std::max(1u, 256u / (e->S * e->S)); }
+
+bool substmap_shape(pll_partition_t * p, const unsigned * freqs_indices, SubstmapShape & shape)
+{
+  Engine * e = engine_of(p);
+  // (the order of sitecat_edge_table: the lookup tables, whose code count sizes lut0, follow the matrices)
+  if (!hip_ok(hipSetDevice(e->device), "hipSetDevice") || !sync_model(p) || !flush_pmatrices(p) || !ensure_luts(p)) return false;
+  const unsigned N = e->Nreal, nblk = (N + S20_BS - 1) / S20_BS;
+  shape.plane = ((size_t)N + 1) & ~(size_t)1;
+  shape.splane = (size_t)std::max(1u, nblk) * S20_BS;
+  shape.pm_cells = (size_t)e->R * e->S * e->Sp;
+  shape.lut_cells = lut_active(e) ? (size_t)e->R * e->lut_codes * e->S : 0;
+  shape.pinv = false;
+  for (unsigned r = 0; r < e->R; ++r) shape.pinv = shape.pinv || p->prop_invar[freqs_indices[r]] > 0.0;
+  const unsigned long long work = substmap_blocked(e) ? (nblk + 3) / 4 : (N + substmap_chunk(e) - 1) / substmap_chunk(e);
+  const unsigned long long fit = SUBSTMAP_PARTIAL_BYTES / (sizeof(double) * e->R * e->S * e->S);
+  shape.grid = capped_grid("PLLHIP_SUBSTMAP_BLOCKS", std::min<unsigned long long>(std::min<unsigned long long>(work, (unsigned long long)e->cu_count * 4), std::max<unsigned long long>(1, fit)));
+  return true;
+}
+
+bool substmap_scale(pll_partition_t * p, unsigned parent_clv, int parent_scaler, unsigned child_clv, int child_scaler,
+                    unsigned matrix_index, const unsigned * freqs_indices, const SubstmapShape & shape,
+                    const SubstmapBuffers & buf)
+{
+  Engine * e = engine_of(p);
+  SiteCatPlanes planes;
+  planes.A = buf.A; planes.B = buf.B; planes.c = buf.c; planes.plane = shape.plane;
+  if (!sitecat_edge_table(p, parent_clv, parent_scaler, child_clv, child_scaler, matrix_index, freqs_indices, planes))
+    return false;
+  const unsigned N = e->Nreal;
+  if (!hip_ok(hipMemsetAsync(buf.dropped, 0, sizeof(unsigned long long), e->stream), "memset")) return false;
+  if (!N) return true;
+  if (buf.A0)
+  {
+    // the same table under matrices whose diagonal is zero: the lookup tables of a coded child follow them
+    const double * pm = e->d_pmat + (size_t)matrix_index * shape.pm_cells;
+    hipLaunchKernelGGL(k_substmap_zero_diag, dim3(grid_for(shape.pm_cells, 256)), dim3(256), 0, e->stream, pm, buf.pm0, e->R,
+                       e->S, e->Sp);
+    if (shape.lut_cells)
+      hipLaunchKernelGGL(k_rebuild_lut, dim3(1, e->R), dim3(256), 0, e->stream, e->S, e->Sp, e->R, buf.pm0, buf.lut0,
+                         e->lut_codes, e->d_tipmap);
+    if (!hip_ok(hipGetLastError(), "zeroed-diagonal matrices")) return false;
+    planes.A = buf.A0;
+    if (!sitecat_edge_table_with(p, parent_clv, parent_scaler, child_clv, child_scaler, matrix_index, freqs_indices, planes,
+                                 buf.pm0, buf.lut0))
+      return false;
+  }
+  SiteCatSide sd;
+  sd.ps = scaler_ptr(e, parent_scaler);
+  sd.cs = scaler_ptr(e, child_scaler);
+  sd.invariant = buf.B ? e->d_invariant : nullptr;
+  sd.rate_scalers = e->rate_scalers ? 1u : 0u;
+  SubstScale io;
+  io.A = buf.A; io.B = buf.B; io.A0 = buf.A0; io.plane = shape.plane; io.m = buf.m; io.scale = buf.scale;
+  io.splane = shape.splane; io.differ = buf.differ; io.dropped = buf.dropped;
+  hipLaunchKernelGGL(k_substmap_scale, dim3(capped_grid("PLLHIP_SUBSTMAP_BLOCKS", grid_for(shape.splane, 256))), dim3(256), 0,
+                     e->stream, model_view(e), make_params(p, freqs_indices), sd, N, e->R, io);
+  return hip_ok(hipGetLastError(), "pair-table scale kernel");
+}
+
+bool substmap_pairs(pll_partition_t * p, unsigned parent_clv, unsigned child_clv, const SubstmapShape & shape,
+                    const SubstmapBuffers & buf)
+{
+  Engine * e = engine_of(p);
+  const unsigned N = e->Nreal;
+  if (!N) return hip_ok(hipMemsetAsync(buf.partial, 0, sizeof(double) * shape.grid * e->R * e->S * e->S, e->stream), "memset");
+  const NodeRef parent = node_ref(e, parent_clv), child = node_ref(e, child_clv);
+  if (substmap_blocked(e))
+  {
+    const unsigned nblk = (N + S20_BS - 1) / S20_BS;
+#define PLLHIP_CALL(KK) \
+    hipLaunchKernelGGL(k_substmap_pairs_blocked<KK>, dim3(shape.grid), dim3(256), 0, e->stream, parent, child, e->d_tipmap, \
+                       buf.scale, shape.splane, N, nblk, e->R, e->S, buf.partial)
+    PLLHIP_DISPATCH_KS(e->family == KernelFamily::S20 ? 5u : s16_ks(e), PLLHIP_CALL);
+#undef PLLHIP_CALL
+  }
+  else
+  {
+    const unsigned CH = substmap_chunk(e), G = substmap_slices(e);
+    const size_t lds = sizeof(double) * ((size_t)G * e->S * e->S + (size_t)2 * CH * e->S);
+    hipLaunchKernelGGL(k_substmap_pairs_generic, dim3(shape.grid), dim3(256), lds, e->stream, parent, child, e->d_tipmap,
+                       e->family == KernelFamily::S4 ? 0u : e->rows, buf.scale, shape.splane, N, e->R, e->S, e->Sp, CH, G,
+                       buf.partial);
+  }
+  return hip_ok(hipGetLastError(), "pair-table kernel");
+}
+
+bool substmap_reduce(pll_partition_t * p, unsigned matrix_index, const unsigned * freqs_indices,
+                     const SubstmapShape & shape, const SubstmapBuffers & buf)
+{
+  Engine * e = engine_of(p);
+  const unsigned total = e->R * e->S * e->S;
+  hipLaunchKernelGGL(k_substmap_reduce, dim3((total + 63) / 64), dim3(256), 0, e->stream, buf.partial, shape.grid, e->R, e->S,
+                     e->Sp, e->d_pmat + (size_t)matrix_index * shape.pm_cells, model_view(e), make_params(p, freqs_indices),
+                     buf.F, buf.pairs);
+  return hip_ok(hipGetLastError(), "pair-table reduction");
 }
 
 } // namespace pllhip

@@ -58,22 +58,7 @@ bool check_set(const pllhip_sitecat_t * set, const char * who)
   return false;
 }
 
-bool check_weights(const double * w, unsigned R, const char * who)
-{
-  double sum = 0.0;
-  for (unsigned r = 0; r < R; ++r)
-  {
-    if (!(w[r] >= 0.0) || !std::isfinite(w[r]))
-    {
-      set_error(PLL_ERROR_PARAM_INVALID, "%s: weight %u is negative or not finite", who, r);
-      return false;
-    }
-    sum += w[r];
-  }
-  if (sum > 0.0) return true;
-  set_error(PLL_ERROR_PARAM_INVALID, "%s: the weights add up to 0", who);
-  return false;
-}
+bool check_weights(const double * w, unsigned R, const char * who) { return check_category_weights(w, R, who); }
 
 void release(pllhip_sitecat_t * set)
 {

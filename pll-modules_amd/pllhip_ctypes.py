@@ -178,7 +178,8 @@ pllhip_eval_set_fused pllhip_eval_newton_iterations pllhip_eval_set_brlen_linkag
 pllhip_eval_set_brlen_scaler pllhip_eval_get_brlen_scaler pllhip_eval_get_partition_branch_length
 pllhip_eval_set_partition_branch_length pllhip_eval_set_transient
 pllhip_eval_site_rates pllhip_eval_destroy_site_rates pllhip_eval_optimize_rate_weights
-pllhip_eval_rate_weights_trail""".split()
+pllhip_eval_rate_weights_trail
+pllhip_substmap_counts pllhip_eval_substitution_map pllhip_eval_destroy_substitution_map""".split()
 
 PLLHIP_H_FUNCTIONS = """pllhip_device_count pllhip_set_device pllhip_get_device
 pllhip_device_arch pllhip_eigen_decompose pllhip_sync_to_host pllhip_sync_to_device pllhip_get_clv
@@ -212,7 +213,8 @@ pllhip_distmat_nj_joins pllhip_distances_last_times
 pllhip_simulate_edges pllhip_simulate_utree pllhip_simulate_last_times
 pllhip_sitecat_edge pllhip_sitecat_from_table pllhip_sitecat_destroy pllhip_sitecat_sites pllhip_sitecat_categories
 pllhip_sitecat_table pllhip_sitecat_posteriors pllhip_site_posteriors_destroy pllhip_sitecat_em_weights
-pllhip_sitecat_last_times""".split()
+pllhip_sitecat_last_times
+pllhip_substmap_edge pllhip_edge_pairs_destroy pllhip_substmap_last_times""".split()
 
 
 def _u32(a):
@@ -295,6 +297,34 @@ class SitePosteriors:
         self.category_prob, self.lnl = take(res.category_prob, (n,)), take(res.lnl, (n,))
         self.posterior = take(res.posterior, (n, r))
         self.expected = np.ctypeslib.as_array(res.expected, shape=(r,)).copy()
+
+
+PLLHIP_SUBST_SITES = 1
+
+
+class EdgePairsResult(C.Structure):
+    """pllhip_edge_pairs_t (include/pllhip.h)"""
+    _fields_ = [("states", C.c_uint), ("cats", C.c_uint), ("sites", C.c_uint), ("F", c_double_p), ("pairs", c_double_p),
+                ("posterior", c_double_p), ("differ", c_double_p), ("weight_sum", C.c_double),
+                ("dropped", C.c_ulonglong)]
+
+
+class BranchSubstResult(C.Structure):
+    """pllhip_branch_subst_t (include/pllhip_eval.h)"""
+    _fields_ = [("node", C.c_void_p), ("pairs", c_double_p), ("counts", c_double_p), ("dwell", c_double_p),
+                ("differ", c_double_p), ("total", C.c_double), ("posterior_weight", C.c_double),
+                ("dropped", C.c_ulonglong), ("states", C.c_uint), ("cats", C.c_uint), ("sites", C.c_uint)]
+
+
+class SubstitutionMapResult(C.Structure):
+    """pllhip_substitution_map_t"""
+    _fields_ = [("partition_count", C.c_uint), ("branch_count", C.c_uint), ("partition_indices", c_uint_p),
+                ("branches", C.POINTER(C.POINTER(BranchSubstResult)))]
+
+
+class BranchSubst:
+    """numpy copy of a pllhip_branch_subst_t: parent / child (clv indices of node and node->back), matrix, pairs
+    [cats][S][S], counts [S][S], dwell [S], differ [sites] or None, total, posterior_weight, dropped"""
 
 
 class EmFit:
@@ -501,6 +531,13 @@ class PllLib:
                 L.pllhip_eval_optimize_rate_weights.argtypes = [C.c_void_p, C.c_uint, C.c_double, C.c_uint]
                 L.pllhip_eval_rate_weights_trail.restype = C.c_uint
                 L.pllhip_eval_rate_weights_trail.argtypes = [C.c_void_p, c_double_p, c_double_p]
+            if hasattr(L, "pllhip_eval_substitution_map"):
+                L.pllhip_substmap_counts.argtypes = [C.c_uint, C.c_uint, c_double_p, c_double_p, c_double_p, C.c_double,
+                                                     c_double_p, c_double_p, c_double_p]
+                L.pllhip_eval_substitution_map.restype = C.POINTER(SubstitutionMapResult)
+                L.pllhip_eval_substitution_map.argtypes = [C.c_void_p, C.c_uint]
+                L.pllhip_eval_destroy_substitution_map.restype = None
+                L.pllhip_eval_destroy_substitution_map.argtypes = [C.POINTER(SubstitutionMapResult)]
             for fn in ("pllhip_eval_ops", "pllhip_eval_pmatrix_updates", "pllhip_eval_derivative_calls",
                        "pllhip_eval_newton_iterations"):
                 getattr(L, fn).restype = C.c_ulong
@@ -594,6 +631,13 @@ class PllLib:
                                                     c_uint_p, c_double_p, c_double_p]
             L.pllhip_sitecat_last_times.restype = None
             L.pllhip_sitecat_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
+        if hasattr(L, "pllhip_substmap_edge"):
+            L.pllhip_substmap_edge.restype = C.POINTER(EdgePairsResult)
+            L.pllhip_substmap_edge.argtypes = [pp, C.c_uint, C.c_int, C.c_uint, C.c_int, C.c_uint, c_uint_p, C.c_uint]
+            L.pllhip_edge_pairs_destroy.restype = None
+            L.pllhip_edge_pairs_destroy.argtypes = [C.POINTER(EdgePairsResult)]
+            L.pllhip_substmap_last_times.restype = None
+            L.pllhip_substmap_last_times.argtypes = [c_double_p, c_double_p, c_double_p]
         if hasattr(L, "pllhip_sitelh_rell"):
             L.pllhip_sitelh_create.restype = C.c_void_p
             L.pllhip_sitelh_create.argtypes = [C.c_uint, c_uint_p]
@@ -1734,6 +1778,61 @@ class SiteCat:
         return tuple(x.value for x in t)
 
 
+class EdgePairs:
+    """a pllhip_edge_pairs_t: `with EdgePairs.edge(inst, parent, parent_scaler, child, child_scaler, matrix, flags) as ep`
+    gives numpy copies F, pairs [cats][S][S], posterior [cats], differ [sites] or None, weight_sum, dropped; raises
+    RuntimeError with the library's message"""
+
+    def __init__(self, lib, ptr):
+        if not ptr:
+            raise RuntimeError(f"[{lib.errno}] {lib.errmsg}")
+        self.lib, self.L, self.ptr = lib, lib.lib, ptr
+        r = ptr.contents
+        S, R, N = r.states, r.cats, r.sites
+        self.states, self.cats, self.sites = S, R, N
+        self.F = np.ctypeslib.as_array(r.F, shape=(R, S, S)).copy()
+        self.pairs = np.ctypeslib.as_array(r.pairs, shape=(R, S, S)).copy()
+        self.posterior = np.ctypeslib.as_array(r.posterior, shape=(R,)).copy()
+        self.differ = (np.ctypeslib.as_array(r.differ, shape=(N,)).copy() if N else np.zeros(0)) if r.differ else None
+        self.weight_sum, self.dropped = r.weight_sum, r.dropped
+
+    @classmethod
+    def edge(cls, inst, pc_, psc, cc, csc, matrix, flags=0, params=None):
+        inst.lib.errno = 0
+        prm = inst.params_p if params is None else _u32(params).ctypes.data_as(c_uint_p)
+        return cls(inst.lib, inst.L.pllhip_substmap_edge(inst.p, pc_, psc, cc, csc, matrix, prm, flags))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.ptr:
+            self.L.pllhip_edge_pairs_destroy(self.ptr)
+            self.ptr = None
+
+    def last_times(self):
+        """(scale_ms, pairs_ms, reduce_ms) of this thread's last call"""
+        t = [C.c_double(0.0) for _ in range(3)]
+        self.L.pllhip_substmap_last_times(*[C.byref(x) for x in t])
+        return tuple(x.value for x in t)
+
+
+def substmap_counts(lib, eigenvecs, inv_eigenvecs, eigenvals, tau, F):
+    """pllhip_substmap_counts -> (counts [S][S], dwell [S]); eigenvecs / inv_eigenvecs [S][Sp] in libpll's storage"""
+    ev, iv, ew, F = _f64(eigenvecs), _f64(inv_eigenvecs), _f64(eigenvals), _f64(F)
+    S, Sp = F.shape[0], ev.shape[1]
+    counts, dwell = np.zeros((S, S)), np.zeros(S)
+    lib.errno = 0
+    if not lib.lib.pllhip_substmap_counts(S, Sp, ev.ctypes.data_as(c_double_p), iv.ctypes.data_as(c_double_p),
+                                          ew.ctypes.data_as(c_double_p), tau, F.ctypes.data_as(c_double_p),
+                                          counts.ctypes.data_as(c_double_p), dwell.ctypes.data_as(c_double_p)):
+        raise RuntimeError(f"[{lib.errno}] {lib.errmsg}")
+    return counts, dwell
+
+
 class DistMat:
     """pllhip_distmat_t (include/pllhip.h): made by distances_partition / distances_msa / distmat_from_host below.
     A failed call returns None / False with lib.errno set."""
@@ -2103,6 +2202,34 @@ class Evaluation:
             return out
         finally:
             self.L.pllhip_eval_destroy_site_rates(arr)
+
+    def substitution_map(self, flags=0):
+        """pllhip_eval_substitution_map -> [[BranchSubst per branch, by pmatrix_index] per local partition]"""
+        self.lib.errno = 0
+        ptr = self.L.pllhip_eval_substitution_map(self.ev, flags)
+        if not ptr:
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        try:
+            res, out = ptr.contents, []
+            for k in range(res.partition_count):
+                rows = []
+                for m in range(res.branch_count):
+                    b, o = res.branches[k][m], BranchSubst()
+                    node = C.cast(b.node, C.POINTER(UNode)).contents
+                    S, R, N = b.states, b.cats, b.sites
+                    o.parent, o.child, o.matrix = node.clv_index, node.back.contents.clv_index, node.pmatrix_index
+                    o.parent_scaler, o.child_scaler = node.scaler_index, node.back.contents.scaler_index
+                    o.length = node.length
+                    o.pairs = np.ctypeslib.as_array(b.pairs, shape=(R, S, S)).copy()
+                    o.counts = np.ctypeslib.as_array(b.counts, shape=(S, S)).copy()
+                    o.dwell = np.ctypeslib.as_array(b.dwell, shape=(S,)).copy()
+                    o.differ = (np.ctypeslib.as_array(b.differ, shape=(N,)).copy() if N else np.zeros(0)) if b.differ else None
+                    o.total, o.posterior_weight, o.dropped = b.total, b.posterior_weight, b.dropped
+                    rows.append(o)
+                out.append(rows)
+            return out
+        finally:
+            self.L.pllhip_eval_destroy_substitution_map(ptr)
 
     def optimize_rate_weights(self, partition=0, epsilon=1e-3, max_iterations=100):
         """pllhip_eval_optimize_rate_weights -> (lnL of the driver afterwards, EmFit of the trail)"""
