@@ -813,6 +813,59 @@ PLL_EXPORT int pllhip_simulate_utree(pll_partition_t * partition, const pllhip_s
 PLL_EXPORT void pllhip_simulate_last_times(double * tables_ms, double * kernel_ms, double * copy_ms,
                                            unsigned long long * chunks);
 
+/* ---- sampled ancestral states ("Sampled ancestral states") ----
+ * One coherent draw of all unobserved nodes from their joint posterior given the data: per pattern and replicate a
+ * component (rate category, invariant or not) and a state for every node of the edge list, by the process
+ * INTEGRATION.md spells out -- the component from the site-category table of the root edge, the root state from both
+ * sides of that edge, then every edge downwards from Pr(child = j | parent = a, r, data below) ~ P_r[a][j] child[n,r,j].
+ * Draws are those of the simulation contract (stream 0: component, 2: root state, 3 + matrix index: an edge) with the
+ * pattern index as the site counter, so the bytes are a function of (seed, replicate, pattern, the doubles the engine
+ * holds, the edge list with its matrix indices, the root edge) alone.  The caller guarantees that every named vector
+ * points away from its listed parent and root_node's away from other_node: the state after pll_update_partials
+ * towards that edge.  Nothing in the partition changes (a vector that exists as its operation or class table only is
+ * stored, as for any reader); queued matrix requests are launched first.  An ascertainment attribute is ignored.
+ * Environment, read at the call, none of which shows in the results: PLLHIP_ANCS_STAGING_BYTES (device staging buffer,
+ * default 1 GiB), PLLHIP_ANCS_REPLICATES (replicates per pass, at most 8), PLLHIP_ANCS_BLOCKS (workgroups, 0: no cap). */
+#define PLLHIP_ANCS_TIPS      (1u << 0)   /* tip rows are written too: a state compatible with the tip's code */
+#define PLLHIP_ANCS_COMPONENT (1u << 1)   /* fill `component` */
+
+typedef struct pllhip_ancsample_params
+{
+  unsigned long long seed;
+  unsigned int first_replicate;      /* absolute number of replicate 0; first_replicate + replicates <= 2^32 */
+  unsigned int replicates;
+  unsigned int flags;                /* PLLHIP_ANCS_* */
+  const char * alphabet;             /* NULL: state indices; else at least `states` characters.  0xFF stays 0xFF */
+} pllhip_ancsample_params_t;
+
+/* Nodes are numbered like CLVs (< partition->tips: a tip), all < node_count; the edge list
+   (parent -> child, matrix) is a tree from root_node and holds the edge root_node -> other_node exactly once, with the
+   root matrix.  out[replicate][node_count][partition->sites], one byte each: rows not named, and tip rows without
+   PLLHIP_ANCS_TIPS, hold 0xFF.  component[replicate][sites] (with PLLHIP_ANCS_COMPONENT, else ignored): r, or 0x80 | r
+   for an invariant draw, on which every row holds invariant[site].  A site whose table total is not > 0 or not finite
+   is dropped: 0xFF in every row and in `component`; *dropped (may be NULL) counts those with a pattern weight, once.
+   PLL_ERROR_PARAM_INVALID, with nothing written: NULLs, zero replicates, unknown flags, an index out of range, a list
+   simplan rejects (a node reached twice, a tip as a parent, a node never reached), no or several root edges in the
+   list, a tip as root_node, a short alphabet, a sharded partition, weights that are negative, not finite or all 0, a
+   vector that cannot be stored beside the others. */
+PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const pllhip_ancsample_params_t * params,
+                                             unsigned int root_node, int root_scaler, unsigned int other_node,
+                                             int other_scaler, unsigned int edge_count, const unsigned int * parent,
+                                             const unsigned int * child, const unsigned int * matrix_indices,
+                                             const unsigned int * freqs_indices, unsigned int node_count,
+                                             unsigned char * out, unsigned char * component,
+                                             unsigned long long * dropped);
+/* The same for a tree walked from `root` (an inner node; the root edge is root -- root->back): rows are clv_index,
+   matrices pmatrix_index, scalers scaler_index, node_count = tips + clv_buffers.  Touches neither matrices nor vectors. */
+PLL_EXPORT int pllhip_sample_ancestral_utree(pll_partition_t * partition, const pllhip_ancsample_params_t * params,
+                                             const pll_unode_t * root, const unsigned int * freqs_indices,
+                                             unsigned char * out, unsigned char * component,
+                                             unsigned long long * dropped);
+/* this thread's last call: device time of the table kernel and of the walk kernels in ms between HIP events, the
+   copies (device to pinned memory, and from there into `out`) in ms, and the staging chunks */
+PLL_EXPORT void pllhip_ancsample_last_times(double * table_ms, double * kernel_ms, double * copy_ms,
+                                            unsigned long long * chunks);
+
 /* ---- topology tests and bootstrap weights ("Topology tests and bootstrap weights"; DESIGN.md
  *      section 20) ----
  * A site-likelihood set holds, on the device pllhip_get_device() names at its creation, a matrix L[trees][patterns]

@@ -330,6 +330,38 @@ typedef struct pllhip_substitution_map
 PLL_EXPORT pllhip_substitution_map_t * pllhip_eval_substitution_map(pllhip_eval_t * ev, unsigned int flags);
 PLL_EXPORT void pllhip_eval_destroy_substitution_map(pllhip_substitution_map_t * map);
 
+/* ---------------------------------------------------------------------------
+ * Sampled ancestral states (include/pllhip.h, "sampled ancestral states"; the process: INTEGRATION.md): one coherent
+ * draw of a rate category and a state for every node of every site from their joint posterior given the data -- the
+ * first step of stochastic mapping, posterior-predictive checks, alternative ancestors, imputation at the tips
+ * (PLLHIP_ANCS_TIPS).
+ * pllhip_eval_sample_ancestral evaluates the whole tree at the current root edge with evaluate-only mode off (every
+ * vector stored; the mode of later evaluations is what it was), then draws params->replicates replicates for every
+ * local partition with its own params_indices.  Rows are clv_index (node_count = tips + clv_buffers, the largest of the
+ * local partitions); `component` is always filled.  The root, the branch lengths and the log-likelihood are afterwards
+ * what they were.  On the HIP engine the draw is pllhip_sample_ancestral_edges; where the library has no such call (the
+ * CPU oracle) the driver runs the same contract in plain C from the partition's own arrays (clv, tipchars / tipmap,
+ * pmatrix, scale_buffer, invariant) and its host site-category table.  NULL on error (pll_errno set): NULL parameters,
+ * zero replicates, unknown flags, more than 256 states or 128 categories, a short alphabet, invalid category weights,
+ * no local partition, a root edge between two tips.
+ * ------------------------------------------------------------------------- */
+typedef struct pllhip_sampled_ancestral
+{
+  unsigned int partition_count;          /* local partitions */
+  unsigned int node_count;               /* rows per replicate */
+  unsigned int replicates;
+  unsigned int * partition_indices;      /* [partition_count] */
+  unsigned int * sites;                  /* [partition_count] */
+  unsigned int * clv_index;              /* [node_count]: the clv_index of every row */
+  unsigned char ** out;                  /* [partition_count][replicate][node_count][sites] */
+  unsigned char ** component;            /* [partition_count][replicate][sites] */
+  unsigned long long * dropped;          /* [partition_count] */
+} pllhip_sampled_ancestral_t;
+
+PLL_EXPORT pllhip_sampled_ancestral_t * pllhip_eval_sample_ancestral(pllhip_eval_t * ev,
+                                                                     const pllhip_ancsample_params_t * params);
+PLL_EXPORT void pllhip_eval_destroy_sampled_ancestral(pllhip_sampled_ancestral_t * sa);
+
 PLL_EXPORT unsigned long pllhip_eval_ops(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_pmatrix_updates(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_derivative_calls(const pllhip_eval_t * ev);   /* sumtable scans */

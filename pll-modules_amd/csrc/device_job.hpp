@@ -148,6 +148,62 @@ bool substmap_pairs(pll_partition_t * p, unsigned parent_clv, unsigned child_clv
 bool substmap_reduce(pll_partition_t * p, unsigned matrix_index, const unsigned * freqs_indices,
                      const SubstmapShape & shape, const SubstmapBuffers & buf);
 
+// The joint sample of the ancestral states (kernels_ancsample.hpp; contract: INTEGRATION.md, "Sampled ancestral
+// states"), in two steps on the engine's stream; the partition must not be a router (pll_core.hip).
+// ancsample_operands: the operand set-up of a reader of all the named vectors -- model, queued matrices, tip map,
+// invariant states, and every vector of `nodes` stored where it existed as its operation or as a class table only --
+// and the device views of these vectors in the order of `nodes`.  Fails, naming the node, where a vector is still
+// unstored afterwards.  ancsample_walk: one launch of k_ancsample_walk.
+struct AncsVector
+{
+  const double * clv = nullptr;
+  const uint8_t * codes = nullptr;             // a coded tip: its byte codes, read through the tip map
+};
+// one edge of the program (sim_plan.hpp, Step) as the kernel reads it
+struct AncsStep
+{
+  AncsVector child;
+  unsigned long long pm = 0;                   // doubles from the first matrix to the edge's own
+  unsigned stream = 0;                         // 3 + matrix index
+  unsigned src = 0, dst = 0;                   // slots (dst ~0u: the child keeps none)
+  unsigned row = 0;                            // output row of the child (~0u: not asked for)
+};
+struct AncsOperands
+{
+  const double * pmat = nullptr;               // [matrix][R][S][Sp]
+  const double * weights = nullptr;            // [R]
+  const double * freqs = nullptr;              // [rate matrix][Sp]
+  ParamIdxHost fidx = {};
+  const int * invariant = nullptr;             // [sites], or null
+  const unsigned long long * tipmap = nullptr;
+  unsigned brows = 0;                          // state rows per blocked unit (0: the API layout)
+  unsigned R = 0, S = 0, Sp = 0;
+  unsigned cu_count = 0;
+};
+struct AncsLaunch
+{
+  const AncsStep * steps = nullptr;
+  unsigned nsteps = 0, slots = 0;
+  AncsVector root, other;
+  unsigned long long pm0 = 0;                  // the root matrix, as AncsStep::pm
+  unsigned root_row = 0;
+  const double * A = nullptr, * B = nullptr;   // the site-category table of the root edge, [R][plane]; B may be null
+  size_t plane = 0;
+  const unsigned * m = nullptr;                // [sites] pattern weights
+  unsigned long long * dropped = nullptr;      // null: this launch does not count
+  unsigned long long seed = 0;
+  unsigned first_replicate = 0;                // absolute number of replicate 0 of the launch
+  unsigned replicates = 0, per_pass = 0;       // per_pass <= ANCS_RC
+  unsigned site0 = 0, sites = 0, tiles = 0;    // patterns site0 .. site0 + sites - 1 are columns 0 .. sites - 1
+  unsigned rows = 0, comp_row = 0;             // rows per replicate in `out`; the row of the component bytes (~0u: none)
+  size_t pitch = 0;
+  uint8_t * out = nullptr;                     // [replicate][rows][pitch], 0xFF before the launch
+  const uint8_t * alphabet = nullptr;          // [256]
+};
+bool ancsample_operands(pll_partition_t * p, const unsigned * freqs_indices, const unsigned * nodes, unsigned count,
+                        AncsOperands & ops, AncsVector * views);
+bool ancsample_walk(pll_partition_t * p, const AncsOperands & ops, const AncsLaunch & launch, unsigned grid);
+
 // category weights a site-category or pair table can be made under: finite, non-negative, not all zero
 inline bool check_category_weights(const double * w, unsigned R, const char * who)
 {

@@ -21,6 +21,7 @@
 #pragma weak pllhip_sitecat_destroy
 #pragma weak pllhip_substmap_edge         /* HIP engine only: with the CPU oracle the driver computes the pair table itself */
 #pragma weak pllhip_edge_pairs_destroy
+#pragma weak pllhip_sample_ancestral_edges   /* HIP engine only: with the CPU oracle the driver walks the tree itself */
 #include <stdarg.h>
 
 static __thread pllhip_eval_t * cb_self;   /* pll_utree_traverse callbacks carry no user pointer */
@@ -1808,6 +1809,320 @@ pllhip_substitution_map_t * pllhip_eval_substitution_map(pllhip_eval_t * ev, uns
   pllhip_eval_destroy_substitution_map(map);
   /* the walk stopped with some vector turned away from the root: let the next evaluation rebuild them */
   memset(ev->clv_valid, 0, ev->records);
+  return NULL;
+}
+
+/* ---------------------------------------------------------------------- */
+/* Sampled ancestral states: one draw of all unobserved nodes from their    */
+/* joint posterior (include/pllhip.h, "sampled ancestral states")           */
+/* ---------------------------------------------------------------------- */
+
+/* the draws of the simulation contract (rell_mix, sim_key, sim_u, the bisection of sim_pick) */
+static unsigned long long as_mix(unsigned long long seed, unsigned long long c)
+{
+  unsigned long long z = seed + (c + 1ULL) * 0x9E3779B97F4A7C15ULL;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+
+static double as_u(unsigned long long seed, unsigned long long b, unsigned int stream, unsigned long long n)
+{
+  return (double)(as_mix(as_mix(seed, (b << 32) | stream), n) >> 11) * 0x1.0p-53;
+}
+
+/* cum[0 .. n): the masses cumulated left to right; the pick for the draw u */
+static unsigned int as_pick(const double * cum, unsigned int n, double u)
+{
+  const double x = u * cum[n - 1];
+  unsigned int lo = 0, hi = n - 1;
+  while (lo < hi)
+  {
+    const unsigned int mid = (lo + hi) >> 1;
+    if (cum[mid] > x) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+static int as_check(const pll_partition_t * part, unsigned int p, const pllhip_ancsample_params_t * params,
+                    const unsigned int * fi)
+{
+  unsigned int r;
+  double sum = 0.0;
+  if (part->states > 256 || part->rate_cats > 128)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: partition %u has more than 256 states or more "
+                      "than 128 categories", p);
+    return 0;
+  }
+  if (params->alphabet && strnlen(params->alphabet, part->states) < part->states)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the alphabet has fewer than %u characters "
+                      "(partition %u)", part->states, p);
+    return 0;
+  }
+  for (r = 0; r < part->rate_cats; ++r)
+  {
+    if (fi[r] >= part->rate_matrices)
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: parameter index %u of category %u of "
+                        "partition %u is out of range", fi[r], r, p);
+      return 0;
+    }
+    if (!(part->rate_weights[r] >= 0.0) || !isfinite(part->rate_weights[r]))
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: weight %u of partition %u is negative or "
+                        "not finite", r, p);
+      return 0;
+    }
+    sum += part->rate_weights[r];
+  }
+  if (sum > 0.0) return 1;
+  pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the weights of partition %u add up to 0", p);
+  return 0;
+}
+
+/* The contract of INTEGRATION.md, "Sampled ancestral states", in plain C from the partition's host arrays: the second
+   implementation of k_ancsample_walk, for libraries that keep host arrays.  The edges come parents first (as_edges);
+   edge 0 is the root edge.  Every product and sum is one fp64 operation in the order written (the file is built
+   without contraction).  0: out of memory. */
+static int as_host(const pll_partition_t * part, const pllhip_ancsample_params_t * params, unsigned int edge_count,
+                   const unsigned int * parent, const unsigned int * child, const unsigned int * matrix,
+                   const double * A, const double * B, const unsigned int * fi, unsigned int node_count,
+                   unsigned char * out, unsigned char * component, unsigned long long * dropped)
+{
+  const unsigned int S = part->states, Sp = part->states_padded, R = part->rate_cats, tips = part->tips;
+  const size_t N = part->sites;
+  const int with_tips = (params->flags & PLLHIP_ANCS_TIPS) != 0;
+  const unsigned int root = parent[0], other = child[0], m0 = matrix[0];
+  double * comp = (double *)malloc(sizeof(double) * (2 * R + S)), * cum = comp ? comp + 2 * R : NULL;   /* [2R], [S] */
+  unsigned char * state = (unsigned char *)malloc(node_count ? node_count : 1);
+  size_t n;
+  unsigned int b, r, i, j, k;
+  *dropped = 0;
+  if (!comp || !state) { free(comp); free(state); return 0; }
+  for (n = 0; n < N; ++n)
+  {
+    double acc = 0.0;
+    for (r = 0; r < R; ++r)
+    {
+      acc = acc + part->rate_weights[r] * A[n * R + r];
+      comp[2 * r] = acc;
+      acc = acc + part->rate_weights[r] * B[n * R + r];
+      comp[2 * r + 1] = acc;
+    }
+    if (!(acc > 0.0) || !isfinite(acc))
+    {
+      if (part->pattern_weights[n] > 0) ++*dropped;     /* (the caller filled everything with 0xFF) */
+      continue;
+    }
+    for (b = 0; b < params->replicates; ++b)
+    {
+      const unsigned long long rep = (unsigned long long)params->first_replicate + b;
+      unsigned char * rows = out + (size_t)b * node_count * N + n;
+      int inv;
+      k = as_pick(comp, 2 * R, as_u(params->seed, rep, 0, n));
+      r = k >> 1;
+      inv = (int)(k & 1u);
+      if (component) component[(size_t)b * N + n] = (unsigned char)(r | (inv ? 0x80u : 0u));
+      if (inv) state[root] = (unsigned char)((part->invariant ? part->invariant[n] : -1) & 255);
+      else
+      {
+        const double * P = part->pmatrix[m0] + (size_t)r * S * Sp, * pi = part->frequencies[fi[r]];
+        acc = 0.0;
+        for (i = 0; i < S; ++i)
+        {
+          double t = 0.0;
+          for (j = 0; j < S; ++j) t = t + P[i * Sp + j] * sc_elem(part, other, n, r, j);
+          acc = acc + (pi[i] * sc_elem(part, root, n, r, i)) * t;
+          cum[i] = acc;
+        }
+        state[root] = (unsigned char)as_pick(cum, S, as_u(params->seed, rep, 2, n));
+      }
+      for (k = 0; k <= edge_count; ++k)
+      {
+        const unsigned int node = k ? child[k - 1] : root;
+        if (k && inv) state[node] = state[root];
+        else if (k)
+        {
+          const double * row = part->pmatrix[matrix[k - 1]] + ((size_t)r * S + state[parent[k - 1]]) * Sp;
+          acc = 0.0;
+          for (j = 0; j < S; ++j)
+          {
+            acc = acc + row[j] * sc_elem(part, node, n, r, j);
+            cum[j] = acc;
+          }
+          state[node] = (unsigned char)as_pick(cum, S, as_u(params->seed, rep, 3u + matrix[k - 1], n));
+        }
+        if (node >= tips || with_tips)
+          rows[(size_t)node * N] = state[node] == 255 || !params->alphabet ? state[node]
+                                                                            : (unsigned char)params->alphabet[state[node]];
+      }
+    }
+  }
+  free(comp);
+  free(state);
+  return 1;
+}
+
+/* the edges of the tree seen from the inner record `root`, parents first and root -> root->back first; 0: out of
+   memory.  (The walk of pllhip_simulate_utree.) */
+static int as_edges(const pllhip_eval_t * ev, const pll_unode_t * root, unsigned int ** parent, unsigned int ** child,
+                    unsigned int ** matrix, unsigned int * count)
+{
+  const size_t cap = (size_t)ev->edges + 1;
+  const pll_unode_t ** stack = (const pll_unode_t **)malloc((cap + 1) * sizeof(pll_unode_t *));
+  size_t top = 0;
+  *parent = (unsigned int *)malloc(cap * sizeof(unsigned int));
+  *child = (unsigned int *)malloc(cap * sizeof(unsigned int));
+  *matrix = (unsigned int *)malloc(cap * sizeof(unsigned int));
+  *count = 0;
+  if (!stack || !*parent || !*child || !*matrix)
+  {
+    free((void *)stack); free(*parent); free(*child); free(*matrix);
+    *parent = *child = *matrix = NULL;
+    return 0;
+  }
+  stack[top++] = root;
+  while (top)
+  {
+    const pll_unode_t * entry = stack[--top];
+    const pll_unode_t * n = entry == root ? entry : entry->next;
+    if (!n) continue;
+    do
+    {
+      if (*count == cap) break;
+      (*parent)[*count] = n->clv_index;
+      (*child)[*count] = n->back->clv_index;
+      (*matrix)[*count] = n->pmatrix_index;
+      ++*count;
+      stack[top++] = n->back;
+      n = n->next;
+    } while (n != entry);
+  }
+  free((void *)stack);
+  return 1;
+}
+
+void pllhip_eval_destroy_sampled_ancestral(pllhip_sampled_ancestral_t * sa)
+{
+  unsigned int k;
+  if (!sa) return;
+  for (k = 0; k < sa->partition_count; ++k)
+  {
+    if (sa->out) free(sa->out[k]);
+    if (sa->component) free(sa->component[k]);
+  }
+  free(sa->out); free(sa->component); free(sa->dropped); free(sa->sites); free(sa->partition_indices);
+  free(sa->clv_index);
+  free(sa);
+}
+
+pllhip_sampled_ancestral_t * pllhip_eval_sample_ancestral(pllhip_eval_t * ev, const pllhip_ancsample_params_t * params)
+{
+  const int device = pllhip_sample_ancestral_edges != NULL;
+  const pll_unode_t * root;
+  pllhip_sampled_ancestral_t * sa = NULL;
+  unsigned int * parent = NULL, * child = NULL, * matrix = NULL;
+  unsigned int p, k = 0, local = 0, count = 0, rows = 0, i;
+  pll_errno = 0;
+  if (!params || !params->replicates || (params->flags & ~(unsigned int)(PLLHIP_ANCS_TIPS | PLLHIP_ANCS_COMPONENT)) ||
+      (unsigned long long)params->first_replicate + params->replicates > (1ULL << 32))
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: NULL parameters, zero replicates, unknown "
+                      "flags or a replicate number of 2^32 or more");
+    return NULL;
+  }
+  root = ev->root->next ? ev->root : ev->root->back;         /* the same edge from its inner end */
+  if (!root->next)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the root edge joins two tips");
+    return NULL;
+  }
+  for (p = 0; p < ev->nparts; ++p)
+    if (ev->parts[p])
+    {
+      if (!as_check(ev->parts[p], p, params, ev->params[p])) return NULL;
+      if (ev->parts[p]->tips + ev->parts[p]->clv_buffers > rows) rows = ev->parts[p]->tips + ev->parts[p]->clv_buffers;
+      ++local;
+    }
+  if (!local)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: no local partition");
+    return NULL;
+  }
+  /* a full evaluation at the current root that stores every vector: evaluate-only mode is off for it, and the next
+     full evaluation decides anew */
+  pllhip_eval_invalidate_all(ev);
+  if (ev->transient != PLLHIP_EVAL_TRANSIENT_OFF) partitions_transient(ev, 0, 1);
+  ev->last_was_full = 0;
+  if (!update_vectors(ev, 0))
+  {
+    if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the traversal failed");
+    return NULL;
+  }
+  sa = (pllhip_sampled_ancestral_t *)calloc(1, sizeof(*sa));
+  if (!sa || !as_edges(ev, root, &parent, &child, &matrix, &count)) goto nomem;
+  sa->partition_count = local;
+  sa->node_count = rows;
+  sa->replicates = params->replicates;
+  sa->partition_indices = (unsigned int *)calloc(local, sizeof(unsigned int));
+  sa->sites = (unsigned int *)calloc(local, sizeof(unsigned int));
+  sa->dropped = (unsigned long long *)calloc(local, sizeof(unsigned long long));
+  sa->out = (unsigned char **)calloc(local, sizeof(unsigned char *));
+  sa->component = (unsigned char **)calloc(local, sizeof(unsigned char *));
+  sa->clv_index = (unsigned int *)calloc(rows ? rows : 1, sizeof(unsigned int));
+  if (!sa->partition_indices || !sa->sites || !sa->dropped || !sa->out || !sa->component || !sa->clv_index) goto nomem;
+  for (i = 0; i < rows; ++i) sa->clv_index[i] = i;
+  for (p = 0; p < ev->nparts; ++p)
+  {
+    pll_partition_t * part = ev->parts[p];
+    size_t cells;
+    int ok;
+    if (!part) continue;
+    cells = (size_t)params->replicates * part->sites;
+    sa->partition_indices[k] = p;
+    sa->sites[k] = part->sites;
+    sa->out[k] = (unsigned char *)malloc(cells && rows ? cells * rows : 1);
+    sa->component[k] = (unsigned char *)malloc(cells ? cells : 1);
+    if (!sa->out[k] || !sa->component[k]) goto nomem;
+    memset(sa->out[k], 0xFF, cells * rows);
+    memset(sa->component[k], 0xFF, cells);
+    if (device)
+    {
+      pllhip_ancsample_params_t q = *params;
+      q.flags |= PLLHIP_ANCS_COMPONENT;
+      ok = pllhip_sample_ancestral_edges(part, &q, root->clv_index, root->scaler_index, root->back->clv_index,
+                                         root->back->scaler_index, count, parent, child, matrix, ev->params[p], rows,
+                                         sa->out[k], sa->component[k], &sa->dropped[k]);
+    }
+    else
+    {
+      double * A, * B;
+      unsigned int * c;
+      const pll_unode_t * saved = ev->root;
+      ev->root = (pll_unode_t *)root;                      /* (sc_host_root_table reads the edge from ev->root) */
+      ok = sc_host_root_table(ev, p, &A, &B, &c);
+      ev->root = (pll_unode_t *)saved;
+      if (ok)
+      {
+        ok = as_host(part, params, count, parent, child, matrix, A, B, ev->params[p], rows, sa->out[k],
+                     sa->component[k], &sa->dropped[k]);
+        free(A); free(B); free(c);
+        if (!ok) goto nomem;
+      }
+    }
+    if (!ok) goto fail;
+    ++k;
+  }
+  free(parent); free(child); free(matrix);
+  return sa;
+nomem:
+  pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the sampled ancestral states");
+fail:
+  if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the call failed");
+  free(parent); free(child); free(matrix);
+  pllhip_eval_destroy_sampled_ancestral(sa);
   return NULL;
 }
 

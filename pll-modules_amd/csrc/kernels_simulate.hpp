@@ -13,7 +13,7 @@
 #include <stdint.h>
 
 #include "engine.h"
-#include "rell_mix.hpp"
+#include "sim_draw.hpp"
 
 namespace pllhip {
 
@@ -53,21 +53,6 @@ struct SimLaunch
   size_t pitch;                   // bytes between rows (a multiple of 4)
   uint8_t * out;                  // [replicate][row][pitch]
 };
-
-__host__ __device__ inline rell_u64 sim_key(rell_u64 seed, rell_u64 b, unsigned k) { return rell_mix(seed, (b << 32) | k); }
-__host__ __device__ inline double sim_u(rell_u64 key, rell_u64 j) { return (double)(rell_mix(key, j) >> 11) * 0x1.0p-53; }
-
-// the number of s in 0 .. n - 2 with cum[s] <= u, by bisection (cum is monotone: its entries were clamped at 0)
-template <typename P> __device__ inline unsigned sim_pick(P cum, unsigned n, double u)
-{
-  unsigned lo = 0, hi = n - 1;
-  while (lo < hi)
-  {
-    const unsigned mid = (lo + hi) >> 1;
-    if (cum[mid] > u) hi = mid; else lo = mid + 1;
-  }
-  return lo;
-}
 
 __device__ inline double sim_clamp(double x) { return x > 0.0 ? x : 0.0; }
 

@@ -30,6 +30,7 @@
 #include "kernels_ancestral.hpp"
 #include "kernels_sitecat.hpp"
 #include "kernels_substmap.hpp"
+#include "kernels_ancsample.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -4006,6 +4007,58 @@ bool sitecat_edge_table(pll_partition_t * p, unsigned parent_clv, int parent_sca
 {
   return sitecat_edge_table_with(p, parent_clv, parent_scaler, child_clv, child_scaler, matrix_index, freqs_indices, planes,
                                  nullptr, nullptr);
+}
+
+// ---- the joint sample of the ancestral states (device_job.hpp, kernels_ancsample.hpp) ----
+bool ancsample_operands(pll_partition_t * p, const unsigned * freqs_indices, const unsigned * nodes, unsigned count,
+                        AncsOperands & ops, AncsVector * views)
+{
+  Engine * e = engine_of(p);
+  if (!hip_ok(hipSetDevice(e->device), "hipSetDevice")) return false;
+  for (unsigned k = 0; k < count; ++k)
+    if (!check_clv_index(e, nodes[k], "named")) return false;
+  // (the order of sitecat_edge_table, which follows with the root edge)
+  if (!sync_model(p) || !flush_pmatrices(p) || !ensure_luts(p) || !ensure_invariant(p)) return false;
+  // vectors that exist as their operation only are stored by one list (children before parents), then the class tables
+  // are expanded; storing writes the vector's own buffer alone, so a vector made valid stays valid for the others
+  std::vector<unsigned> unstored;
+  for (unsigned k = 0; k < count; ++k)
+    if (e->ledger.live(nodes[k])) unstored.push_back(nodes[k]);
+  if (!unstored.empty() && !e->transient_busy && !store_unstored(e, unstored)) return false;
+  for (unsigned k = 0; k < count; ++k)
+  {
+    if (!need_clv(e, nodes[k])) return false;
+    if (e->ledger.live(nodes[k]))
+    {
+      set_error(PLL_ERROR_PARAM_INVALID, "the vector of node %u exists as its operation only and cannot be stored beside "
+                "the others", nodes[k]);
+      return false;
+    }
+    const NodeRef ref = node_ref(e, nodes[k]);
+    views[k].clv = ref.clv;
+    views[k].codes = ref.codes;
+  }
+  const ModelView mv = model_view(e);
+  ops.pmat = e->d_pmat;
+  ops.weights = mv.base + mv.off_weights;
+  ops.freqs = mv.base + mv.off_freqs;
+  ops.fidx = make_params(p, freqs_indices);
+  ops.invariant = e->d_invariant && e->invariant_uploaded ? e->d_invariant : nullptr;
+  ops.tipmap = e->d_tipmap;
+  ops.brows = e->rows;
+  ops.R = e->R;
+  ops.S = e->S;
+  ops.Sp = e->Sp;
+  ops.cu_count = e->cu_count;
+  return true;
+}
+
+bool ancsample_walk(pll_partition_t * p, const AncsOperands & ops, const AncsLaunch & launch, unsigned grid)
+{
+  Engine * e = engine_of(p);
+  const size_t lds = (size_t)launch.slots * ANCS_WG * sizeof(unsigned long long) + 256;
+  hipLaunchKernelGGL(k_ancsample_walk, dim3(grid), dim3(ANCS_WG), lds, e->stream, ops, launch);
+  return hip_ok(hipGetLastError(), "k_ancsample_walk");
 }
 
 // ---- the endpoint-pair table of an edge (device_job.hpp, kernels_substmap.hpp) ----

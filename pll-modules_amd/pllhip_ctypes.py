@@ -179,7 +179,8 @@ pllhip_eval_set_brlen_scaler pllhip_eval_get_brlen_scaler pllhip_eval_get_partit
 pllhip_eval_set_partition_branch_length pllhip_eval_set_transient
 pllhip_eval_site_rates pllhip_eval_destroy_site_rates pllhip_eval_optimize_rate_weights
 pllhip_eval_rate_weights_trail
-pllhip_substmap_counts pllhip_eval_substitution_map pllhip_eval_destroy_substitution_map""".split()
+pllhip_substmap_counts pllhip_eval_substitution_map pllhip_eval_destroy_substitution_map
+pllhip_eval_sample_ancestral pllhip_eval_destroy_sampled_ancestral""".split()
 
 PLLHIP_H_FUNCTIONS = """pllhip_device_count pllhip_set_device pllhip_get_device
 pllhip_device_arch pllhip_eigen_decompose pllhip_sync_to_host pllhip_sync_to_device pllhip_get_clv
@@ -214,7 +215,8 @@ pllhip_simulate_edges pllhip_simulate_utree pllhip_simulate_last_times
 pllhip_sitecat_edge pllhip_sitecat_from_table pllhip_sitecat_destroy pllhip_sitecat_sites pllhip_sitecat_categories
 pllhip_sitecat_table pllhip_sitecat_posteriors pllhip_site_posteriors_destroy pllhip_sitecat_em_weights
 pllhip_sitecat_last_times
-pllhip_substmap_edge pllhip_edge_pairs_destroy pllhip_substmap_last_times""".split()
+pllhip_substmap_edge pllhip_edge_pairs_destroy pllhip_substmap_last_times
+pllhip_sample_ancestral_edges pllhip_sample_ancestral_utree pllhip_ancsample_last_times""".split()
 
 
 def _u32(a):
@@ -383,6 +385,28 @@ class SimParams(C.Structure):
                 ("first_replicate", C.c_uint), ("replicates", C.c_uint), ("flags", C.c_uint), ("alphabet", C.c_char_p)]
 
 
+PLLHIP_ANCS_TIPS, PLLHIP_ANCS_COMPONENT = 1, 2
+
+
+class AncSampleParams(C.Structure):
+    """pllhip_ancsample_params_t, include/pllhip.h"""
+    _fields_ = [("seed", C.c_ulonglong), ("first_replicate", C.c_uint), ("replicates", C.c_uint), ("flags", C.c_uint),
+                ("alphabet", C.c_char_p)]
+
+
+class SampledAncestralResult(C.Structure):
+    """pllhip_sampled_ancestral_t, include/pllhip_eval.h"""
+    _fields_ = [("partition_count", C.c_uint), ("node_count", C.c_uint), ("replicates", C.c_uint),
+                ("partition_indices", C.POINTER(C.c_uint)), ("sites", C.POINTER(C.c_uint)),
+                ("clv_index", C.POINTER(C.c_uint)), ("out", C.POINTER(C.POINTER(C.c_ubyte))),
+                ("component", C.POINTER(C.POINTER(C.c_ubyte))), ("dropped", C.POINTER(C.c_ulonglong))]
+
+
+class SampledAncestral:
+    """one local partition of pllhip_eval_sample_ancestral: out uint8 [replicates][rows][sites], component
+    [replicates][sites], dropped, clv_index [rows]"""
+
+
 class Rell:
     """numpy copy of a pllhip_rell_result_t: trees, replicates, best, batch, lnl, bp_count, kh_count, sh_count, elw,
     R [replicates][trees] or None, times = (draw, product, statistics) in ms"""
@@ -531,6 +555,11 @@ class PllLib:
                 L.pllhip_eval_optimize_rate_weights.argtypes = [C.c_void_p, C.c_uint, C.c_double, C.c_uint]
                 L.pllhip_eval_rate_weights_trail.restype = C.c_uint
                 L.pllhip_eval_rate_weights_trail.argtypes = [C.c_void_p, c_double_p, c_double_p]
+            if hasattr(L, "pllhip_eval_sample_ancestral"):
+                L.pllhip_eval_sample_ancestral.restype = C.POINTER(SampledAncestralResult)
+                L.pllhip_eval_sample_ancestral.argtypes = [C.c_void_p, C.POINTER(AncSampleParams)]
+                L.pllhip_eval_destroy_sampled_ancestral.restype = None
+                L.pllhip_eval_destroy_sampled_ancestral.argtypes = [C.POINTER(SampledAncestralResult)]
             if hasattr(L, "pllhip_eval_substitution_map"):
                 L.pllhip_substmap_counts.argtypes = [C.c_uint, C.c_uint, c_double_p, c_double_p, c_double_p, C.c_double,
                                                      c_double_p, c_double_p, c_double_p]
@@ -693,6 +722,14 @@ class PllLib:
             L.pllhip_simulate_utree.argtypes = [pp, C.POINTER(SimParams), up, c_uint_p, C.c_int, ubyte_p]
             L.pllhip_simulate_last_times.restype = None
             L.pllhip_simulate_last_times.argtypes = [c_double_p, c_double_p, c_double_p, C.POINTER(C.c_ulonglong)]
+        if hasattr(L, "pllhip_sample_ancestral_edges"):
+            ubyte_p, ull_p = C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong)
+            L.pllhip_sample_ancestral_edges.argtypes = [pp, C.POINTER(AncSampleParams), C.c_uint, C.c_int, C.c_uint, C.c_int,
+                                                        C.c_uint, c_uint_p, c_uint_p, c_uint_p, c_uint_p, C.c_uint,
+                                                        ubyte_p, ubyte_p, ull_p]
+            L.pllhip_sample_ancestral_utree.argtypes = [pp, C.POINTER(AncSampleParams), up, c_uint_p, ubyte_p, ubyte_p, ull_p]
+            L.pllhip_ancsample_last_times.restype = None
+            L.pllhip_ancsample_last_times.argtypes = [c_double_p, c_double_p, c_double_p, ull_p]
         if hasattr(L, "pllhip_msa_compute_stats"):
             L.pllhip_empirical_frequencies.restype = c_double_p
             L.pllhip_empirical_frequencies.argtypes = [pp]
@@ -2015,6 +2052,57 @@ def simulate_last_times(lib):
     return a.value, b.value, c.value, n.value
 
 
+def _ancs_params(seed, replicates, first_replicate, flags, alphabet):
+    a = None if alphabet is None else (alphabet if isinstance(alphabet, bytes) else alphabet.encode())
+    return AncSampleParams(seed, first_replicate, replicates, flags, a)
+
+
+def sample_ancestral_edges(inst, root_edge, parent, child, matrix, seed, replicates=1, first_replicate=0, flags=0,
+                           alphabet=None, node_count=None, freqs_indices=None, out=None, component=None):
+    """pllhip_sample_ancestral_edges on an Instance whose vectors point towards root_edge = (root node, root scaler,
+    other node, other scaler): (out uint8 [replicates][node_count][sites], component [replicates][sites], dropped);
+    raises RuntimeError with the library's message.  `out`, `component`: the arrays to fill (left as they are on
+    failure)."""
+    pa, ch, mi = _u32(parent), _u32(child), _u32(matrix)
+    nodes = inst.tips + inst.p.contents.clv_buffers if node_count is None else node_count
+    if out is None:
+        out = np.zeros((replicates, nodes, inst.N), dtype=np.uint8)
+    if component is None:
+        component = np.zeros((replicates, inst.N), dtype=np.uint8)
+    prm = _ancs_params(seed, replicates, first_replicate, flags, alphabet)
+    idx = inst.params if freqs_indices is None else _u32(freqs_indices)
+    dropped = C.c_ulonglong(0)
+    ubyte_p = C.POINTER(C.c_ubyte)
+    rn, rs, on, os_ = root_edge
+    if not inst.L.pllhip_sample_ancestral_edges(inst.p, C.byref(prm), rn, rs, on, os_, len(pa), pa.ctypes.data_as(c_uint_p),
+                                                ch.ctypes.data_as(c_uint_p), mi.ctypes.data_as(c_uint_p),
+                                                idx.ctypes.data_as(c_uint_p), nodes, out.ctypes.data_as(ubyte_p),
+                                                component.ctypes.data_as(ubyte_p), C.byref(dropped)):
+        raise RuntimeError(inst.lib.errmsg)
+    return out, component, dropped.value
+
+
+def sample_ancestral_utree(inst, root, seed, replicates=1, first_replicate=0, flags=0, alphabet=None):
+    """pllhip_sample_ancestral_utree from `root` (a POINTER(UNode) at an inner node)"""
+    nodes = inst.tips + inst.p.contents.clv_buffers
+    out = np.zeros((replicates, nodes, inst.N), dtype=np.uint8)
+    component = np.zeros((replicates, inst.N), dtype=np.uint8)
+    prm = _ancs_params(seed, replicates, first_replicate, flags, alphabet)
+    dropped = C.c_ulonglong(0)
+    ubyte_p = C.POINTER(C.c_ubyte)
+    if not inst.L.pllhip_sample_ancestral_utree(inst.p, C.byref(prm), root, inst.params_p, out.ctypes.data_as(ubyte_p),
+                                                component.ctypes.data_as(ubyte_p), C.byref(dropped)):
+        raise RuntimeError(inst.lib.errmsg)
+    return out, component, dropped.value
+
+
+def ancsample_last_times(lib):
+    """(table_ms, kernel_ms, copy_ms, chunks) of this thread's last pllhip_sample_ancestral_edges"""
+    a, b, c, n = C.c_double(0), C.c_double(0), C.c_double(0), C.c_ulonglong(0)
+    lib.lib.pllhip_ancsample_last_times(C.byref(a), C.byref(b), C.byref(c), C.byref(n))
+    return a.value, b.value, c.value, n.value
+
+
 def state_charmap(nstates):
     """a 256-entry char -> mask map where byte value 48+i ('0'+i) means state i and
     '-' means every state (so uint8 state arrays + 48 are valid sequences)"""
@@ -2202,6 +2290,28 @@ class Evaluation:
             return out
         finally:
             self.L.pllhip_eval_destroy_site_rates(arr)
+
+    def sample_ancestral(self, seed, replicates=1, first_replicate=0, flags=0, alphabet=None):
+        """pllhip_eval_sample_ancestral -> [SampledAncestral per local partition] (numpy copies)"""
+        self.lib.errno = 0
+        prm = _ancs_params(seed, replicates, first_replicate, flags, alphabet)
+        ptr = self.L.pllhip_eval_sample_ancestral(self.ev, C.byref(prm))
+        if not ptr:
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        try:
+            res, out = ptr.contents, []
+            rows, reps = res.node_count, res.replicates
+            for k in range(res.partition_count):
+                o, N = SampledAncestral(), res.sites[k]
+                o.partition = res.partition_indices[k]
+                o.clv_index = np.array([res.clv_index[i] for i in range(rows)], dtype=np.uint32)
+                o.out = np.ctypeslib.as_array(res.out[k], shape=(reps, rows, N)).copy() if N else np.zeros((reps, rows, 0), np.uint8)
+                o.component = np.ctypeslib.as_array(res.component[k], shape=(reps, N)).copy() if N else np.zeros((reps, 0), np.uint8)
+                o.dropped = res.dropped[k]
+                out.append(o)
+            return out
+        finally:
+            self.L.pllhip_eval_destroy_sampled_ancestral(ptr)
 
     def substitution_map(self, flags=0):
         """pllhip_eval_substitution_map -> [[BranchSubst per branch, by pmatrix_index] per local partition]"""
