@@ -866,6 +866,56 @@ PLL_EXPORT int pllhip_sample_ancestral_utree(pll_partition_t * partition, const 
 PLL_EXPORT void pllhip_ancsample_last_times(double * table_ms, double * kernel_ms, double * copy_ms,
                                             unsigned long long * chunks);
 
+/* ---- sampled substitution histories ("Sampled substitution histories") ----
+ * Stochastic mapping: after the ancestral draw above, a path of substitutions along every edge, drawn by
+ * uniformization conditioned on the sampled component and the sampled states at both ends of the edge -- a jump count
+ * from the Poisson table of (matrix, category) weighted by Rpow[k][a][c], a chain of states through the uniformized
+ * matrix R, and event times from the order statistics of 32-bit draws.  The tables come from the host stage
+ * (include/pllhip_eval.h, pllhip_history_*), built from branch_lengths[edge] -- the lengths the caller promises the
+ * matrices were made from -- and the model of params_indices[category].  Draws are those of the simulation contract on
+ * the streams 0x40000000 + (matrix << 11) + i (i = 0: jump count, 1 .. 1023: chain steps) and + 1024 + i (event
+ * times).  Every accumulated number is a 64-bit integer, so all outputs are a function of (seed, replicate, pattern,
+ * the doubles the engine holds and the tables, the edge list with its matrix indices and lengths) alone.
+ * counts[replicate][edge][states][states]: pattern-weighted number of a -> b substitutions.
+ * units[replicate][edge][cats][states]: pattern-weighted time in a state under category r, in units of 2^-32 tau_r
+ *   (two's complement; every final cell is >= 0).  pllhip_history_summary turns both into doubles.
+ * changes[replicate][edge][sites] (with PLLHIP_HIST_SITES, else ignored): substitutions of the site on the edge,
+ *   saturating at 254; 0xFF: the site, or this edge of it, was dropped.
+ * dropped_edges[replicate][edge]: sites with a pattern weight whose jump-count table had no mass (the sampled ends
+ *   cannot be joined within the table), which add nothing.  Edges are in the order of the caller's list.
+ * out, component (either may be NULL) hold what pllhip_sample_ancestral_edges returns for the same seed and flags.
+ * PLL_ERROR_PARAM_INVALID with nothing written: whatever pllhip_sample_ancestral_edges refuses, a NULL, negative or
+ * non-finite length, a Poisson table of more than 1024 entries (mu tau of roughly 760 and more), a matrix index of 2^19
+ * or more, pattern weights that add up to 2^31 or more, unknown flags.  The partition is left as it was.
+ * Environment, read at the call, none of which shows in the results: PLLHIP_HIST_BLOCKS (workgroups of the history
+ * kernel, 0: no cap), PLLHIP_HIST_REPLICATES (replicates per staging chunk, 0: no cap), and the PLLHIP_ANCS_* above. */
+#define PLLHIP_HIST_SITES (1u << 8)       /* fill `changes` */
+#define PLLHIP_HIST_MAX_TABLE 1024u       /* entries of a Poisson table, at most */
+
+PLL_EXPORT int pllhip_sample_histories_edges(pll_partition_t * partition, const pllhip_ancsample_params_t * params,
+                                             unsigned int root_node, int root_scaler, unsigned int other_node,
+                                             int other_scaler, unsigned int edge_count, const unsigned int * parent,
+                                             const unsigned int * child, const unsigned int * matrix_indices,
+                                             const unsigned int * freqs_indices, unsigned int node_count,
+                                             const unsigned int * params_indices, const double * branch_lengths,
+                                             unsigned char * out, unsigned char * component,
+                                             unsigned long long * dropped, unsigned long long * counts,
+                                             unsigned long long * units, unsigned char * changes,
+                                             unsigned long long * dropped_edges);
+/* The same for a tree walked from `root`: the edge list of pllhip_sample_ancestral_utree in its order, which is the
+   order of counts, units, changes and dropped_edges (*edge_count receives its length and edge_matrix[tips +
+   clv_buffers] the pmatrix_index of every edge; either may be NULL), lengths from node->length. */
+PLL_EXPORT int pllhip_sample_histories_utree(pll_partition_t * partition, const pllhip_ancsample_params_t * params,
+                                             const pll_unode_t * root, const unsigned int * freqs_indices,
+                                             const unsigned int * params_indices, unsigned char * out,
+                                             unsigned char * component, unsigned long long * dropped,
+                                             unsigned long long * counts, unsigned long long * units,
+                                             unsigned char * changes, unsigned long long * dropped_edges,
+                                             unsigned int * edge_count, unsigned int * edge_matrix);
+/* this thread's last call: device time of the site-category table, of the walk kernels and of the history kernels in
+   ms between HIP events, and the copies in ms */
+PLL_EXPORT void pllhip_history_last_times(double * table_ms, double * walk_ms, double * history_ms, double * copy_ms);
+
 /* ---- topology tests and bootstrap weights ("Topology tests and bootstrap weights"; DESIGN.md
  *      section 20) ----
  * A site-likelihood set holds, on the device pllhip_get_device() names at its creation, a matrix L[trees][patterns]

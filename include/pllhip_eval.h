@@ -362,6 +362,62 @@ PLL_EXPORT pllhip_sampled_ancestral_t * pllhip_eval_sample_ancestral(pllhip_eval
                                                                      const pllhip_ancsample_params_t * params);
 PLL_EXPORT void pllhip_eval_destroy_sampled_ancestral(pllhip_sampled_ancestral_t * sa);
 
+/* ---------------------------------------------------------------------------
+ * Sampled substitution histories (include/pllhip.h, "sampled substitution histories"; the process: INTEGRATION.md):
+ * stochastic mapping by uniformization, conditioned on the sampled component and states at both ends of every branch.
+ *
+ * The host stage is pure C, no device:
+ * pllhip_history_rate_table: from the eigen system in libpll's storage (V = inv_eigenvecs, V^-1 = eigenvecs, both
+ *   [states][states_padded]) Q[a][b] = sum_k V[a][k] lambda_k V^-1[k][b] (a != b, negative values clamped to 0),
+ *   Q[a][a] = -sum_(b != a) Q[a][b], *mu = max_a -Q[a][a], R = I + Q / mu (diagonal 1 - sum of the row's others, clamped
+ *   at 0; mu = 0: R = I) and Rpow[k] = Rpow[k - 1] R, Rpow[0] = I, k < K, each [states][states] row-major, a plain
+ *   triple loop.  Rpow[1] is R.  PLL_FAILURE for K = 0 or without memory.
+ * pllhip_history_poisson: pois[k] = exp(k log lambda - lambda - lgamma(k + 1)) (lambda = 0: pois[0] = 1) for k < *K,
+ *   *K the first k > lambda with pois[k] < 2^-70 sum_(i<k) pois[i].  PLL_FAILURE (pll_errno PLL_ERROR_PARAM_INVALID)
+ *   where lambda is negative or not finite or the table would need more than PLLHIP_HIST_MAX_TABLE entries.
+ * pllhip_history_summary: counts as doubles, dwell[c] = sum_r (tau[r] 2^-32) units[r][c] with r ascending (rate-scaled
+ *   time, as in the substitution map; units are two's complement), *total = sum counts.
+ *
+ * pllhip_eval_sample_histories evaluates the tree as pllhip_eval_sample_ancestral does, draws the ancestral states and
+ * then a history on every branch, for every local partition with its own params_indices, the driver's own branch
+ * lengths and linkage mode.  params->flags: PLLHIP_ANCS_* and PLLHIP_HIST_SITES.  Branches are indexed by
+ * pmatrix_index.  The root, the branch lengths, the vectors and the log-likelihood are afterwards what they were.  On
+ * the HIP engine the draw is pllhip_sample_histories_edges; where the library has no such call (the CPU oracle) the
+ * driver runs the same contract in plain C.  NULL on error (pll_errno set): what pllhip_eval_sample_ancestral refuses,
+ * a Poisson table beyond the cap, pattern weights that add up to 2^31 or more, 2^19 or more branches.
+ * ------------------------------------------------------------------------- */
+PLL_EXPORT int pllhip_history_rate_table(unsigned int states, unsigned int states_padded, const double * eigenvecs,
+                                         const double * inv_eigenvecs, const double * eigenvals, unsigned int K,
+                                         double * mu, double * Rpow);
+PLL_EXPORT int pllhip_history_poisson(double lambda, double * pois, unsigned int * K);
+PLL_EXPORT int pllhip_history_summary(unsigned int states, unsigned int cats, const double * tau,
+                                      const unsigned long long * counts_int, const unsigned long long * units,
+                                      double * counts, double * dwell, double * total);
+
+typedef struct pllhip_sampled_histories
+{
+  unsigned int partition_count;          /* local partitions */
+  unsigned int node_count;               /* rows per replicate of `out` */
+  unsigned int replicates;
+  unsigned int branch_count;
+  unsigned int * partition_indices;      /* [partition_count] */
+  unsigned int * sites, * states, * cats;/* [partition_count] */
+  unsigned int * clv_index;              /* [node_count]: the clv_index of every row */
+  unsigned char ** out;                  /* [partition_count][replicate][node_count][sites], as pllhip_sampled_ancestral_t */
+  unsigned char ** component;            /* [partition_count][replicate][sites] */
+  unsigned long long * dropped;          /* [partition_count]: dropped sites */
+  unsigned long long ** counts;          /* [partition_count][replicate][branch][states][states] */
+  unsigned long long ** units;           /* [partition_count][replicate][branch][cats][states] */
+  double ** dwell;                       /* [partition_count][replicate][branch][states] */
+  double ** total;                       /* [partition_count][replicate][branch] */
+  unsigned long long ** dropped_edges;   /* [partition_count][replicate][branch] */
+  unsigned char ** changes;              /* [partition_count][replicate][branch][sites]; NULL without PLLHIP_HIST_SITES */
+} pllhip_sampled_histories_t;
+
+PLL_EXPORT pllhip_sampled_histories_t * pllhip_eval_sample_histories(pllhip_eval_t * ev,
+                                                                     const pllhip_ancsample_params_t * params);
+PLL_EXPORT void pllhip_eval_destroy_sampled_histories(pllhip_sampled_histories_t * sh);
+
 PLL_EXPORT unsigned long pllhip_eval_ops(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_pmatrix_updates(const pllhip_eval_t * ev);
 PLL_EXPORT unsigned long pllhip_eval_derivative_calls(const pllhip_eval_t * ev);   /* sumtable scans */

@@ -204,6 +204,38 @@ bool ancsample_operands(pll_partition_t * p, const unsigned * freqs_indices, con
                         AncsOperands & ops, AncsVector * views);
 bool ancsample_walk(pll_partition_t * p, const AncsOperands & ops, const AncsLaunch & launch, unsigned grid);
 
+// A stage between the walk and the copy of every staging half (pll_ancsample_dev.hip, ancsample_run; used by
+// pll_history_dev.hip).  The half holds [replicate][rows][pitch] bytes: state indices in the rows of all nodes, tips
+// included, the component in comp_row, and extra_rows rows of the hook's own from extra_row on, 0xFF before the walk.
+// prepare runs once inside the job, after the arguments passed every check and before the first launch; launch
+// enqueues on the job's stream; deliver sees the pinned copy of a half; finish runs after the last delivery.
+struct DeviceJob;
+struct AncsStaged
+{
+  uint8_t * half = nullptr;                            // on the device for launch, pinned for deliver
+  unsigned rep0 = 0, reps = 0, col0 = 0, cols = 0;     // replicates and patterns of the chunk
+  unsigned rows = 0, comp_row = 0, extra_row = 0;
+  size_t pitch = 0;
+};
+struct AncsStageHook
+{
+  unsigned flags = 0;                                  // flags of the caller's that are the hook's
+  unsigned extra_rows = 0;
+  unsigned long long chunk_replicates = 0;             // replicates per staging chunk, at most (0: no cap)
+  virtual bool prepare(DeviceJob & j, unsigned cu_count, const unsigned * d_pattern_weights) = 0;
+  virtual bool launch(DeviceJob & j, const AncsStaged & s) = 0;
+  virtual void deliver(const AncsStaged & s) = 0;
+  virtual bool finish(DeviceJob & j) = 0;
+  virtual ~AncsStageHook() = default;
+};
+// times_ms (with a hook): table, walk, hook, copy
+int ancsample_run(const char * who, pll_partition_t * partition, const pllhip_ancsample_params_t * params,
+                  unsigned int root_node, int root_scaler, unsigned int other_node, int other_scaler,
+                  unsigned int edge_count, const unsigned int * parent, const unsigned int * child,
+                  const unsigned int * matrix_indices, const unsigned int * freqs_indices, unsigned int node_count,
+                  unsigned char * out, unsigned char * component, unsigned long long * dropped, AncsStageHook * hook,
+                  double * times_ms);
+
 // category weights a site-category or pair table can be made under: finite, non-negative, not all zero
 inline bool check_category_weights(const double * w, unsigned R, const char * who)
 {

@@ -6,6 +6,7 @@
  */
 #include "pllhip_eval_internal.h"
 #include "pllhip.h"
+#include "pllhip_history.h"
 #pragma weak pllhip_eval_attach_comm   /* HIP engine only (pllhip_comm.hip) */
 #pragma weak pllhip_newton_branch      /* HIP engine only (pll_core.hip) */
 #pragma weak pllhip_newton_branch_multi
@@ -22,6 +23,7 @@
 #pragma weak pllhip_substmap_edge         /* HIP engine only: with the CPU oracle the driver computes the pair table itself */
 #pragma weak pllhip_edge_pairs_destroy
 #pragma weak pllhip_sample_ancestral_edges   /* HIP engine only: with the CPU oracle the driver walks the tree itself */
+#pragma weak pllhip_sample_histories_edges   /* HIP engine only: with the CPU oracle the driver samples the paths itself */
 #include <stdarg.h>
 
 static __thread pllhip_eval_t * cb_self;   /* pll_utree_traverse callbacks carry no user pointer */
@@ -1968,7 +1970,7 @@ static int as_host(const pll_partition_t * part, const pllhip_ancsample_params_t
 /* the edges of the tree seen from the inner record `root`, parents first and root -> root->back first; 0: out of
    memory.  (The walk of pllhip_simulate_utree.) */
 static int as_edges(const pllhip_eval_t * ev, const pll_unode_t * root, unsigned int ** parent, unsigned int ** child,
-                    unsigned int ** matrix, unsigned int * count)
+                    unsigned int ** matrix, unsigned int * count, double * length)
 {
   const size_t cap = (size_t)ev->edges + 1;
   const pll_unode_t ** stack = (const pll_unode_t **)malloc((cap + 1) * sizeof(pll_unode_t *));
@@ -1995,6 +1997,7 @@ static int as_edges(const pllhip_eval_t * ev, const pll_unode_t * root, unsigned
       (*parent)[*count] = n->clv_index;
       (*child)[*count] = n->back->clv_index;
       (*matrix)[*count] = n->pmatrix_index;
+      if (length) length[*count] = n->length;           /* [edges + 1], the tree's own lengths */
       ++*count;
       stack[top++] = n->back;
       n = n->next;
@@ -2018,6 +2021,45 @@ void pllhip_eval_destroy_sampled_ancestral(pllhip_sampled_ancestral_t * sa)
   free(sa);
 }
 
+/* what both sampling calls do first: the root edge from its inner end, the checks of every local partition, and a full
+   evaluation at the current root that stores every vector.  0: refused or failed (pll_errno set) */
+static int as_begin(pllhip_eval_t * ev, const pllhip_ancsample_params_t * params, const pll_unode_t ** root_out,
+                    unsigned int * rows_out, unsigned int * local_out)
+{
+  const pll_unode_t * root;
+  unsigned int p, rows = 0, local = 0;
+  root = ev->root->next ? ev->root : ev->root->back;         /* the same edge from its inner end */
+  if (!root->next)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the root edge joins two tips");
+    return 0;
+  }
+  for (p = 0; p < ev->nparts; ++p)
+    if (ev->parts[p])
+    {
+      if (!as_check(ev->parts[p], p, params, ev->params[p])) return 0;
+      if (ev->parts[p]->tips + ev->parts[p]->clv_buffers > rows) rows = ev->parts[p]->tips + ev->parts[p]->clv_buffers;
+      ++local;
+    }
+  if (!local)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: no local partition");
+    return 0;
+  }
+  /* a full evaluation at the current root that stores every vector: evaluate-only mode is off for it, and the next
+     full evaluation decides anew */
+  pllhip_eval_invalidate_all(ev);
+  if (ev->transient != PLLHIP_EVAL_TRANSIENT_OFF) partitions_transient(ev, 0, 1);
+  ev->last_was_full = 0;
+  if (!update_vectors(ev, 0))
+  {
+    if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the traversal failed");
+    return 0;
+  }
+  *root_out = root; *rows_out = rows; *local_out = local;
+  return 1;
+}
+
 pllhip_sampled_ancestral_t * pllhip_eval_sample_ancestral(pllhip_eval_t * ev, const pllhip_ancsample_params_t * params)
 {
   const int device = pllhip_sample_ancestral_edges != NULL;
@@ -2033,36 +2075,9 @@ pllhip_sampled_ancestral_t * pllhip_eval_sample_ancestral(pllhip_eval_t * ev, co
                       "flags or a replicate number of 2^32 or more");
     return NULL;
   }
-  root = ev->root->next ? ev->root : ev->root->back;         /* the same edge from its inner end */
-  if (!root->next)
-  {
-    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the root edge joins two tips");
-    return NULL;
-  }
-  for (p = 0; p < ev->nparts; ++p)
-    if (ev->parts[p])
-    {
-      if (!as_check(ev->parts[p], p, params, ev->params[p])) return NULL;
-      if (ev->parts[p]->tips + ev->parts[p]->clv_buffers > rows) rows = ev->parts[p]->tips + ev->parts[p]->clv_buffers;
-      ++local;
-    }
-  if (!local)
-  {
-    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: no local partition");
-    return NULL;
-  }
-  /* a full evaluation at the current root that stores every vector: evaluate-only mode is off for it, and the next
-     full evaluation decides anew */
-  pllhip_eval_invalidate_all(ev);
-  if (ev->transient != PLLHIP_EVAL_TRANSIENT_OFF) partitions_transient(ev, 0, 1);
-  ev->last_was_full = 0;
-  if (!update_vectors(ev, 0))
-  {
-    if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the traversal failed");
-    return NULL;
-  }
+  if (!as_begin(ev, params, &root, &rows, &local)) return NULL;
   sa = (pllhip_sampled_ancestral_t *)calloc(1, sizeof(*sa));
-  if (!sa || !as_edges(ev, root, &parent, &child, &matrix, &count)) goto nomem;
+  if (!sa || !as_edges(ev, root, &parent, &child, &matrix, &count, NULL)) goto nomem;
   sa->partition_count = local;
   sa->node_count = rows;
   sa->replicates = params->replicates;
@@ -2123,6 +2138,539 @@ fail:
   if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled ancestral states: the call failed");
   free(parent); free(child); free(matrix);
   pllhip_eval_destroy_sampled_ancestral(sa);
+  return NULL;
+}
+
+/* ---------------------------------------------------------------------- */
+/* Sampled substitution histories: stochastic mapping by uniformization,    */
+/* conditioned on the sampled ends of every branch (include/pllhip.h,       */
+/* "sampled substitution histories"; the process: INTEGRATION.md)           */
+/* ---------------------------------------------------------------------- */
+
+int pllhip_history_rate_table(unsigned int states, unsigned int states_padded, const double * eigenvecs,
+                              const double * inv_eigenvecs, const double * eigenvals, unsigned int K, double * mu,
+                              double * Rpow)
+{
+  const size_t S = states, Sp = states_padded, SS = S * S;
+  const double * W = eigenvecs, * V = inv_eigenvecs;
+  double * Q, * R, m = 0.0;
+  size_t a, b, d, k;
+  if (!states || !K || !eigenvecs || !inv_eigenvecs || !eigenvals || !mu || !Rpow)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "pllhip_history_rate_table: a NULL argument, no states or K = 0");
+    return PLL_FAILURE;
+  }
+  Q = (double *)calloc(2 * SS, sizeof(double));
+  if (!Q)
+  {
+    pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the rate table");
+    return PLL_FAILURE;
+  }
+  R = Q + SS;
+  for (a = 0; a < S; ++a)
+  {
+    double sum = 0.0;
+    for (b = 0; b < S; ++b)
+    {
+      double q = 0.0;
+      if (b == a) continue;
+      for (k = 0; k < S; ++k) q += V[a * Sp + k] * eigenvals[k] * W[k * Sp + b];
+      Q[a * S + b] = q > 0.0 ? q : 0.0;
+      sum = sum + Q[a * S + b];
+    }
+    Q[a * S + a] = -sum;
+    if (sum > m) m = sum;
+  }
+  *mu = m;
+  for (a = 0; a < S; ++a)
+  {
+    double off = 0.0;
+    if (!(m > 0.0)) { R[a * S + a] = 1.0; continue; }
+    for (b = 0; b < S; ++b)
+    {
+      if (b == a) continue;
+      R[a * S + b] = Q[a * S + b] / m;
+      off = off + R[a * S + b];
+    }
+    R[a * S + a] = 1.0 - off > 0.0 ? 1.0 - off : 0.0;
+  }
+  memset(Rpow, 0, sizeof(double) * SS);
+  for (a = 0; a < S; ++a) Rpow[a * S + a] = 1.0;
+  for (k = 1; k < K; ++k)
+  {
+    const double * prev = Rpow + (k - 1) * SS;
+    double * next = Rpow + k * SS;
+    for (a = 0; a < S; ++a)
+      for (b = 0; b < S; ++b)
+      {
+        double acc = 0.0;
+        for (d = 0; d < S; ++d) acc = acc + prev[a * S + d] * R[d * S + b];
+        next[a * S + b] = acc;
+      }
+  }
+  free(Q);
+  return PLL_SUCCESS;
+}
+
+int pllhip_history_poisson(double lambda, double * pois, unsigned int * K)
+{
+  double loglam, sum = 0.0;
+  unsigned int k;
+  if (!pois || !K || !(lambda >= 0.0) || !isfinite(lambda))
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "pllhip_history_poisson: a NULL argument, or lambda negative or not finite");
+    return PLL_FAILURE;
+  }
+  if (lambda == 0.0)
+  {
+    pois[0] = 1.0;
+    *K = 1;
+    return PLL_SUCCESS;
+  }
+  loglam = log(lambda);
+  for (k = 0; k <= PLLHIP_HIST_MAX_TABLE; ++k)
+  {
+    const double p = exp((double)k * loglam - lambda - lgamma((double)k + 1.0));
+    if ((double)k > lambda && p < 0x1.0p-70 * sum)
+    {
+      *K = k;
+      return PLL_SUCCESS;
+    }
+    if (k == PLLHIP_HIST_MAX_TABLE) break;
+    pois[k] = p;
+    sum = sum + p;
+  }
+  pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "pllhip_history_poisson: lambda = %g needs more than %u entries", lambda,
+                    PLLHIP_HIST_MAX_TABLE);
+  return PLL_FAILURE;
+}
+
+int pllhip_history_summary(unsigned int states, unsigned int cats, const double * tau,
+                           const unsigned long long * counts_int, const unsigned long long * units, double * counts,
+                           double * dwell, double * total)
+{
+  const size_t S = states;
+  size_t x, r;
+  double sum = 0.0;
+  if (!tau || !counts_int || !units || !counts || !dwell || !total)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "pllhip_history_summary: a NULL argument");
+    return PLL_FAILURE;
+  }
+  for (x = 0; x < S * S; ++x)
+  {
+    counts[x] = (double)counts_int[x];
+    sum += counts[x];
+  }
+  for (x = 0; x < S; ++x)
+  {
+    double d = 0.0;
+    for (r = 0; r < cats; ++r) d = d + (tau[r] * 0x1.0p-32) * (double)(long long)units[r * S + x];
+    dwell[x] = d;
+  }
+  *total = sum;
+  return PLL_SUCCESS;
+}
+
+void pllhip_history_tables_destroy(pllhip_history_tables_t * t)
+{
+  if (!t) return;
+  free(t->slot); free(t->mu); free(t->rpow); free(t->tau); free(t->len); free(t->off); free(t->pois);
+  free(t);
+}
+
+pllhip_history_tables_t * pllhip_history_tables_create(const pll_partition_t * part, unsigned int edge_count,
+                                                       const unsigned int * matrix_indices,
+                                                       const unsigned int * params_indices,
+                                                       const double * branch_lengths, const char * who)
+{
+  pllhip_history_tables_t * t;
+  unsigned int S, R, e, r, s, * rm = NULL;
+  unsigned long long wsum = 0, cap = 0;
+  double tmp[PLLHIP_HIST_MAX_TABLE], * one = NULL;
+  size_t n;
+  if (!part || !params_indices || (edge_count && (!matrix_indices || !branch_lengths)))
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "%s: the partition, params_indices, the edge list or the branch lengths "
+                      "are NULL", who);
+    return NULL;
+  }
+  S = part->states; R = part->rate_cats;
+  for (n = 0; n < part->sites; ++n) wsum += part->pattern_weights[n];
+  if (wsum >= (1ULL << 31))
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "%s: the pattern weights add up to %llu, 2^31 or more", who, wsum);
+    return NULL;
+  }
+  for (r = 0; r < R; ++r)
+  {
+    if (params_indices[r] >= part->rate_matrices)
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "%s: parameter index %u of category %u out of range (%u rate matrices)",
+                        who, params_indices[r], r, part->rate_matrices);
+      return NULL;
+    }
+    if (!part->eigen_decomp_valid[params_indices[r]])
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "%s: the eigen system of rate matrix %u is not valid: no matrix can "
+                        "have been made from it", who, params_indices[r]);
+      return NULL;
+    }
+  }
+  for (e = 0; e < edge_count; ++e)
+  {
+    if (matrix_indices[e] >= PLLHIP_HIST_MAX_MATRIX)
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "%s: matrix index %u of edge %u is 2^19 or more", who,
+                        matrix_indices[e], e);
+      return NULL;
+    }
+    if (!(branch_lengths[e] >= 0.0) || !isfinite(branch_lengths[e]))
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "%s: the length of edge %u is negative or not finite", who, e);
+      return NULL;
+    }
+  }
+  t = (pllhip_history_tables_t *)calloc(1, sizeof(*t));
+  rm = (unsigned int *)calloc(R ? R : 1, sizeof(unsigned int));
+  one = (double *)calloc((size_t)S * S + 1, sizeof(double));
+  if (!t || !rm || !one) goto nomem;
+  t->states = S; t->cats = R; t->edge_count = edge_count;
+  t->kmax = 2;
+  t->slot = (unsigned int *)calloc(R ? R : 1, sizeof(unsigned int));
+  t->mu = (double *)calloc(R ? R : 1, sizeof(double));
+  t->tau = (double *)calloc((size_t)edge_count * R + 1, sizeof(double));
+  t->len = (unsigned int *)calloc((size_t)edge_count * R + 1, sizeof(unsigned int));
+  t->off = (unsigned long long *)calloc((size_t)edge_count * R + 1, sizeof(unsigned long long));
+  if (!t->slot || !t->mu || !t->tau || !t->len || !t->off) goto nomem;
+  /* the distinct rate matrices and their mu */
+  for (r = 0; r < R; ++r)
+  {
+    const unsigned int i = params_indices[r];
+    for (s = 0; s < t->nmat && rm[s] != i; ++s) ;
+    t->slot[r] = s;
+    if (s < t->nmat) continue;
+    rm[t->nmat++] = i;
+    if (!pllhip_history_rate_table(S, part->states_padded, part->eigenvecs[i], part->inv_eigenvecs[i],
+                                   part->eigenvals[i], 1, &t->mu[s], one)) goto fail;
+  }
+  /* the Poisson table of every (edge, category) */
+  for (e = 0; e < edge_count; ++e)
+    for (r = 0; r < R; ++r)
+    {
+      const double tau = part->rates[r] * branch_lengths[e] / (1.0 - part->prop_invar[params_indices[r]]);
+      const double lambda = t->mu[t->slot[r]] * tau;
+      unsigned int K = 0;
+      if (!(lambda >= 0.0) || !isfinite(lambda) || !pllhip_history_poisson(lambda, tmp, &K))
+      {
+        pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "%s: edge %u (matrix %u), category %u: mu tau = %g needs a table of "
+                          "more than %u entries", who, e, matrix_indices[e], r, lambda, PLLHIP_HIST_MAX_TABLE);
+        goto fail;
+      }
+      if (t->pois_count + K > cap)
+      {
+        double * grown;
+        cap = 2 * cap + K + 1024;
+        grown = (double *)realloc(t->pois, (size_t)cap * sizeof(double));
+        if (!grown) goto nomem;
+        t->pois = grown;
+      }
+      memcpy(t->pois + t->pois_count, tmp, sizeof(double) * K);
+      t->tau[(size_t)e * R + r] = tau;
+      t->len[(size_t)e * R + r] = K;
+      t->off[(size_t)e * R + r] = t->pois_count;
+      t->pois_count += K;
+      if (K > t->kmax) t->kmax = K;
+    }
+  t->rpow = (double *)calloc((size_t)(t->nmat ? t->nmat : 1) * t->kmax * S * S, sizeof(double));
+  if (!t->rpow) goto nomem;
+  for (s = 0; s < t->nmat; ++s)
+    if (!pllhip_history_rate_table(S, part->states_padded, part->eigenvecs[rm[s]], part->inv_eigenvecs[rm[s]],
+                                   part->eigenvals[rm[s]], t->kmax, &t->mu[s], t->rpow + (size_t)s * t->kmax * S * S))
+      goto fail;
+  free(rm); free(one);
+  return t;
+nomem:
+  pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "%s: cannot allocate the history tables", who);
+fail:
+  free(rm); free(one);
+  pllhip_history_tables_destroy(t);
+  return NULL;
+}
+
+static int hs_cmp(const void * a, const void * b)
+{
+  const unsigned long long x = *(const unsigned long long *)a, y = *(const unsigned long long *)b;
+  return x < y ? -1 : x > y;
+}
+
+/* One site of one edge in one replicate, in plain C: the second implementation of k_history_edges.  a, c: the sampled
+   states at the parent and the child, r the sampled category.  cum holds max(kmax, states) doubles, key 1023 words.
+   Returns the number of real jumps, or -1 for a dropped edge (nothing added). */
+static int hs_site(const pllhip_history_tables_t * T, unsigned long long seed, unsigned long long rep, unsigned int m,
+                   unsigned int e, unsigned long long n, unsigned int r, unsigned int a, unsigned int c,
+                   unsigned long long w, unsigned long long * counts, unsigned long long * units, double * cum,
+                   unsigned long long * key)
+{
+  const size_t S = T->states, SS = S * S;
+  const unsigned int K = T->len[(size_t)e * T->cats + r], base = PLLHIP_HIST_STREAM + (m << 11);
+  const double * pois = T->pois + T->off[(size_t)e * T->cats + r];
+  const double * rp = T->rpow + (size_t)T->slot[r] * T->kmax * SS, * R1 = rp + SS;
+  double acc = 0.0;
+  unsigned int k, i, N, x = a;
+  int real = 0;
+  for (k = 0; k < K; ++k)
+  {
+    acc = acc + pois[k] * rp[k * SS + a * S + c];
+    cum[k] = acc;
+  }
+  if (!(acc > 0.0) || !isfinite(acc)) return -1;
+  N = as_pick(cum, K, as_u(seed, rep, base, n));
+  /* the event times in order: (T_i, i) ascending */
+  for (i = 1; i <= N; ++i) key[i - 1] = ((as_mix(as_mix(seed, (rep << 32) | (base + 1024u + i)), n) >> 32) << 10) | i;
+  qsort(key, N, sizeof(unsigned long long), hs_cmp);
+  for (i = 1; i <= N; ++i)
+  {
+    const double * to = rp + (size_t)(N - i) * SS;
+    unsigned int d, y;
+    acc = 0.0;
+    for (d = 0; d < S; ++d)
+    {
+      acc = acc + R1[x * S + d] * to[d * S + c];
+      cum[d] = acc;
+    }
+    y = as_pick(cum, (unsigned int)S, as_u(seed, rep, base + i, n));
+    if (y != x)
+    {
+      const unsigned long long t = key[i - 1] >> 10;
+      counts[x * S + y] += w;
+      units[x] += w * t;
+      units[y] -= w * t;
+      ++real;
+      x = y;
+    }
+  }
+  units[c] += w << 32;
+  return real;
+}
+
+/* every replicate, edge and site of a partition on the host, from the identity-coded rows of the ancestral draw
+   (`states`: [replicate][node_count][sites] with the tip rows, `comp`: [replicate][sites]).  0: out of memory. */
+static int hs_host(const pll_partition_t * part, const pllhip_ancsample_params_t * params,
+                   const pllhip_history_tables_t * T, unsigned int edge_count, const unsigned int * parent,
+                   const unsigned int * child, const unsigned int * matrix, unsigned int node_count,
+                   const unsigned char * states, const unsigned char * comp, unsigned long long * counts,
+                   unsigned long long * units, unsigned char * changes, unsigned long long * dropped_edges)
+{
+  const size_t S = part->states, R = part->rate_cats, N = part->sites;
+  double * cum = (double *)malloc(sizeof(double) * (T->kmax > S ? T->kmax : S));
+  unsigned long long * key = (unsigned long long *)malloc(sizeof(unsigned long long) * PLLHIP_HIST_MAX_TABLE);
+  unsigned int b, e;
+  size_t n;
+  if (!cum || !key) { free(cum); free(key); return 0; }
+  for (b = 0; b < params->replicates; ++b)
+    for (e = 0; e < edge_count; ++e)
+    {
+      const size_t be = (size_t)b * edge_count + e;
+      const unsigned char * pa = states + ((size_t)b * node_count + parent[e]) * N;
+      const unsigned char * ch = states + ((size_t)b * node_count + child[e]) * N;
+      for (n = 0; n < N; ++n)
+      {
+        const unsigned int k = comp[(size_t)b * N + n];
+        int real = 0;
+        if (k == 0xFF) continue;                        /* a dropped site: its changes byte stays 0xFF */
+        if (!(k & 0x80u) && (pa[n] >= S || ch[n] >= S)) real = -1;      /* (no such state: no mass) */
+        else if (!(k & 0x80u))
+          real = hs_site(T, params->seed, (unsigned long long)params->first_replicate + b, matrix[e], e, n, k, pa[n], ch[n],
+                         part->pattern_weights[n], counts + be * S * S, units + (be * R + k) * S, cum, key);
+        if (real < 0 && part->pattern_weights[n] > 0) ++dropped_edges[be];
+        if (changes && real >= 0) changes[be * N + n] = (unsigned char)(real > 254 ? 254 : real);
+      }
+    }
+  free(cum); free(key);
+  return 1;
+}
+
+void pllhip_eval_destroy_sampled_histories(pllhip_sampled_histories_t * sh)
+{
+  unsigned int k;
+  if (!sh) return;
+  for (k = 0; k < sh->partition_count; ++k)
+  {
+    if (sh->out) free(sh->out[k]);
+    if (sh->component) free(sh->component[k]);
+    if (sh->counts) free(sh->counts[k]);
+    if (sh->units) free(sh->units[k]);
+    if (sh->dwell) free(sh->dwell[k]);
+    if (sh->total) free(sh->total[k]);
+    if (sh->dropped_edges) free(sh->dropped_edges[k]);
+    if (sh->changes) free(sh->changes[k]);
+  }
+  free(sh->out); free(sh->component); free(sh->counts); free(sh->units); free(sh->dwell); free(sh->total);
+  free(sh->dropped_edges); free(sh->changes);
+  free(sh->dropped); free(sh->sites); free(sh->states); free(sh->cats); free(sh->partition_indices); free(sh->clv_index);
+  free(sh);
+}
+
+pllhip_sampled_histories_t * pllhip_eval_sample_histories(pllhip_eval_t * ev, const pllhip_ancsample_params_t * params)
+{
+  const int device = pllhip_sample_histories_edges != NULL;
+  const unsigned int known = PLLHIP_ANCS_TIPS | PLLHIP_ANCS_COMPONENT | PLLHIP_HIST_SITES;
+  const pll_unode_t * root;
+  pllhip_sampled_histories_t * sh = NULL;
+  pllhip_history_tables_t * T = NULL;
+  unsigned int * parent = NULL, * child = NULL, * matrix = NULL, * sp = NULL, * sc = NULL, * smx = NULL;
+  double * length = NULL, * slen = NULL, * cd = NULL;
+  unsigned char * states = NULL;
+  unsigned int p, k = 0, local = 0, count = 0, rows = 0, i, e, E;
+  pllhip_ancsample_params_t anc;
+  int with_sites;
+  pll_errno = 0;
+  if (!params || !params->replicates || (params->flags & ~known) ||
+      (unsigned long long)params->first_replicate + params->replicates > (1ULL << 32))
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled histories: NULL parameters, zero replicates, unknown flags or a "
+                      "replicate number of 2^32 or more");
+    return NULL;
+  }
+  if (ev->edges >= PLLHIP_HIST_MAX_MATRIX)
+  {
+    pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled histories: 2^19 or more branches");
+    return NULL;
+  }
+  with_sites = (params->flags & PLLHIP_HIST_SITES) != 0;
+  anc = *params;
+  anc.flags &= ~PLLHIP_HIST_SITES;
+  if (!as_begin(ev, &anc, &root, &rows, &local)) return NULL;
+  E = ev->edges;
+  sh = (pllhip_sampled_histories_t *)calloc(1, sizeof(*sh));
+  length = (double *)calloc((size_t)E + 1, sizeof(double));
+  sp = (unsigned int *)calloc(3 * (size_t)E + 1, sizeof(unsigned int));
+  slen = (double *)calloc((size_t)E + 1, sizeof(double));
+  if (!sh || !length || !sp || !slen || !as_edges(ev, root, &parent, &child, &matrix, &count, length)) goto nomem;
+  /* the same edges by pmatrix_index: the order of the result (the draw does not depend on the order of its list) */
+  sc = sp + E; smx = sc + E;
+  for (e = 0; e < count; ++e)
+    if (count != E || matrix[e] >= E)
+    {
+      pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled histories: the tree's pmatrix indices do not number its branches");
+      goto fail;
+    }
+  for (e = 0; e < count; ++e) { sp[matrix[e]] = parent[e]; sc[matrix[e]] = child[e]; smx[matrix[e]] = matrix[e]; }
+  sh->partition_count = local;
+  sh->node_count = rows;
+  sh->replicates = params->replicates;
+  sh->branch_count = E;
+  sh->partition_indices = (unsigned int *)calloc(local, sizeof(unsigned int));
+  sh->sites = (unsigned int *)calloc(local, sizeof(unsigned int));
+  sh->states = (unsigned int *)calloc(local, sizeof(unsigned int));
+  sh->cats = (unsigned int *)calloc(local, sizeof(unsigned int));
+  sh->dropped = (unsigned long long *)calloc(local, sizeof(unsigned long long));
+  sh->out = (unsigned char **)calloc(local, sizeof(unsigned char *));
+  sh->component = (unsigned char **)calloc(local, sizeof(unsigned char *));
+  sh->counts = (unsigned long long **)calloc(local, sizeof(unsigned long long *));
+  sh->units = (unsigned long long **)calloc(local, sizeof(unsigned long long *));
+  sh->dwell = (double **)calloc(local, sizeof(double *));
+  sh->total = (double **)calloc(local, sizeof(double *));
+  sh->dropped_edges = (unsigned long long **)calloc(local, sizeof(unsigned long long *));
+  if (with_sites) sh->changes = (unsigned char **)calloc(local, sizeof(unsigned char *));
+  sh->clv_index = (unsigned int *)calloc(rows ? rows : 1, sizeof(unsigned int));
+  if (!sh->partition_indices || !sh->sites || !sh->states || !sh->cats || !sh->dropped || !sh->out || !sh->component ||
+      !sh->counts || !sh->units || !sh->dwell || !sh->total || !sh->dropped_edges || (with_sites && !sh->changes) ||
+      !sh->clv_index) goto nomem;
+  for (i = 0; i < rows; ++i) sh->clv_index[i] = i;
+  for (p = 0; p < ev->nparts; ++p)
+  {
+    pll_partition_t * part = ev->parts[p];
+    size_t cells, S, R, be;
+    int ok;
+    if (!part) continue;
+    S = part->states; R = part->rate_cats;
+    cells = (size_t)params->replicates * part->sites;
+    be = (size_t)params->replicates * E;
+    sh->partition_indices[k] = p;
+    sh->sites[k] = part->sites; sh->states[k] = part->states; sh->cats[k] = part->rate_cats;
+    sh->out[k] = (unsigned char *)malloc(cells && rows ? cells * rows : 1);
+    sh->component[k] = (unsigned char *)malloc(cells ? cells : 1);
+    sh->counts[k] = (unsigned long long *)calloc(be * S * S + 1, sizeof(unsigned long long));
+    sh->units[k] = (unsigned long long *)calloc(be * R * S + 1, sizeof(unsigned long long));
+    sh->dwell[k] = (double *)calloc(be * S + 1, sizeof(double));
+    sh->total[k] = (double *)calloc(be ? be : 1, sizeof(double));
+    sh->dropped_edges[k] = (unsigned long long *)calloc(be ? be : 1, sizeof(unsigned long long));
+    if (with_sites) sh->changes[k] = (unsigned char *)malloc(cells * E + 1);
+    if (!sh->out[k] || !sh->component[k] || !sh->counts[k] || !sh->units[k] || !sh->dwell[k] || !sh->total[k] ||
+        !sh->dropped_edges[k] || (with_sites && !sh->changes[k])) { ++k; goto nomem; }
+    ++k;
+    memset(sh->out[k - 1], 0xFF, cells * rows);
+    memset(sh->component[k - 1], 0xFF, cells);
+    if (with_sites) memset(sh->changes[k - 1], 0xFF, cells * E);
+    /* the lengths the matrices of this partition were made from */
+    for (e = 0; e < count; ++e) slen[matrix[e]] = effective_length(ev, p, matrix[e], length[e]);
+    if (device)
+    {
+      pllhip_ancsample_params_t q = *params;
+      q.flags |= PLLHIP_ANCS_COMPONENT;
+      ok = pllhip_sample_histories_edges(part, &q, root->clv_index, root->scaler_index, root->back->clv_index,
+                                         root->back->scaler_index, E, sp, sc, smx, ev->params[p], rows, ev->params[p],
+                                         slen, sh->out[k - 1], sh->component[k - 1], &sh->dropped[k - 1], sh->counts[k - 1],
+                                         sh->units[k - 1], with_sites ? sh->changes[k - 1] : NULL, sh->dropped_edges[k - 1]);
+      if (ok) T = pllhip_history_tables_create(part, E, smx, ev->params[p], slen, "sampled histories");
+      if (!ok || !T) goto fail;
+    }
+    else
+    {
+      double * A, * B;
+      unsigned int * c;
+      const pll_unode_t * saved = ev->root;
+      pllhip_ancsample_params_t q = *params;
+      size_t x;
+      q.flags = PLLHIP_ANCS_TIPS;
+      q.alphabet = NULL;
+      T = pllhip_history_tables_create(part, E, smx, ev->params[p], slen, "sampled histories");
+      if (!T) goto fail;
+      states = (unsigned char *)malloc(cells && rows ? cells * rows : 1);
+      if (!states) goto nomem;
+      memset(states, 0xFF, cells * rows);
+      ev->root = (pll_unode_t *)root;                      /* (sc_host_root_table reads the edge from ev->root) */
+      ok = sc_host_root_table(ev, p, &A, &B, &c);
+      ev->root = (pll_unode_t *)saved;
+      if (!ok) goto fail;
+      ok = as_host(part, &q, count, parent, child, matrix, A, B, ev->params[p], rows, states, sh->component[k - 1],
+                   &sh->dropped[k - 1]);
+      free(A); free(B); free(c);
+      if (!ok || !hs_host(part, params, T, E, sp, sc, smx, rows, states, sh->component[k - 1], sh->counts[k - 1],
+                          sh->units[k - 1], with_sites ? sh->changes[k - 1] : NULL, sh->dropped_edges[k - 1])) goto nomem;
+      /* the rows the caller asked for, in the caller's alphabet */
+      for (x = 0; x < cells * rows; ++x)
+      {
+        const size_t row = x / part->sites % rows;
+        if (states[x] == 0xFF || (row < part->tips && !(params->flags & PLLHIP_ANCS_TIPS))) continue;
+        sh->out[k - 1][x] = params->alphabet ? (unsigned char)params->alphabet[states[x]] : states[x];
+      }
+      free(states); states = NULL;
+    }
+    cd = (double *)malloc(sizeof(double) * (S * S + 1));
+    if (!cd) goto nomem;
+    for (i = 0; i < params->replicates; ++i)
+      for (e = 0; e < E; ++e)
+      {
+        const size_t x = (size_t)i * E + e;
+        if (!pllhip_history_summary(part->states, part->rate_cats, T->tau + (size_t)e * R, sh->counts[k - 1] + x * S * S,
+                                    sh->units[k - 1] + x * R * S, cd, sh->dwell[k - 1] + x * S, &sh->total[k - 1][x]))
+          goto fail;
+      }
+    free(cd); cd = NULL;
+    pllhip_history_tables_destroy(T); T = NULL;
+  }
+  free(parent); free(child); free(matrix); free(length); free(sp); free(slen);
+  return sh;
+nomem:
+  pllhip_eval_error(PLL_ERROR_MEM_ALLOC, "Cannot allocate the sampled histories");
+fail:
+  if (!pll_errno) pllhip_eval_error(PLL_ERROR_PARAM_INVALID, "sampled histories: the call failed");
+  free(parent); free(child); free(matrix); free(length); free(sp); free(slen); free(states); free(cd);
+  pllhip_history_tables_destroy(T);
+  pllhip_eval_destroy_sampled_histories(sh);
   return NULL;
 }
 

@@ -28,43 +28,6 @@ constexpr unsigned ANCS_WG = 256;
 constexpr unsigned ANCS_RC = 8;                 // replicates of a group: their bytes fill a 64-bit word
 constexpr unsigned ANCS_NO = ~0u;
 
-// pick(u total, cum) over the n masses term(0) .. term(n - 1), cumulated left to right from 0.0: the bisection of
-// sim_pick.  The table is never stored: where no mass is negative the running sums do not fall, and the bisection ends
-// at the number of s in 0 .. n - 2 whose sum is not above the draw; otherwise the bisection is walked as it stands,
-// every probe cumulated anew (the same additions, hence the same sums).
-template <class Term> __device__ inline unsigned ancs_pick(unsigned n, double u, Term term)
-{
-  double total = 0.0;
-  bool monotone = true;
-  for (unsigned s = 0; s < n; ++s)
-  {
-    const double m = term(s);
-    monotone = monotone && m >= 0.0;
-    total = total + m;
-  }
-  const double x = u * total;
-  if (monotone)
-  {
-    double acc = 0.0;
-    unsigned s = 0;
-    for (; s + 1 < n; ++s)
-    {
-      acc = acc + term(s);
-      if (acc > x) break;
-    }
-    return s;
-  }
-  unsigned lo = 0, hi = n - 1;
-  while (lo < hi)
-  {
-    const unsigned mid = (lo + hi) >> 1;
-    double acc = 0.0;
-    for (unsigned s = 0; s <= mid; ++s) acc = acc + term(s);
-    if (acc > x) hi = mid; else lo = mid + 1;
-  }
-  return lo;
-}
-
 // grid: x over (tile, group) pairs, any size.  Dynamic LDS: [slots][ANCS_WG] 64-bit words, 256 bytes of alphabet.
 __global__ __launch_bounds__(ANCS_WG) void k_ancsample_walk(AncsOperands O, AncsLaunch L)
 {

@@ -60,22 +60,25 @@ bool invalid(const char * who, const std::string & what)
 
 } // namespace
 
-extern "C" {
-
-PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const pllhip_ancsample_params_t * params,
-                                             unsigned int root_node, int root_scaler, unsigned int other_node,
-                                             int other_scaler, unsigned int edge_count, const unsigned int * parent,
-                                             const unsigned int * child, const unsigned int * matrix_indices,
-                                             const unsigned int * freqs_indices, unsigned int node_count,
-                                             unsigned char * out, unsigned char * component, unsigned long long * dropped)
+// The draw behind pllhip_sample_ancestral_edges.  With a hook (device_job.hpp, AncsStageHook) every staging half holds
+// state indices in all rows, tips included, the component row and the hook's extra rows, and the hook works on it on
+// the partition's stream before it is copied out; the caller's rows, flags and alphabet are served on the host, so
+// that `out` and `component` (either may then be NULL) hold what the call without a hook returns.
+int pllhip::ancsample_run(const char * who, pll_partition_t * partition, const pllhip_ancsample_params_t * params,
+                          unsigned int root_node, int root_scaler, unsigned int other_node, int other_scaler,
+                          unsigned int edge_count, const unsigned int * parent, const unsigned int * child,
+                          const unsigned int * matrix_indices, const unsigned int * freqs_indices,
+                          unsigned int node_count, unsigned char * out, unsigned char * component,
+                          unsigned long long * dropped, AncsStageHook * hook, double * times_ms)
 {
-  const char * who = "pllhip_sample_ancestral_edges";
-  if (!partition || !partition->engine || !params || !freqs_indices || !out)
+  if (!partition || !partition->engine || !params || !freqs_indices || (!out && !hook))
     return invalid(who, "the partition, the parameters, freqs_indices or the output is NULL");
   if (edge_count && (!parent || !child || !matrix_indices)) return invalid(who, "the edge list is NULL");
-  if (params->flags & ~(unsigned)(PLLHIP_ANCS_TIPS | PLLHIP_ANCS_COMPONENT)) return invalid(who, "unknown flags");
-  const bool with_tips = (params->flags & PLLHIP_ANCS_TIPS) != 0, with_comp = (params->flags & PLLHIP_ANCS_COMPONENT) != 0;
-  if (with_comp && !component) return invalid(who, "PLLHIP_ANCS_COMPONENT without a component array");
+  const unsigned known = PLLHIP_ANCS_TIPS | PLLHIP_ANCS_COMPONENT | (hook ? hook->flags : 0u);
+  if (params->flags & ~known) return invalid(who, "unknown flags");
+  const bool ask_tips = (params->flags & PLLHIP_ANCS_TIPS) != 0, ask_comp = (params->flags & PLLHIP_ANCS_COMPONENT) != 0;
+  const bool with_tips = ask_tips || hook, with_comp = ask_comp || hook;
+  if (ask_comp && !component) return invalid(who, "PLLHIP_ANCS_COMPONENT without a component array");
   if (!params->replicates) return invalid(who, "replicates is 0");
   if ((u64)params->first_replicate + params->replicates > (1ULL << 32))
     return invalid(who, "first_replicate + replicates exceeds 2^32");
@@ -120,7 +123,9 @@ PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const 
   if (!check_category_weights(partition->rate_weights, R, who)) return PLL_FAILURE;
   if (!N) { if (dropped) *dropped = 0; return PLL_SUCCESS; }
 
-  const unsigned rows = node_count + (with_comp ? 1u : 0u), comp_row = with_comp ? node_count : ANCS_NONE;
+  const unsigned extra_row = node_count + 1u;        // the first row of the hook's own
+  const unsigned rows = node_count + (with_comp ? 1u : 0u) + (hook ? hook->extra_rows : 0u);
+  const unsigned comp_row = with_comp ? node_count : ANCS_NONE;
   auto row_of = [&](unsigned node) { return node >= tips || with_tips ? node : ANCS_NONE; };
   const size_t lds = (size_t)plan.slots * ANCS_TILE * sizeof(u64) + 256;
   if (lds > (64u << 10)) return invalid(who, "the tree needs more slots than the LDS of a workgroup holds");
@@ -129,13 +134,14 @@ PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const 
   const u64 budget = env_u64("PLLHIP_ANCS_STAGING_BYTES", ANCS_DEFAULT_STAGING);
   const u64 half = std::max<u64>(budget / 2, (u64)rows * ANCS_TILE);
   const u64 per_pass = std::min<u64>(ANCS_GROUP, env_u64("PLLHIP_ANCS_REPLICATES", ANCS_GROUP));
+  const u64 rep_cap = hook && hook->chunk_replicates ? hook->chunk_replicates : ~0ULL;
   const u64 sites = N, full_pitch = (sites + 3) & ~3ULL;
   u64 chunk_reps = 1, chunk_cols = sites;
   if ((u64)rows * full_pitch <= half)
   {
     const u64 tiles = (sites + ANCS_TILE - 1) / ANCS_TILE;
     chunk_reps = std::max<u64>(1, std::min<u64>({(u64)params->replicates, half / ((u64)rows * full_pitch),
-                                                 ANCS_MAX_ITEMS / tiles}));
+                                                 ANCS_MAX_ITEMS / tiles, rep_cap}));
   }
   else
     chunk_cols = std::max<u64>(ANCS_TILE, half / rows / ANCS_TILE * ANCS_TILE);
@@ -181,8 +187,12 @@ PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const 
   }
 
   // the tables of the call
-  uint8_t h_alpha[256];
+  uint8_t h_alpha[256], h_ident[256];
   for (unsigned s = 0; s < 256; ++s) h_alpha[s] = (uint8_t)(params->alphabet && s < S ? params->alphabet[s] : s);
+  for (unsigned s = 0; s < 256; ++s) h_ident[s] = (uint8_t)s;
+  uint8_t h_lut[256];                                  // with a hook the host maps; 0xFF stays 0xFF, as in the kernel
+  memcpy(h_lut, h_alpha, 256);
+  h_lut[255] = 255;
   const size_t plane = ((size_t)N + 1) & ~(size_t)1;
   SiteCatPlanes planes;
   planes.A = j.alloc<double>((size_t)R * plane, "site-category table");
@@ -194,19 +204,20 @@ PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const 
   AncsStep * d_steps = j.alloc<AncsStep>(steps.size(), "edge program");
   uint8_t * d_alpha = j.alloc<uint8_t>(256, "alphabet");
   uint8_t * d_half[2] = {nullptr, nullptr}, * h_half[2] = {nullptr, nullptr};
-  hipEvent_t k0[2], k1[2], c0[2], c1[2];
+  hipEvent_t k0[2], k1[2], c0[2], c1[2], w1[2] = {nullptr, nullptr};
   bool ok = planes.A && (!pinv || planes.B) && planes.c && d_m && d_dropped && d_steps && d_alpha;
   for (unsigned h = 0; ok && h < nhalves; ++h)
   {
     d_half[h] = j.alloc<uint8_t>(half_bytes, "the staging buffer");
     h_half[h] = j.pinned<uint8_t>(half_bytes);
     k0[h] = j.event(); k1[h] = j.event(); c0[h] = j.event(); c1[h] = j.event();
-    ok = d_half[h] && h_half[h] && k0[h] && k1[h] && c0[h] && c1[h];
+    if (hook) w1[h] = j.event();
+    ok = d_half[h] && h_half[h] && k0[h] && k1[h] && c0[h] && c1[h] && (!hook || w1[h]);
   }
   if (!ok) return PLL_FAILURE;
   // (pageable sources: the runtime stages them before it returns)
   if (!j.upload(d_steps, steps.data(), steps.size(), "upload edge program") ||
-      !j.upload(d_alpha, h_alpha, 256, "upload alphabet") ||
+      !j.upload(d_alpha, hook ? h_ident : h_alpha, 256, "upload alphabet") ||
       !j.upload(d_m, partition->pattern_weights, N, "upload pattern weights") ||
       !hip_ok(hipMemsetAsync(d_dropped, 0, sizeof(u64), j.stream), "hipMemsetAsync"))
     return PLL_FAILURE;
@@ -215,9 +226,18 @@ PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const 
     return PLL_FAILURE;
   hipEvent_t t1 = j.mark();
   if (!t1) return PLL_FAILURE;
+  if (hook && !hook->prepare(j, ops.cu_count, d_m)) return PLL_FAILURE;
 
   const size_t out_rows = node_count;
-  double kernel_ms = 0.0, copy_ms = 0.0;
+  double kernel_ms = 0.0, copy_ms = 0.0, hook_ms = 0.0;
+  auto staged = [&](const Chunk & c, uint8_t * half) {
+    AncsStaged s;
+    s.half = half;
+    s.rep0 = c.rep0; s.reps = c.reps; s.col0 = c.col0; s.cols = c.cols;
+    s.rows = rows; s.comp_row = comp_row; s.extra_row = extra_row;
+    s.pitch = c.pitch;
+    return s;
+  };
 
   // chunk q is in pinned half q & 1: wait for its copy, then put its rows where the caller wants them
   auto deliver = [&](size_t q) -> bool {
@@ -227,15 +247,28 @@ PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const 
     if (!hip_ok(hipEventSynchronize(c1[h]), "copy of a staging chunk") || !j.elapsed(k0[h], k1[h], &km) ||
         !j.elapsed(c0[h], c1[h], &cm))
       return false;
+    if (hook)
+    {
+      float wm = 0.f;
+      if (!j.elapsed(k0[h], w1[h], &wm)) return false;
+      hook_ms += km - wm;
+      km = wm;
+    }
     kernel_ms += km;
     const auto begin = std::chrono::steady_clock::now();
     for (unsigned r = 0; r < c.reps; ++r)
     {
       const uint8_t * src = h_half[h] + (size_t)r * rows * c.pitch;
-      for (size_t row = 0; row < out_rows; ++row)
-        memcpy(out + ((size_t)(c.rep0 + r) * out_rows + row) * sites + c.col0, src + row * c.pitch, c.cols);
-      if (with_comp) memcpy(component + (size_t)(c.rep0 + r) * sites + c.col0, src + (size_t)comp_row * c.pitch, c.cols);
+      for (size_t row = 0; out && row < out_rows; ++row)
+      {
+        uint8_t * dst = out + ((size_t)(c.rep0 + r) * out_rows + row) * sites + c.col0;
+        if (!hook) memcpy(dst, src + row * c.pitch, c.cols);
+        else if (row < tips && !ask_tips) memset(dst, 0xff, c.cols);
+        else for (unsigned x = 0; x < c.cols; ++x) dst[x] = h_lut[src[row * c.pitch + x]];
+      }
+      if (ask_comp) memcpy(component + (size_t)(c.rep0 + r) * sites + c.col0, src + (size_t)comp_row * c.pitch, c.cols);
     }
+    if (hook) hook->deliver(staged(c, h_half[h]));
     copy_ms += cm + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - begin).count();
     return true;
   };
@@ -275,7 +308,9 @@ PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const 
     const unsigned grid = (unsigned)std::max<u64>(1, block_cap ? std::min(wanted, block_cap) : wanted);
     if (!hip_ok(hipEventRecord(k0[h], j.stream), "hipEventRecord") ||
         !hip_ok(hipMemsetAsync(d_half[h], 0xff, (size_t)c.reps * rows * c.pitch, j.stream), "hipMemsetAsync") ||
-        !ancsample_walk(partition, ops, L, grid) || !hip_ok(hipEventRecord(k1[h], j.stream), "hipEventRecord") ||
+        !ancsample_walk(partition, ops, L, grid) ||
+        (hook && (!hip_ok(hipEventRecord(w1[h], j.stream), "hipEventRecord") || !hook->launch(j, staged(c, d_half[h])))) ||
+        !hip_ok(hipEventRecord(k1[h], j.stream), "hipEventRecord") ||
         !hip_ok(hipStreamWaitEvent(copy.s, k1[h], 0), "hipStreamWaitEvent") ||
         !hip_ok(hipEventRecord(c0[h], copy.s), "hipEventRecord") ||
         !hip_ok(hipMemcpyAsync(h_half[h], d_half[h], (size_t)c.reps * rows * c.pitch, hipMemcpyDeviceToHost, copy.s),
@@ -290,12 +325,32 @@ PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const 
   if (!j.download(&h_dropped, d_dropped, 1, "download") || !hip_ok(hipStreamSynchronize(j.stream), "download") ||
       !j.elapsed(t0, t1, &tm))
     return PLL_FAILURE;
+  if (hook && !hook->finish(j)) return PLL_FAILURE;
   if (dropped) *dropped = h_dropped;
+  if (times_ms)
+  {
+    times_ms[0] = tm; times_ms[1] = kernel_ms; times_ms[2] = hook_ms; times_ms[3] = copy_ms;
+    return PLL_SUCCESS;
+  }
   g_ancs_ms[0] = tm;
   g_ancs_ms[1] = kernel_ms;
   g_ancs_ms[2] = copy_ms;
   g_ancs_chunks = chunks.size();
   return PLL_SUCCESS;
+}
+
+extern "C" {
+
+PLL_EXPORT int pllhip_sample_ancestral_edges(pll_partition_t * partition, const pllhip_ancsample_params_t * params,
+                                             unsigned int root_node, int root_scaler, unsigned int other_node,
+                                             int other_scaler, unsigned int edge_count, const unsigned int * parent,
+                                             const unsigned int * child, const unsigned int * matrix_indices,
+                                             const unsigned int * freqs_indices, unsigned int node_count,
+                                             unsigned char * out, unsigned char * component, unsigned long long * dropped)
+{
+  return ancsample_run("pllhip_sample_ancestral_edges", partition, params, root_node, root_scaler, other_node,
+                       other_scaler, edge_count, parent, child, matrix_indices, freqs_indices, node_count, out, component,
+                       dropped, nullptr, nullptr);
 }
 
 PLL_EXPORT void pllhip_ancsample_last_times(double * table_ms, double * kernel_ms, double * copy_ms,

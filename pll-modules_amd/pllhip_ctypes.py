@@ -180,7 +180,9 @@ pllhip_eval_set_partition_branch_length pllhip_eval_set_transient
 pllhip_eval_site_rates pllhip_eval_destroy_site_rates pllhip_eval_optimize_rate_weights
 pllhip_eval_rate_weights_trail
 pllhip_substmap_counts pllhip_eval_substitution_map pllhip_eval_destroy_substitution_map
-pllhip_eval_sample_ancestral pllhip_eval_destroy_sampled_ancestral""".split()
+pllhip_eval_sample_ancestral pllhip_eval_destroy_sampled_ancestral
+pllhip_history_rate_table pllhip_history_poisson pllhip_history_summary
+pllhip_eval_sample_histories pllhip_eval_destroy_sampled_histories""".split()
 
 PLLHIP_H_FUNCTIONS = """pllhip_device_count pllhip_set_device pllhip_get_device
 pllhip_device_arch pllhip_eigen_decompose pllhip_sync_to_host pllhip_sync_to_device pllhip_get_clv
@@ -216,7 +218,8 @@ pllhip_sitecat_edge pllhip_sitecat_from_table pllhip_sitecat_destroy pllhip_site
 pllhip_sitecat_table pllhip_sitecat_posteriors pllhip_site_posteriors_destroy pllhip_sitecat_em_weights
 pllhip_sitecat_last_times
 pllhip_substmap_edge pllhip_edge_pairs_destroy pllhip_substmap_last_times
-pllhip_sample_ancestral_edges pllhip_sample_ancestral_utree pllhip_ancsample_last_times""".split()
+pllhip_sample_ancestral_edges pllhip_sample_ancestral_utree pllhip_ancsample_last_times
+pllhip_sample_histories_edges pllhip_sample_histories_utree pllhip_history_last_times""".split()
 
 
 def _u32(a):
@@ -407,6 +410,29 @@ class SampledAncestral:
     [replicates][sites], dropped, clv_index [rows]"""
 
 
+PLLHIP_HIST_SITES, PLLHIP_HIST_MAX_TABLE = 1 << 8, 1024
+
+
+class SampledHistoriesResult(C.Structure):
+    """pllhip_sampled_histories_t, include/pllhip_eval.h"""
+    _fields_ = [("partition_count", C.c_uint), ("node_count", C.c_uint), ("replicates", C.c_uint),
+                ("branch_count", C.c_uint), ("partition_indices", C.POINTER(C.c_uint)), ("sites", C.POINTER(C.c_uint)),
+                ("states", C.POINTER(C.c_uint)), ("cats", C.POINTER(C.c_uint)), ("clv_index", C.POINTER(C.c_uint)),
+                ("out", C.POINTER(C.POINTER(C.c_ubyte))), ("component", C.POINTER(C.POINTER(C.c_ubyte))),
+                ("dropped", C.POINTER(C.c_ulonglong)), ("counts", C.POINTER(C.POINTER(C.c_ulonglong))),
+                ("units", C.POINTER(C.POINTER(C.c_ulonglong))), ("dwell", C.POINTER(C.POINTER(C.c_double))),
+                ("total", C.POINTER(C.POINTER(C.c_double))), ("dropped_edges", C.POINTER(C.POINTER(C.c_ulonglong))),
+                ("changes", C.POINTER(C.POINTER(C.c_ubyte)))]
+
+
+class SampledHistories:
+    """one local partition of pllhip_eval_sample_histories, branches by pmatrix_index: out uint8
+    [replicates][rows][sites], component [replicates][sites], dropped, clv_index [rows], counts uint64
+    [replicates][branches][S][S], units uint64 [replicates][branches][R][S], dwell [replicates][branches][S], total
+    [replicates][branches], dropped_edges uint64 [replicates][branches], changes uint8 [replicates][branches][sites] or
+    None"""
+
+
 class Rell:
     """numpy copy of a pllhip_rell_result_t: trees, replicates, best, batch, lnl, bp_count, kh_count, sh_count, elw,
     R [replicates][trees] or None, times = (draw, product, statistics) in ms"""
@@ -560,6 +586,17 @@ class PllLib:
                 L.pllhip_eval_sample_ancestral.argtypes = [C.c_void_p, C.POINTER(AncSampleParams)]
                 L.pllhip_eval_destroy_sampled_ancestral.restype = None
                 L.pllhip_eval_destroy_sampled_ancestral.argtypes = [C.POINTER(SampledAncestralResult)]
+            if hasattr(L, "pllhip_eval_sample_histories"):
+                ull_p = C.POINTER(C.c_ulonglong)
+                L.pllhip_history_rate_table.argtypes = [C.c_uint, C.c_uint, c_double_p, c_double_p, c_double_p, C.c_uint,
+                                                        c_double_p, c_double_p]
+                L.pllhip_history_poisson.argtypes = [C.c_double, c_double_p, c_uint_p]
+                L.pllhip_history_summary.argtypes = [C.c_uint, C.c_uint, c_double_p, ull_p, ull_p, c_double_p, c_double_p,
+                                                     c_double_p]
+                L.pllhip_eval_sample_histories.restype = C.POINTER(SampledHistoriesResult)
+                L.pllhip_eval_sample_histories.argtypes = [C.c_void_p, C.POINTER(AncSampleParams)]
+                L.pllhip_eval_destroy_sampled_histories.restype = None
+                L.pllhip_eval_destroy_sampled_histories.argtypes = [C.POINTER(SampledHistoriesResult)]
             if hasattr(L, "pllhip_eval_substitution_map"):
                 L.pllhip_substmap_counts.argtypes = [C.c_uint, C.c_uint, c_double_p, c_double_p, c_double_p, C.c_double,
                                                      c_double_p, c_double_p, c_double_p]
@@ -730,6 +767,16 @@ class PllLib:
             L.pllhip_sample_ancestral_utree.argtypes = [pp, C.POINTER(AncSampleParams), up, c_uint_p, ubyte_p, ubyte_p, ull_p]
             L.pllhip_ancsample_last_times.restype = None
             L.pllhip_ancsample_last_times.argtypes = [c_double_p, c_double_p, c_double_p, ull_p]
+        if hasattr(L, "pllhip_sample_histories_edges"):
+            ubyte_p, ull_p = C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong)
+            L.pllhip_sample_histories_edges.argtypes = [pp, C.POINTER(AncSampleParams), C.c_uint, C.c_int, C.c_uint, C.c_int,
+                                                        C.c_uint, c_uint_p, c_uint_p, c_uint_p, c_uint_p, C.c_uint,
+                                                        c_uint_p, c_double_p, ubyte_p, ubyte_p, ull_p, ull_p, ull_p,
+                                                        ubyte_p, ull_p]
+            L.pllhip_sample_histories_utree.argtypes = [pp, C.POINTER(AncSampleParams), up, c_uint_p, c_uint_p, ubyte_p,
+                                                        ubyte_p, ull_p, ull_p, ull_p, ubyte_p, ull_p, c_uint_p, c_uint_p]
+            L.pllhip_history_last_times.restype = None
+            L.pllhip_history_last_times.argtypes = [c_double_p, c_double_p, c_double_p, c_double_p]
         if hasattr(L, "pllhip_msa_compute_stats"):
             L.pllhip_empirical_frequencies.restype = c_double_p
             L.pllhip_empirical_frequencies.argtypes = [pp]
@@ -2103,6 +2150,125 @@ def ancsample_last_times(lib):
     return a.value, b.value, c.value, n.value
 
 
+def history_rate_table(lib, eigenvecs, inv_eigenvecs, eigenvals, K, states=None):
+    """pllhip_history_rate_table -> (mu, Rpow [K][S][S]); eigenvecs / inv_eigenvecs [S][Sp] in libpll's storage"""
+    ev, iv, ew = _f64(eigenvecs), _f64(inv_eigenvecs), _f64(eigenvals)
+    S, Sp = (ev.shape[0] if states is None else states), ev.shape[1]
+    mu, rpow = C.c_double(0.0), np.zeros((max(K, 1), S, S))
+    lib.errno = 0
+    if not lib.lib.pllhip_history_rate_table(S, Sp, ev.ctypes.data_as(c_double_p), iv.ctypes.data_as(c_double_p),
+                                             ew.ctypes.data_as(c_double_p), K, C.byref(mu), rpow.ctypes.data_as(c_double_p)):
+        raise RuntimeError(f"[{lib.errno}] {lib.errmsg}")
+    return mu.value, rpow
+
+
+def history_poisson(lib, lam):
+    """pllhip_history_poisson -> pois [K]"""
+    pois, K = np.zeros(PLLHIP_HIST_MAX_TABLE), C.c_uint(0)
+    lib.errno = 0
+    if not lib.lib.pllhip_history_poisson(lam, pois.ctypes.data_as(c_double_p), C.byref(K)):
+        raise RuntimeError(f"[{lib.errno}] {lib.errmsg}")
+    return pois[:K.value].copy()
+
+
+def history_summary(lib, tau, counts_int, units):
+    """pllhip_history_summary of one (replicate, branch): counts_int uint64 [S][S], units uint64 [R][S], tau [R] ->
+    (counts [S][S], dwell [S], total)"""
+    ull_p = C.POINTER(C.c_ulonglong)
+    tau = _f64(tau)
+    ci, un = np.ascontiguousarray(counts_int, dtype=np.uint64), np.ascontiguousarray(units, dtype=np.uint64)
+    S, R = ci.shape[0], un.shape[0]
+    counts, dwell, total = np.zeros((S, S)), np.zeros(S), C.c_double(0.0)
+    lib.errno = 0
+    if not lib.lib.pllhip_history_summary(S, R, tau.ctypes.data_as(c_double_p), ci.ctypes.data_as(ull_p),
+                                          un.ctypes.data_as(ull_p), counts.ctypes.data_as(c_double_p),
+                                          dwell.ctypes.data_as(c_double_p), C.byref(total)):
+        raise RuntimeError(f"[{lib.errno}] {lib.errmsg}")
+    return counts, dwell, total.value
+
+
+class Histories:
+    """what pllhip_sample_histories_* returns, edges in the order of the list: out uint8 [replicates][node_count][sites],
+    component [replicates][sites], dropped, counts uint64 [replicates][edges][S][S], units uint64
+    [replicates][edges][R][S], changes uint8 [replicates][edges][sites] or None, dropped_edges uint64
+    [replicates][edges], and for the utree form edge_matrix [edges]"""
+
+
+def sample_histories_edges(inst, root_edge, parent, child, matrix, lengths, seed, replicates=1, first_replicate=0, flags=0,
+                           alphabet=None, node_count=None, freqs_indices=None, params_indices=None, want_out=True,
+                           want_component=True, fill=0):
+    """pllhip_sample_histories_edges on an Instance whose vectors point towards root_edge = (root node, root scaler,
+    other node, other scaler) -> Histories; raises RuntimeError with the library's message, with h.partial holding the
+    arrays as the call left them (initialised to `fill`)."""
+    pa, ch, mi = _u32(parent), _u32(child), _u32(matrix)
+    ln = None if lengths is None else _f64(lengths)
+    nodes = inst.tips + inst.p.contents.clv_buffers if node_count is None else node_count
+    S, R, E = inst.p.contents.states, inst.p.contents.rate_cats, len(pa)
+    h = Histories()
+    h.out = np.full((replicates, nodes, inst.N), fill, dtype=np.uint8) if want_out else None
+    h.component = np.full((replicates, inst.N), fill, dtype=np.uint8) if want_component else None
+    h.counts = np.full((replicates, E, S, S), fill, dtype=np.uint64)
+    h.units = np.full((replicates, E, R, S), fill, dtype=np.uint64)
+    h.changes = np.full((replicates, E, inst.N), fill, dtype=np.uint8) if flags & PLLHIP_HIST_SITES else None
+    h.dropped_edges = np.full((replicates, E), fill, dtype=np.uint64)
+    prm = _ancs_params(seed, replicates, first_replicate, flags, alphabet)
+    fidx = inst.params if freqs_indices is None else _u32(freqs_indices)
+    pidx = inst.params if params_indices is None else _u32(params_indices)
+    dropped = C.c_ulonglong(0)
+    ubyte_p, ull_p = C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong)
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    rn, rs, on, os_ = root_edge
+    if not inst.L.pllhip_sample_histories_edges(inst.p, C.byref(prm), rn, rs, on, os_, E, ptr(pa, c_uint_p),
+                                                ptr(ch, c_uint_p), ptr(mi, c_uint_p), ptr(fidx, c_uint_p), nodes,
+                                                ptr(pidx, c_uint_p), ptr(ln, c_double_p), ptr(h.out, ubyte_p),
+                                                ptr(h.component, ubyte_p), C.byref(dropped), ptr(h.counts, ull_p),
+                                                ptr(h.units, ull_p), ptr(h.changes, ubyte_p), ptr(h.dropped_edges, ull_p)):
+        err = RuntimeError(inst.lib.errmsg)
+        err.partial = h
+        raise err
+    h.dropped = dropped.value
+    return h
+
+
+def sample_histories_utree(inst, root, seed, replicates=1, first_replicate=0, flags=0, alphabet=None):
+    """pllhip_sample_histories_utree from `root` (a POINTER(UNode) at an inner node) -> Histories with edge_matrix"""
+    nodes = inst.tips + inst.p.contents.clv_buffers
+    S, R = inst.p.contents.states, inst.p.contents.rate_cats
+    h = Histories()
+    h.out = np.zeros((replicates, nodes, inst.N), dtype=np.uint8)
+    h.component = np.zeros((replicates, inst.N), dtype=np.uint8)
+    counts = np.zeros((replicates, nodes, S, S), dtype=np.uint64)          # (a tree has fewer edges than vectors)
+    units = np.zeros((replicates, nodes, R, S), dtype=np.uint64)
+    changes = np.zeros((replicates, nodes, inst.N), dtype=np.uint8) if flags & PLLHIP_HIST_SITES else None
+    dropped_edges = np.zeros((replicates, nodes), dtype=np.uint64)
+    edge_matrix, E = np.zeros(nodes, dtype=np.uint32), C.c_uint(0)
+    prm = _ancs_params(seed, replicates, first_replicate, flags, alphabet)
+    dropped = C.c_ulonglong(0)
+    ubyte_p, ull_p = C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong)
+    if not inst.L.pllhip_sample_histories_utree(inst.p, C.byref(prm), root, inst.params_p, inst.params_p,
+                                                h.out.ctypes.data_as(ubyte_p), h.component.ctypes.data_as(ubyte_p),
+                                                C.byref(dropped), counts.ctypes.data_as(ull_p), units.ctypes.data_as(ull_p),
+                                                None if changes is None else changes.ctypes.data_as(ubyte_p),
+                                                dropped_edges.ctypes.data_as(ull_p), C.byref(E),
+                                                edge_matrix.ctypes.data_as(c_uint_p)):
+        raise RuntimeError(inst.lib.errmsg)
+    E = E.value
+    # the library fills [replicates][E][...] densely from the start of each array
+    h.counts = counts.reshape(-1)[:replicates * E * S * S].reshape(replicates, E, S, S).copy()
+    h.units = units.reshape(-1)[:replicates * E * R * S].reshape(replicates, E, R, S).copy()
+    h.changes = None if changes is None else changes.reshape(-1)[:replicates * E * inst.N].reshape(replicates, E, inst.N).copy()
+    h.dropped_edges = dropped_edges.reshape(-1)[:replicates * E].reshape(replicates, E).copy()
+    h.edge_matrix, h.dropped = edge_matrix[:E].copy(), dropped.value
+    return h
+
+
+def history_last_times(lib):
+    """(table_ms, walk_ms, history_ms, copy_ms) of this thread's last pllhip_sample_histories_edges"""
+    t = [C.c_double(0.0) for _ in range(4)]
+    lib.lib.pllhip_history_last_times(*[C.byref(x) for x in t])
+    return tuple(x.value for x in t)
+
+
 def state_charmap(nstates):
     """a 256-entry char -> mask map where byte value 48+i ('0'+i) means state i and
     '-' means every state (so uint8 state arrays + 48 are valid sequences)"""
@@ -2312,6 +2478,39 @@ class Evaluation:
             return out
         finally:
             self.L.pllhip_eval_destroy_sampled_ancestral(ptr)
+
+    def sample_histories(self, seed, replicates=1, first_replicate=0, flags=0, alphabet=None):
+        """pllhip_eval_sample_histories -> [SampledHistories per local partition] (numpy copies)"""
+        self.lib.errno = 0
+        prm = _ancs_params(seed, replicates, first_replicate, flags, alphabet)
+        ptr = self.L.pllhip_eval_sample_histories(self.ev, C.byref(prm))
+        if not ptr:
+            raise RuntimeError(f"[{self.lib.errno}] {self.lib.errmsg}")
+        try:
+            res, out = ptr.contents, []
+            rows, reps, E = res.node_count, res.replicates, res.branch_count
+
+            def arr(p, shape, dtype):
+                n = int(np.prod(shape))
+                return np.ctypeslib.as_array(p, shape=(n,)).reshape(shape).copy() if n else np.zeros(shape, dtype)
+
+            for k in range(res.partition_count):
+                o, N, S, R = SampledHistories(), res.sites[k], res.states[k], res.cats[k]
+                o.partition = res.partition_indices[k]
+                o.clv_index = np.array([res.clv_index[i] for i in range(rows)], dtype=np.uint32)
+                o.out = arr(res.out[k], (reps, rows, N), np.uint8)
+                o.component = arr(res.component[k], (reps, N), np.uint8)
+                o.dropped = res.dropped[k]
+                o.counts = arr(res.counts[k], (reps, E, S, S), np.uint64)
+                o.units = arr(res.units[k], (reps, E, R, S), np.uint64)
+                o.dwell = arr(res.dwell[k], (reps, E, S), np.float64)
+                o.total = arr(res.total[k], (reps, E), np.float64)
+                o.dropped_edges = arr(res.dropped_edges[k], (reps, E), np.uint64)
+                o.changes = arr(res.changes[k], (reps, E, N), np.uint8) if res.changes else None
+                out.append(o)
+            return out
+        finally:
+            self.L.pllhip_eval_destroy_sampled_histories(ptr)
 
     def substitution_map(self, flags=0):
         """pllhip_eval_substitution_map -> [[BranchSubst per branch, by pmatrix_index] per local partition]"""
